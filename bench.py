@@ -2,6 +2,8 @@
 """bench.py -- the render path's headline benchmark: Msamples/s (+ FPS) at 1920x1080 on the lego-like snapshot.
 
     python bench.py --gpus 1 --steps 8 --warmup 2
+    python bench.py --gpus 1 --full                          # + secondary workloads, next_rows, live PMC traffic, CPU baseline
+    python bench.py --gpus 1 --steps 8 --dump-outputs DIR    # + the last timed step's frame / depth as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full frame: clear -> nrs_render_nerf (one persistent HIP launch) [-> RCCL gather of the image tiles to
@@ -9,8 +11,13 @@ rank 0 + de-tile when N > 1].  The camera orbits (azimuth = 45 deg * step) so st
 All inputs (parameters, bitfield, cage tables) are resident in HBM before the timed region.  With N > 1 the SAME frame
 is cut into 32x32 tiles dealt round-robin to the ranks ("scaling": "strong": total work per step is fixed).
 
+A plain run does only what the headline needs: set up, count the samples of the 8 views, warm up, time --steps frames, print
+the line (`roofline.traffic` is then the recorded figure of profiles/).  Everything else -- the secondary workloads and
+pipelined legs, next_rows, the live rocprofv3 traffic passes, the CPU baseline, and at N > 1 the N = 1 reference, the
+exchange alone and the gathered-frame check -- runs with --full (--no-extra / --no-cpu-baseline switch parts of it off).
+
 Workloads (BASELINE.json configs): lego_cage (default; config[2]/[4]: one active cage edit -- the configuration the
-north-star target is quoted on), lego (config[1], no edit; also reported as `noedit` in the default line), garden_cage
+north-star target is quoted on), lego (config[1], no edit; also reported as `noedit` in the --full line), garden_cage
 (config[3]: aabb_scale 16, cone stepping, one cage edit).
 """
 import argparse
@@ -313,6 +320,23 @@ def live_traffic(workload, width, height):
                      f"mean of its {n_disp} render_kernel dispatches; 2 x FETCH_SIZE ({kb['FETCH_SIZE']:.0f} KB) + WRITE_SIZE ({kb['WRITE_SIZE']:.0f} KB), gfx950 correction of MI355X_MICROARCH.md")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each per-pixel array as out_dir/<name>.npy in float32.  Above `limit` bytes in all, every array keeps the same fixed sample of
+    pixels (numpy default_rng(0), ascending pixel order) as [n_sampled, channels]; at 1920x1080 the whole frame and depth fit (41.5 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    n_px = next(iter(arrays.values())).shape[0] * next(iter(arrays.values())).shape[1]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n_px, int(n_px * limit // total), replace=False))
+        arrays = {k: v.reshape(n_px, -1)[keep] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
 def time_gather(torch, dist, ctx, sharder, stream, p, frame, depth, reps, world, stats_dev):
     """The frame's exchange step alone (VERDICT r4 next #4c): `reps` x nrs_gather_tiles (ncclSend / ncclRecv of every rank's tile block to rank 0 + de-tile there) on
     `stream`, each bracketed by HIP events recorded on that stream; plus the wall clock of the `reps` calls back to back between barriers.  Every rank takes part.
@@ -354,11 +378,17 @@ def main():
     ap.add_argument("--workload", default="lego_cage", choices=["lego_cage", "lego", "garden_cage", "garden_cage_records64", "garden", "lego_cage_varied", "lego_cage_membrane", "garden_cage_norecords", "lego_cage_tcnn_numerics", "lego_cage_norecords", "lego_cage_base_1layer", "lego_cage_base_3layer", "lego_affine"])
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary no-edit measurement")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check (off: the headline line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads, legs and checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame and depth to DIR/<name>.npy (float32)")
     ap.add_argument("--frames-in-flight", type=int, default=1, help="frames rendered concurrently (double-buffered streams when > 1)")
     ap.add_argument("--gather-only", action="store_true", help="N > 1: time nrs_gather_tiles (the frame's one exchange step: RCCL send/recv to rank 0 + de-tile) alone, with HIP events; no rendering")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extra
+    cpu_leg = args.full and not args.no_cpu_baseline
 
     import torch
     import torch.distributed as dist
@@ -415,7 +445,7 @@ def main():
     # latency, during which the GPU drains -- then overlaps the start of frame k + 1, and the RCCL gather hides behind rendering.
     n_buf = max(1, args.frames_in_flight)
     tiled = world > 1 or n_buf > 1
-    max_buf = max(n_buf, 1 if args.no_extra else 4)
+    max_buf = max(n_buf, 4 if extras else 1)
     all_sharders = [tiles.TileSharder(W, H, TILE, rank, world, dev) for _ in range(max_buf)]
     all_streams = [torch.cuda.Stream(device=dev) for _ in range(max_buf)]
     frames = [torch.zeros((H, W, 4), dtype=torch.float32, device=dev) for _ in range(max_buf)]
@@ -476,6 +506,10 @@ def main():
         one_step(s, timed_idx=s)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (rank 0 holds the gathered frame), before any secondary leg reuses the buffers
+        b = (args.steps - 1) % n_buf
+        dump_outputs(args.dump_outputs, {"frame": (frames[b] if tiled else frame).cpu().numpy(), "depth": (depths[b] if tiled else depth).cpu().numpy()})
 
     local_samples = sum(samples_per_step[s % 8] for s in range(args.steps))
     kernel_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / args.steps
@@ -490,7 +524,7 @@ def main():
         total_samples = float(local_samples)
 
     extra = {}
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == "lego_cage":
+    if rank == 0 and world == 1 and extras and args.workload == "lego_cage":
         # secondary: BASELINE config[1] (no edit operators; same occupancy so the sample set is comparable)
         for s in range(2):
             one_step(s, apply_ops=False)
@@ -529,7 +563,7 @@ def main():
         extra["noedit_spp8"] = {"images_per_s": round(4 / dt, 2), "ms_per_8spp_image": round(dt / 4 * 1e3, 2), "msamples_per_s": round(ns_spp8 / dt / 1e6, 2),
                                 "note": "BASELINE configs[1] offline: 8 frames (Sobol offsets of spp_index 0..7) + nrs_accumulate per 1920x1080 image, no edits"}
 
-    if not args.no_extra:
+    if extras:
         # secondary: the same frames with 2 and with 4 in flight (all ranks take part; `value` stays the one-at-a-time figure).  The drain of
         # frame k -- one ray's latency, during which a GPU that owns only 1/N of the picture runs nearly empty -- overlaps frames k+1..;
         # a viewer that accepts that latency (or an offline render) gets this rate, DESIGN 5.
@@ -554,7 +588,7 @@ def main():
             rec = {"frames_in_flight": k, "msamples_per_s": round(total_samples / float(dtp[0]) / 1e6, 2), "fps": round(args.steps / float(dtp[0]), 2)}
             extra["pipelined" if k == 2 else "pipelined4"] = rec
 
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == "lego_cage":
+    if rank == 0 and world == 1 and extras and args.workload == "lego_cage":
         # secondary workloads, one frame at a time like `value`: BASELINE configs[3] (garden-style: aabb_scale 16, cone stepping, 5 cascades, one
         # cage edit) and the lego-like scene with non-uniform opacity (a wide distribution of ray lengths, as a trained snapshot has)
         # plus the membrane correction on (SURVEY 8d's "one extra run with it on") and the garden scene WITHOUT the 64 GB of sparse brick records
@@ -600,14 +634,14 @@ def main():
                 extra[name]["l2_misses_per_sample"] = round(tr / 128.0 / (ns / 8), 2)  # every L2 miss is one 128-byte fabric request (profiles/r02_gather_probe.md)
                 extra[name]["traffic_source"] = src
 
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == "lego_cage":
+    if rank == 0 and world == 1 and extras and args.workload == "lego_cage":
         try:
             extra["next_rows"] = next_rows(rt, synth, ctx, torch)
         except Exception as e:  # (a secondary measurement must not take the headline down)
             extra["next_rows"] = {"error": f"{type(e).__name__}: {e}"}
 
     n1_ref, gather_leg = None, None
-    if world > 1 and not args.no_extra:
+    if world > 1 and extras:
         # (VERDICT r4 next #4b) the same run's N = 1 figure: rank 0 renders the WHOLE frames alone, one at a time, while the other ranks wait at the barrier --
         # `retention_k` below = per-GPU sample throughput of the N-GPU job with k frames in flight relative to this
         sync_all()
@@ -638,7 +672,7 @@ def main():
         sync_all()
 
     gather_check = None
-    if world > 1:
+    if world > 1 and args.full:
         # the exchanged frame against the same view rendered WHOLE on rank 0 (every rank takes part in the exchange; outside the timed region): what the
         # N > 1 branch delivers is the single-GPU picture, bit for bit
         p_chk = make_params(0)
@@ -664,7 +698,7 @@ def main():
         # roofline of the dominant kernel (render_kernel): algorithmic bytes per launch / mean launch duration (HIP events)
         per_launch_samples = total_samples / args.steps / world
         traffic, traffic_source = (None, None)
-        if world == 1 and not args.no_extra:  # (the default run; the child runs it spawns carry --no-extra)
+        if world == 1 and extras:  # (--full; the child runs it spawns are plain runs)
             traffic, traffic_source = live_traffic(args.workload, W, H)
             if traffic is None:
                 why = traffic_source
@@ -752,7 +786,7 @@ def main():
                     line[f"retention_{k}"] = round(extra[key]["msamples_per_s"] / world / n1_ref["msamples_per_s"], 4)
         if gather_leg is not None:
             line["gather"] = gather_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_leg:
             line["cpu_baseline"] = cpu_baseline(synth, scene)
         print(json.dumps(line), flush=True)
 

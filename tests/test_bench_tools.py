@@ -1,7 +1,9 @@
-"""CPU-only tests of bench.py's measurement helpers (no GPU, no rocprofv3): the PMC counter parser behind `roofline.traffic`, and the recorded fall-back."""
+"""CPU-only tests of bench.py's measurement helpers (no GPU, no rocprofv3): the PMC counter parser behind `roofline.traffic`, the recorded fall-back, and --dump-outputs."""
 import json
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -39,3 +41,20 @@ def test_live_traffic_can_be_switched_off(monkeypatch):
     monkeypatch.setenv("NRS_BENCH_LIVE_TRAFFIC", "0")
     t, why = bench.live_traffic("lego_cage", 1920, 1080)
     assert t is None and "switched off" in why
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    rng = np.random.default_rng(3)
+    frame, depth = rng.random((36, 64, 4), dtype=np.float32), rng.random((36, 64), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), {"frame": frame, "depth": depth})
+    f, d = np.load(tmp_path / "whole" / "frame.npy"), np.load(tmp_path / "whole" / "depth.npy")
+    assert f.dtype == d.dtype == np.float32 and np.array_equal(f, frame) and np.array_equal(d, depth)
+    # over the limit: one fixed sample of pixels, the same rows in every array, the same sample on every call
+    limit = (frame.nbytes + depth.nbytes) // 4
+    for out in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / out), {"frame": frame, "depth": depth}, limit=limit)
+    fa, da = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert fa.nbytes + da.nbytes <= limit and fa.shape == (36 * 64 // 4, 4) and da.shape == (36 * 64 // 4, 1)
+    assert np.array_equal(fa, np.load(tmp_path / "b" / "frame.npy")) and np.array_equal(da, np.load(tmp_path / "b" / "depth.npy"))
+    rows = [int(np.flatnonzero((frame.reshape(-1, 4) == r).all(axis=1))[0]) for r in fa]
+    assert rows == sorted(rows) and np.array_equal(depth.reshape(-1)[rows], da[:, 0])

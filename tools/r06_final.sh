@@ -7,9 +7,9 @@ cd $R
 ( time timeout 1500 python -m pytest tests -x -q -m gpu ) > $OUT/gpu_tests.log 2>&1
 tail -5 $OUT/gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
-( time python bench.py ) > $OUT/bench.json 2> $OUT/bench.err
+( time python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json; tail -4 $OUT/bench.err
-python bench.py > $OUT/bench2.json 2> $OUT/bench2.err
+python bench.py --full > $OUT/bench2.json 2> $OUT/bench2.err
 if [ "$1" == "prof" ]; then
 bash tools/prof.sh lego_cage r06_final > $OUT/prof_lego.log 2>&1
 for W in lego_cage_varied lego_cage_membrane lego_cage_tcnn_numerics garden_cage_records64; do
