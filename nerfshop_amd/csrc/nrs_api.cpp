@@ -1640,7 +1640,9 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
 		const bool poisson_teams = a.any_poisson && !a.any_affine && !a.extra && m->dm.numerics == 0u;
 		const bool affine_teams = a.any_affine && !a.any_poisson && !a.extra && m->dm.numerics == 0u; // (round 6: the AFFINE instantiation of the automatic schedule)
 		const bool one_lane_only = (a.any_poisson && !poisson_teams) || (a.any_affine && !affine_teams) || a.extra;
-		if (one_lane_only || a.any_poisson) team = 1; // (fixed 2 / 4 lanes per ray exist for the default kernel only; a forced size leaves the membrane path on the catch-all)
+		// (fixed 2 / 4 lanes per ray exist for the default kernel only: a forced size leaves the membrane path on the catch-all and AffineDuplication on its
+		// one-lane instantiation -- packets sized for 8x4 / 4x4 there would send packet_pixel<1> past the owned tiles; launch_render's route check refuses it)
+		if (one_lane_only || a.any_poisson || a.any_affine) team = 1;
 		static const bool log_teams = dev_knob("NRS_TEAM_LOG") != nullptr;
 		if (log_teams) fprintf(stderr, "[nrs team] pixels=%u hit_share=%.3f busy=%u rays/lane=%.3f small-launch=%d fill lanes=%u forced=%d\n", a.pixels_owned, hit_share, busy, rays_per_lane, (int)small_launch, fill_lanes, forced);
 		static const uint32_t tail_target = []() { const char* e = dev_knob("NRS_TAIL_TARGET"); return e && atoi(e) >= 1 ? (uint32_t)std::min(atoi(e), 64) : 24u; }(); // (<= kRing - 64: the fill adds up to 64 rays per packet to a 128-entry ring) 8 / 16 / 24 / 32 / 48: 8.92 / 8.91 / 9.11 / 9.01 / 8.47 Gsamples/s

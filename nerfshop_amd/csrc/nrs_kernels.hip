@@ -1105,10 +1105,45 @@ __global__ __launch_bounds__(64 * WAVES, XTRA == 6 ? 2 : 3) __attribute__((amdgp
 	render_body<WAVES, 3, PROF, POISSON, AFFINE, TEAM, NUM, XTRA>(m_arg, a_arg);
 }
 #ifndef NRS_BODY_ONLY // (tools/one_kernel.sh compiles ONE explicit instantiation of render_kernel for register work: everything below is left out)
+// The precondition of every render launch: nrs_render_nerf sized the packets (a.team, tile_geometry) and launch_render picked the instantiation from flags of
+// its own -- the two must agree, or packet_pixel lays out pixels with another packet shape than the launch was sized for and writes past a tiled frame.
+// A route that fails it is refused (NRS_ERR_STATE) and nothing is launched.
+// route_name: the instantiation as the NRS_KERNEL_LOG line names it (occ < 0: the 128-register entry point render_kernel_c128, which has no OCC argument)
+static void route_name(char* buf, size_t n, int waves, int occ, bool prof, bool poisson, bool affine, int team, int num, int extra) {
+	char head[32];
+	if (occ < 0) snprintf(head, sizeof(head), "render_kernel_c128<%d", waves);
+	else snprintf(head, sizeof(head), "render_kernel<%d, %d", waves, occ);
+	snprintf(buf, n, "%s, prof %d, poisson %d, affine %d, team %d, num %d, extra %d>", head, (int)prof, (int)poisson, (int)affine, team, num, extra);
+}
+static int check_route(const DeviceModel& m, const RenderArgs& a, int waves, int occ, bool prof, bool poisson, bool affine, int team, int num, int extra) {
+	const bool intro = a.p.render_mode == NRS_RENDER_NORMALS || a.p.render_mode == NRS_RENDER_ENCODING_VIS;
+	const char* why = nullptr;
+	if ((int)a.team != team) why = "lanes per ray of the packet geometry (a.team) differ from TEAM";
+	else if (a.any_affine && !affine) why = "an AffineDuplication operator needs AFFINE";
+	else if (a.any_poisson && !poisson) why = "the membrane correction needs POISSON";
+	else if (num != kNumRuntime && (uint32_t)num != m.numerics) why = "NUM does not match the model's numerics";
+	else if ((a.extra != 0u) != (extra >= 1 && extra <= 4)) why = "a.extra needs EXTRA 1..4 and only it";
+	else if ((m.rgb_deep != 0u) != (extra >= 3 && extra <= 5)) why = "a third rgb hidden layer needs EXTRA 3..5 and only it";
+	else if (extra == 6 && !a.gate) why = "EXTRA 6 (GATE) without a.gate";
+	else if (intro && extra != 2 && extra != 4) why = "Normals / EncodingVis need EXTRA 2 or 4";
+	else if (prof && !(a.dbg & 4u)) why = "PROF without NRS_DEBUG bit 2";
+	if (!why) return NRS_OK;
+	char name[160];
+	route_name(name, sizeof(name), waves, occ, prof, poisson, affine, team, num, extra);
+	snprintf(g_launch_err, sizeof(g_launch_err), "launch_render: route refused: %s for team %u, affine %u, poisson %u, numerics %u, extra %u, deep %u, gate %u, render mode %u: %s",
+	         name, a.team, a.any_affine, a.any_poisson, m.numerics, a.extra, m.rgb_deep, a.gate, (uint32_t)a.p.render_mode, why);
+	return NRS_ERR_STATE;
+}
+static void log_route(int waves, int occ, bool prof, bool poisson, bool affine, int team, int num, int extra) {
+	char name[160];
+	route_name(name, sizeof(name), waves, occ, prof, poisson, affine, team, num, extra);
+	fprintf(stderr, "[nrs kernel] %s\n", name);
+}
 template <int WAVES, int OCC, bool PROF, bool POISSON, bool AFFINE, int TEAM, int NUM, int EXTRA>
 static int launch_render_cfg(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream);
 template <int WAVES, bool PROF = false, bool POISSON = false, bool AFFINE = false, int TEAM = 1, int NUM = 0, int XTRA = 0>
 static int launch_render_c128(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream) {
+	{ const int rc = check_route(m, a, WAVES, -1, PROF, POISSON, AFFINE, TEAM, NUM, XTRA); if (rc != NRS_OK) return rc; }
 	int blocks_per_cu = 0;
 	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, render_kernel_c128<WAVES, PROF, POISSON, AFFINE, TEAM, NUM, XTRA>, 64 * WAVES, 0);
 	if (e != hipSuccess) return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor(render_kernel_c128)");
@@ -1121,7 +1156,7 @@ static int launch_render_c128(const DeviceModel& m, const RenderArgs& a, int n_c
 	if (grid > max_useful) grid = max_useful;
 	if (grid == 0) return NRS_OK;
 	static const bool log_kernel = dev_knob("NRS_KERNEL_LOG") != nullptr;
-	if (log_kernel) fprintf(stderr, "[nrs kernel] render_kernel_c128<%d, team %d, extra %d>\n", WAVES, TEAM, XTRA);
+	if (log_kernel) log_route(WAVES, -1, PROF, POISSON, AFFINE, TEAM, NUM, XTRA);
 	hipLaunchKernelGGL((render_kernel_c128<WAVES, PROF, POISSON, AFFINE, TEAM, NUM, XTRA>), dim3(grid), dim3(64 * WAVES), 0, stream, m, a);
 	NRS_LAUNCH_CHECK("render_kernel launch");
 	return NRS_OK;
@@ -1129,8 +1164,9 @@ static int launch_render_c128(const DeviceModel& m, const RenderArgs& a, int n_c
 
 template <int WAVES, int OCC, bool PROF = false, bool POISSON = false, bool AFFINE = false, int TEAM = 1, int NUM = 0, int EXTRA = 0>
 static int launch_render_cfg(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream) {
+	{ const int rc = check_route(m, a, WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA); if (rc != NRS_OK) return rc; }
 	static const bool log_kernel = dev_knob("NRS_KERNEL_LOG") != nullptr;
-	if (log_kernel) fprintf(stderr, "[nrs kernel] render_kernel<%d, %d, prof %d, poisson %d, affine %d, team %d, num %d, extra %d>\n", WAVES, OCC, (int)PROF, (int)POISSON, (int)AFFINE, TEAM, NUM, (int)EXTRA);
+	if (log_kernel) log_route(WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA);
 	int blocks_per_cu = 0;
 	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, render_kernel<WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA>, 64 * WAVES, 0);
 	if (e != hipSuccess) return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor(render_kernel)");
@@ -1202,13 +1238,16 @@ int launch_render(const DeviceModel& m, const RenderArgs& a, int n_cus, void* st
 		return launch_render_cfg<8, 4, false, true, false, 0>(m, a, n_cus, s);
 	}
 	if (a.any_poisson) return launch_render_cfg<12, 3, false, true, true>(m, a, n_cus, s);
-	if (a.dbg & 4u) return a.team == 0 ? launch_render_cfg<8, 4, true, false, false, 0>(m, a, n_cus, s) : launch_render_cfg<8, 4, true>(m, a, n_cus, s);
+	// the wave log (NRS_DEBUG bit 2) has PROF twins of the default kernel for the automatic schedule and one lane per ray only: AffineDuplication and fixed
+	// 2 / 4 lanes per ray run their production instantiation below with an empty log
+	if ((a.dbg & 4u) && !a.any_affine && (a.team == 0 || a.team == 1))
+		return a.team == 0 ? launch_render_cfg<8, 4, true, false, false, 0>(m, a, n_cus, s) : launch_render_cfg<8, 4, true>(m, a, n_cus, s);
 	// Production instantiations: scheduled for 3 waves/SIMD, capped at 128 VGPRs = 4 waves/SIMD (render_kernel_c128).  Measured against the
 	// __launch_bounds__(512, 4) build of the same code (NRS_RENDER_CFG=84): 1080p lego + cage 9.43 -> 9.82 Gsamples/s, lego 10.7 -> 11.0,
 	// varied-opacity scene 7.65 -> 7.89, aabb-16 4.35 -> 4.72.  (Plain __launch_bounds__(512, 3), round 1's choice, now lets the allocator
 	// take 131 VGPRs = 3 waves/SIMD: 7.3.)
 	if (cfg == 84) {
-		if (a.any_affine) return launch_render_cfg<8, 4, false, false, true>(m, a, n_cus, s);
+		if (a.any_affine) return a.team == 0 ? launch_render_cfg<8, 4, false, false, true, 0>(m, a, n_cus, s) : launch_render_cfg<8, 4, false, false, true>(m, a, n_cus, s);
 		if (a.team == 0) return launch_render_cfg<8, 4, false, false, false, 0>(m, a, n_cus, s);
 		if (a.team == 2) return launch_render_cfg<8, 4, false, false, false, 2>(m, a, n_cus, s);
 		if (a.team == 4) return launch_render_cfg<8, 4, false, false, false, 4>(m, a, n_cus, s);

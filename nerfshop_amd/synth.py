@@ -115,8 +115,22 @@ def level_table(desc):
 def default_sigma_raw(aabb_scale=1):
     """Raw density that gives alpha ~ 0.14 per sample at the scene's typical step: dt_min for aabb_scale 1; for the
     x6 "garden-style" scene the orbit camera sits ~8 units away, where cone stepping makes dt ~ t/256 ~ 0.031."""
-    dt = 1.73205080757 / 1024.0 if aabb_scale == 1 else 0.031
-    return math.log(0.15 / dt)
+    return math.log(0.15 / _typical_dt(aabb_scale))
+
+
+def _typical_dt(aabb_scale):
+    return 1.73205080757 / 1024.0 if aabb_scale == 1 else 0.031
+
+
+def sigma_for_alpha(alpha, aabb_scale=1):
+    """Raw density whose constant channel gives opacity `alpha` per sample at default_sigma_raw's step dt: 1 - exp(-exp(sigma_raw) * dt) = alpha,
+    i.e. sigma_raw = ln(-ln(1 - alpha) / dt).  alpha = 1 means "exactly 1.0f": ln(40 / dt) + 1, so that exp(sigma_raw) * dt = 40 e ~ 109 and
+    1 - __expf(-sigma * dt) rounds to 1 (which needs sigma * dt > 17.4) for every sample even where the density noise (make_params) takes
+    a raw unit or more off the constant."""
+    dt = _typical_dt(aabb_scale)
+    if alpha >= 1.0:
+        return math.log(40.0 / dt) + 1.0
+    return math.log(-math.log1p(-alpha) / dt)
 
 
 def make_params(desc, seed=SEED, sigma_raw=None, density_noise=0.25, shaped=False, aabb_scale=1, shape_gain=12.0):

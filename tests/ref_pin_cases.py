@@ -171,7 +171,17 @@ FRAME_CASES = [
     ("aabb16_glow_mask_to_alpha", "aabb16", (64, 36, 30.0), {"glow_mode": 5, "glow_y_cutoff": 0.6}, "cage"),
     ("lego_slice_distorted_lens", "lego", (64, 36, 30.0), {"render_mode": 9, "slice_plane_z": 1.3, "distortion_mode": 1, "distortion_params": (0.15, -0.05, 0.003, 0.002, 0, 0, 0), "dof": 0.05,
                                                           "_distmap": (24, 12, 9, 0.01)}, None),
+    # short rays (tests/test_gpu_opacity_regimes.py): opacity per sample 0.84 (a ray of constant alpha saturates after ~2.5 samples), exactly 1.0f (one sample),
+    # min_transmittance at its edges (0: rays run to the box exit; 1: a ray ends at its first sample with alpha > 0), the membrane correction on short rays.
+    # (48 x 32: the golden file stays below the 1 MiB a committed file may have)
+    ("lego_a084_edit", "lego_a084", (48, 32, 60.0), {}, "cage"),
+    ("lego_a1_edit", "lego_a1", (48, 32, 60.0), {}, "cage"),
+    ("lego_a05_mt0", "lego_a05", (48, 32, 100.0), {"min_transmittance": 0.0}, "cage"),
+    ("lego_a05_mt1", "lego_a05", (48, 32, 100.0), {"min_transmittance": 1.0}, "cage"),
+    ("lego_a084_membrane", "lego_a084", (48, 32, 60.0), {"poisson_target": 1}, "membrane"),
 ]
+# scenes of another constant opacity per sample (synth.sigma_for_alpha): key -> alpha
+ALPHA_SCENES = {"lego_a05": 0.5, "lego_a084": 0.84, "lego_a1": 1.0}
 
 
 def camera_extras(p, over):
@@ -206,9 +216,22 @@ class Scenes:
             from conftest import Scene
             if key == "lego_shaped":  # geometry in the network: the occupancy refresh has something to find
                 self._s[key] = Scene(aabb_scale=1, with_edit=True, lattice_n=6, shaped=True)
+            elif key in ALPHA_SCENES:
+                self._s[key] = alpha_scene(Scene(aabb_scale=1, with_edit=True, lattice_n=6), ALPHA_SCENES[key])
             else:
                 self._s[key] = Scene(aabb_scale=1, with_edit=True, lattice_n=6) if key == "lego" else Scene(aabb_scale=16, with_edit=True, lattice_n=5)
         return self._s[key]
+
+
+def alpha_scene(sc, alpha, shaped=False, density_noise=0.25):
+    """a conftest.Scene whose network has the opacity `alpha` per sample (synth.sigma_for_alpha) instead of default_sigma_raw's ~0.14: same occupancy,
+    same edit, new parameters and a new oracle model (`shaped` as the Scene was built)"""
+    from oracle import oracle as orc
+    sc.params = sc.synth.make_params(sc.desc, sigma_raw=sc.synth.sigma_for_alpha(alpha, sc.aabb_scale), density_noise=density_noise, shaped=shaped,
+                                     aabb_scale=sc.aabb_scale)
+    sc.oracle_model = orc.Model(sc.desc, sc.params, sc.bitfield)
+    sc.alpha = alpha
+    return sc
 
 
 def _case_setup(scenes, case):
