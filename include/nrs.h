@@ -541,6 +541,36 @@ int nrs_mvc_apply(const float* h_weights, const float* h_cage_vertices, uint32_t
 int nrs_tet_local_rotations(const float* h_vertices, const float* h_original_vertices, const uint32_t* h_tets,
                             uint32_t n_tets, float* h_rotations_out);
 
+/* ---- several samples per pixel of one view in one launch ------------------------------------------------------------ */
+/* What an offline caller of the reference does with a still view -- render_to_cpu (src/python_api.cu:129) and scripts/run.py --screenshot_spp / --video_spp loop
+ * `spp` times over render + accumulate -- as ONE launch of the render kernel and ONE pass over the accumulate buffer.  Callers detect the two entry points by symbol
+ * (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.
+ *
+ * nrs_render_nerf_spp renders samples params->spp_index + k, k = 0 .. spp_count - 1, of the view `params` describes: the packet queue of the persistent kernel holds the
+ * packets of all spp_count samples (one dispatch ramp, one staging of the weights, one drain).  Sample k is written to slab k of each buffer: what nrs_render_nerf
+ * writes at pixel index i of d_frame / d_depth / d_steps lands at k * slab_stride_pixels + i of d_frames (f32x4) / d_depths (f32) / d_steps (u32, may be NULL).  Every
+ * frame slab is pre-cleared by the caller exactly as d_frame is for nrs_render_nerf.  Each slab is bit-equal to the output of nrs_render_nerf with spp_index + k, and
+ * h_stats is the sum over the samples.  spp_count == 1 is nrs_render_nerf.
+ * NRS_ERR_INVALID_ARG, with the argument named in the message:
+ *   spp_count == 0 or > NRS_SPP_BATCH_MAX;
+ *   slab_stride_pixels smaller than the pixels one call owns (W * H, or owned tiles * tile_size^2 in tiled mode), or spp_count * slab_stride_pixels >= 2^32;
+ *   spp_count > 1 and a resolution above NRS_SPP_BATCH_MAX_RESOLUTION in either axis (a pending ray's record holds the sample beside the pixel);
+ *   spp_count times the packets, or the pixels, of one sample beyond 2^30 (the 32-bit packet counter);
+ *   render mode Slice with spp_count > 1: a slice has no per-sample jitter beyond the pixel offset and no persistent launch to share -- loop over the single-frame call;
+ *   and everything the single-frame call refuses (the checks are the same code).
+ * The schedule is chosen from the rays of the whole batch.  A batch launch leaves the hit-share feedback that sizes the caller's next single-frame launch untouched. */
+#define NRS_SPP_BATCH_MAX 64u
+#define NRS_SPP_BATCH_MAX_RESOLUTION 8192
+int nrs_render_nerf_spp(nrs_model* model, const nrs_render_params* params, nrs_edit* const* edits, int n_edits, uint32_t spp_count,
+                        float* d_frames, float* d_depths, uint32_t* d_steps, size_t slab_stride_pixels, void* stream, nrs_render_stats* h_stats);
+/* Folds the spp_count slabs into the running mean in sample order: bit-equal to spp_count calls of the single-frame accumulate with sample_count, sample_count + 1, ...
+ * (the per-sample update of accumulate_kernel inside a loop over the slabs: the running mean is not associative), with one read and one write of d_accumulate. */
+int nrs_accumulate_spp(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count,
+                       float* d_accumulate, uint32_t sample_count, uint32_t color_space);
+/* Introspection: render-kernel dispatches this context has enqueued so far (a batch of any size is one), and the schedule of the last one:
+ * lanes per ray (0 = sized per generation) | lanes on a pixel during the fill << 8 | small-launch schedule << 16 | hybrid queue << 17 | BATCH twin << 18.  Either may be NULL. */
+int nrs_ctx_render_launches(const nrs_ctx* ctx, uint64_t* n_dispatches_out, uint32_t* last_schedule_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,7 +155,9 @@ EXPORTS = [
     "nrs_tet_lut_build", "nrs_tet_lut_n_idx", "nrs_tet_lut_max_per_cell", "nrs_tet_lut_offsets",
     "nrs_tet_lut_idx", "nrs_tet_lut_bitfield", "nrs_tet_lut_destroy",
     "nrs_mvc_compute", "nrs_mvc_apply", "nrs_tet_local_rotations",
+    "nrs_render_nerf_spp", "nrs_accumulate_spp", "nrs_ctx_render_launches",
 ]
+SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
 
 _lib = None
 
@@ -254,6 +256,11 @@ def load():
     lib.nrs_detile.argtypes = [P, P, C.POINTER(RenderParams), U32, U32, P, U32, C.c_size_t, P]
     lib.nrs_trace_samples.argtypes = [P, C.POINTER(RenderParams), P, U32, P, U32, P, P, P]
     lib.nrs_accumulate.argtypes = [P, P, U32, U32, P, P, U32, U32]
+    # several samples per pixel in one launch (appended exports: a library without them predates the feature -- callers may test with hasattr)
+    if hasattr(lib, "nrs_render_nerf_spp"):  # (an A/B build of an older tree through NRS_LIB_PATH has none of the three)
+        lib.nrs_render_nerf_spp.argtypes = [P, C.POINTER(RenderParams), C.POINTER(P), I, U32, P, P, P, C.c_size_t, P, C.POINTER(RenderStats)]
+        lib.nrs_accumulate_spp.argtypes = [P, P, U32, U32, P, C.c_size_t, U32, P, U32, U32]
+        lib.nrs_ctx_render_launches.argtypes = [P, C.POINTER(C.c_uint64), C.POINTER(U32)]
     lib.nrs_snapshot_open.argtypes = [C.c_char_p, C.POINTER(P)]
     lib.nrs_snapshot_close.argtypes = [P]
     lib.nrs_snapshot_close.restype = None

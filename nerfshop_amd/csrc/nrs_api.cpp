@@ -44,6 +44,8 @@ struct nrs_ctx {
 	int lane_teams = 0; // nrs_ctx_set_lane_teams: 0 = automatic, 1 / 2 / 4 = lanes per ray for every render launch
 	int handover = -1;  // nrs_ctx_set_ray_handover: -1 = default (on; NRS_STEAL=0 turns it off), 0 / 1
 	unsigned long long last_handover = 0; // rays | hand-overs << 32 of the last launch that returned statistics
+	unsigned long long render_dispatches = 0; // render-kernel dispatches enqueued through this context, and the schedule of the last one (nrs_ctx_render_launches; under launch_mutex)
+	uint32_t last_schedule = 0;
 	int device = 0;
 	int n_cus = 0;
 	size_t hbm_bytes = 0;
@@ -1479,9 +1481,10 @@ uint32_t nrs_render_owned_tiles(const nrs_render_params* p) {
 	return owned;
 }
 
-int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, float* d_frame, float* d_depth,
-                    uint32_t* d_steps, void* stream, nrs_render_stats* h_stats) {
-	if (!m || !p || !d_frame || !d_depth) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: NULL argument");
+// nrs_render_nerf and nrs_render_nerf_spp: spp_count samples of the view into slabs slab_stride pixels apart (a single frame: 1, 0)
+static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frame, float* d_depth,
+                          uint32_t* d_steps, size_t slab_stride, void* stream, nrs_render_stats* h_stats) {
+	if (!m || !p || !d_frame || !d_depth) return fail(NRS_ERR_INVALID_ARG, spp_count > 1u ? "nrs_render_nerf_spp: NULL argument (model, params, d_frames, d_depths)" : "nrs_render_nerf: NULL argument");
 	if (!m->have_params) return fail(NRS_ERR_STATE, "nrs_render_nerf: parameters not set (nrs_model_set_params)");
 	if (!m->have_bitfield) return fail(NRS_ERR_STATE, "nrs_render_nerf: occupancy not set (nrs_model_set_density_bitfield/_grid)");
 	{ const int pc = check_march_params(*p, "nrs_render_nerf"); if (pc != NRS_OK) return pc; }
@@ -1498,6 +1501,24 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
 	if (p->dof != 0.f && p->slice_plane_z == 0.f) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: dof != 0 needs a focus distance (slice_plane_z = m_slice_plane_z + m_scale != 0)");
 	if (n_edits < 0 || n_edits > nrs_ctx::kMaxEdits) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: too many edit operators");
 	if (n_edits > 0 && !edits) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: edits is NULL");
+	if (spp_count > 1u) { // what only a batch can get wrong; everything above is the single frame's check
+		if (p->render_mode == NRS_RENDER_SLICE)
+			return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: render_mode Slice with spp_count > 1: a slice has no persistent launch to share -- call nrs_render_nerf per sample");
+		if (p->resolution[0] > NRS_SPP_BATCH_MAX_RESOLUTION || p->resolution[1] > NRS_SPP_BATCH_MAX_RESOLUTION)
+			return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: resolution above NRS_SPP_BATCH_MAX_RESOLUTION (8192) in one axis with spp_count > 1");
+	}
+	if (spp_count > 1u) {
+		uint32_t tx = 0, owned = 0, np = 0, ppt = 0;
+		{ const int gs = tile_geometry(*p, 1, tx, owned, np, ppt); if (gs != NRS_OK) return gs; }
+		const uint64_t own_pixels = p->tile_size ? (uint64_t)owned * p->tile_size * p->tile_size : (uint64_t)p->resolution[0] * (uint64_t)p->resolution[1];
+		if ((uint64_t)slab_stride < own_pixels)
+			return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: slab_stride_pixels is smaller than the pixels one call owns (W * H, or owned tiles * tile_size^2)");
+		if ((uint64_t)slab_stride * spp_count >= (1ull << 32))
+			return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count * slab_stride_pixels does not fit the 32-bit pixel index");
+		// (16-pixel packets are the smallest any schedule cuts: 4 per 8x8 block; the queue's state word keeps bit 31 for "dry" and workgroups overshoot the counter by a chunk each)
+		if ((uint64_t)np * 4ull * spp_count > (1ull << 30) || (uint64_t)np * 64ull * spp_count > (1ull << 30))
+			return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count times the packets / pixels of one sample overflows the 32-bit packet counter (limit 2^30)");
+	}
 	nrs_ctx* ctx = m->ctx;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = (hipStream_t)stream;
@@ -1602,7 +1623,7 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
 		const int forced = ctx->lane_teams ? ctx->lane_teams : env_forced;
 		const unsigned long long fb = ctx->h_feedback ? __atomic_load_n(ctx->h_feedback, __ATOMIC_RELAXED) : 0ull;
 		const double hit_share = (fb >> 32) ? (double)(uint32_t)fb / (double)(fb >> 32) : 0.25;
-		a.pixels_owned = (uint32_t)std::min<uint64_t>((uint64_t)a.n_packets * 64ull, 0xffffffffull);
+		a.pixels_owned = (uint32_t)std::min<uint64_t>((uint64_t)a.n_packets * 64ull * spp_count, 0xffffffffull); // (a batch: the rays of all its samples decide the schedule)
 		// Launches of this context still running on OTHER streams (frames in flight: a rank of a multi-GPU job that overlaps its frames, a viewer that
 		// double-buffers) share the GPU with this one: the launch gets 1 / (1 + busy) of the lanes, and once three or more overlap the GPU is full
 		// whatever the size of one launch -- lane teams (a latency device) then only cost fill passes.  Measured, 1/8 share of the 1080p bench frame,
@@ -1679,8 +1700,16 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
 				a.n_packets = a.p_big + tail_rows * a.tiles_x * tail_fill;
 			}
 		}
-		a.feedback = ctx->d_feedback;
+		// a batch does not report: the feedback word sizes the caller's next single-frame launch, whose pixels_owned this launch's is not
+		a.feedback = spp_count > 1u ? nullptr : ctx->d_feedback;
 	}
+	// the queue of a batch: spp_count times the packets of one sample (hybrid: all samples' 8x8 packets, then all samples' tail packets -- one tail, one drain)
+	a.spp_count = spp_count;
+	a.spp_packets = a.n_packets;
+	a.spp_big = a.p_big;
+	a.slab_stride = spp_count > 1u ? (uint32_t)slab_stride : 0u;
+	a.n_packets *= spp_count;
+	a.p_big *= spp_count;
 	a.max_steps = p->max_march_steps ? p->max_march_steps : 10000u; // MARCH_ITER, testbed_nerf.cu:56
 	a.frame = d_frame;
 	a.depth = d_depth;
@@ -1694,7 +1723,10 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
 	if (a.n_packets == 0) { // nothing to launch (no owned tiles): the block stays as it is -- zero
 		ctx->counters_clean[slot] = true;
 	} else {
+		const unsigned long long dispatches0 = launch_render_dispatches();
 		NRS_TRY(launch_render(model_for_launch(m, *p), a, ctx->n_cus, s));
+		ctx->render_dispatches += launch_render_dispatches() - dispatches0;
+		ctx->last_schedule = a.team | (a.fill_lanes << 8) | (a.all_tail << 16) | ((a.p_big ? 1u : 0u) << 17) | ((spp_count > 1u ? 1u : 0u) << 18);
 		ctx->counter_parity[slot] ^= 1u;
 		ctx->counters_clean[slot] = true;
 	}
@@ -1759,6 +1791,37 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
 			}
 		}
 	}
+	return NRS_OK;
+}
+
+int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, float* d_frame, float* d_depth,
+                    uint32_t* d_steps, void* stream, nrs_render_stats* h_stats) {
+	return render_samples(m, p, edits, n_edits, 1u, d_frame, d_depth, d_steps, 0, stream, h_stats);
+}
+int nrs_render_nerf_spp(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frames, float* d_depths,
+                        uint32_t* d_steps, size_t slab_stride_pixels, void* stream, nrs_render_stats* h_stats) {
+	if (!d_frames || !d_depths) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: d_frames / d_depths is NULL");
+	if (spp_count == 0u) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count is 0");
+	if (spp_count > NRS_SPP_BATCH_MAX) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count above NRS_SPP_BATCH_MAX (64)");
+	return render_samples(m, p, edits, n_edits, spp_count, d_frames, d_depths, d_steps, slab_stride_pixels, stream, h_stats);
+}
+int nrs_ctx_render_launches(const nrs_ctx* ctx, uint64_t* n_dispatches, uint32_t* last_schedule) {
+	if (!ctx) return fail(NRS_ERR_INVALID_ARG, "nrs_ctx_render_launches: NULL context");
+	std::lock_guard<std::mutex> lock(const_cast<nrs_ctx*>(ctx)->launch_mutex);
+	if (n_dispatches) *n_dispatches = ctx->render_dispatches;
+	if (last_schedule) *last_schedule = ctx->last_schedule;
+	return NRS_OK;
+}
+int nrs_accumulate_spp(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count, float* d_accumulate,
+                       uint32_t sample_count, uint32_t color_space) {
+	if (!ctx || !d_frames || !d_accumulate) return fail(NRS_ERR_INVALID_ARG, "nrs_accumulate_spp: NULL argument (ctx, d_frames, d_accumulate)");
+	if (color_space > NRS_COLOR_VISPOSNEG) return fail(NRS_ERR_INVALID_ARG, "nrs_accumulate_spp: color_space is 0 (Linear), 1 (SRGB) or 2 (VisPosNeg)");
+	if ((uint64_t)width * height > 0xffffffffull) return fail(NRS_ERR_INVALID_ARG, "nrs_accumulate_spp: image too large");
+	if (spp_count == 0u) return fail(NRS_ERR_INVALID_ARG, "nrs_accumulate_spp: spp_count is 0");
+	if (spp_count > NRS_SPP_BATCH_MAX) return fail(NRS_ERR_INVALID_ARG, "nrs_accumulate_spp: spp_count above NRS_SPP_BATCH_MAX (64)");
+	if ((uint64_t)slab_stride_pixels < (uint64_t)width * height) return fail(NRS_ERR_INVALID_ARG, "nrs_accumulate_spp: slab_stride_pixels is smaller than width * height");
+	HIP_TRY(hipSetDevice(ctx->device));
+	NRS_TRY(launch_accumulate_spp(width * height, d_frames, slab_stride_pixels, spp_count, d_accumulate, sample_count, (int)color_space, stream));
 	return NRS_OK;
 }
 

@@ -299,14 +299,15 @@ __device__ __forceinline__ float4 read_envmap(const float* __restrict__ data, co
 // pixel_to_ray (common_device.cuh:245-295): origin and UN-normalised direction of pixel (x, y) through the camera of its ray time
 // (init_rays_with_payload_kernel_nerf, tn:2551-2567).  offset = ld_random_pixel_offset(snap ? 0 : spp), computed once per thread by the caller.
 // LENS compiles in the thin-lens branch (:285-293; m_dof, focus distance focus_z = plane_z): only the instantiations that serve dof != 0 carry it.
-template <bool LENS = false>
-__device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, float focus_z, f3& o, f3& d, bool use_dof = true) {
+// SPP: the Sobol sample index is the argument `spp`, not p.spp_index (a batch of samples of one view in one launch, nrs_render_nerf_spp: the index differs per packet)
+template <bool LENS = false, bool SPP = false>
+__device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, float focus_z, f3& o, f3& d, bool use_dof = true, uint32_t spp = 0u) {
 	const float W = (float)p.resolution[0], H = (float)p.resolution[1];
 	const uint32_t idx = x + (uint32_t)p.resolution[0] * y;
 	float u = ((float)x + 0.5f) * (1.f / W);
 	float v = ((float)y + 0.5f) * (1.f / H);
 	float ray_time = p.rolling_shutter[0] + p.rolling_shutter[1] * u + p.rolling_shutter[2] * v;
-	float rs_rand = (p.rolling_shutter[3] != 0.f) ? ld_random_val(p.spp_index, idx * 72239731u) : 0.f; // x * 0 == 0 for finite x
+	float rs_rand = (p.rolling_shutter[3] != 0.f) ? ld_random_val(SPP ? spp : p.spp_index, idx * 72239731u) : 0.f; // x * 0 == 0 for finite x
 	ray_time = ray_time + p.rolling_shutter[3] * rs_rand;
 	float cam[12];
 	#pragma unroll
@@ -340,7 +341,7 @@ __device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32
 	if (LENS && use_dof && p.dof != 0.0f) {
 		const f3 lookat = o + d * focus_z;
 		float r0, r1, bx, by;
-		ld_random_val_2d(p.spp_index, x * 19349663u + y * 96925573u, r0, r1);
+		ld_random_val_2d(SPP ? spp : p.spp_index, x * 19349663u + y * 96925573u, r0, r1);
 		square2disk_shirley(r0 * 2.0f - 1.0f, r1 * 2.0f - 1.0f, bx, by);
 		bx = p.dof * bx; by = p.dof * by;
 		o = {o.x + (cam[0] * bx + cam[3] * by), o.y + (cam[1] * bx + cam[4] * by), o.z + (cam[2] * bx + cam[5] * by)};
@@ -349,17 +350,17 @@ __device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32
 	}
 }
 // origin and normalised direction (tn:2588)
-template <bool LENS = false>
-__device__ __forceinline__ void ray_origin_dir(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, f3& o, f3& d) {
-	pixel_ray_raw<LENS>(p, x, y, off_x, off_y, p.slice_plane_z, o, d);
+template <bool LENS = false, bool SPP = false>
+__device__ __forceinline__ void ray_origin_dir(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, f3& o, f3& d, uint32_t spp = 0u) {
+	pixel_ray_raw<LENS, SPP>(p, x, y, off_x, off_y, p.slice_plane_z, o, d, true, spp);
 	float n = sqrtf(dot3(d, d));
 	d = {d.x / n, d.y / n, d.z / n};
 }
 
-template <bool LENS = false>
-__device__ __forceinline__ Ray init_ray(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y) {
+template <bool LENS = false, bool SPP = false>
+__device__ __forceinline__ Ray init_ray(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, uint32_t spp = 0u) {
 	Ray r;
-	ray_origin_dir<LENS>(p, x, y, off_x, off_y, r.o, r.d);
+	ray_origin_dir<LENS, SPP>(p, x, y, off_x, off_y, r.o, r.d, spp);
 	float tmin;
 	ray_intersect(p.render_aabb_min, p.render_aabb_max, r.o, r.d, tmin);
 	r.t = fmaxf(tmin, NRS_NEAR_DISTANCE) + 1e-6f;
@@ -664,10 +665,11 @@ __device__ __forceinline__ bool stands_in_occupied_cell(const nrs_render_params&
 }
 
 // advance_pos_nerf, tn:557-606: jitter by one Sobol value, then skip to the first occupied cell
+template <bool SPP = false>
 __device__ __forceinline__ bool first_hit(const nrs_render_params& p, const DeviceModel& m, const uint32_t* __restrict__ march_lds, uint32_t pixel_idx, Ray& r,
-                                          uint32_t* n_iter = nullptr) {
+                                          uint32_t* n_iter = nullptr, uint32_t spp = 0u) {
 	float dt = calc_dt(r.t, p.cone_angle_constant);
-	r.t += ld_random_val(p.spp_index, pixel_idx * 786433u) * dt;
+	r.t += ld_random_val(SPP ? spp : p.spp_index, pixel_idx * 786433u) * dt;
 	f3 pos;
 	return march_to_occupied<true>(p, m, march_lds, r.o, r.d, r.t, pos, dt, n_iter);
 }

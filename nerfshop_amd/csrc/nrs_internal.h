@@ -173,6 +173,10 @@ struct RenderArgs {
 	uint32_t fill_lanes;       // small-launch schedule (all_tail): lanes that stand on one pixel during the fill (4, 2 or 1: packets of 16 / 32 / 64 pixels)
 	uint32_t p_big;            // hybrid launches (team == 0): packets [0, p_big) are 8x8, the rest 4x4 tail packets; else 0
 	uint32_t team;             // 0 = hybrid (full generations, lane teams for the queue's tail); lanes per ray: 1, or 2 / 4 for launches with too few rays to fill the GPU (render_kernel's TEAM)
+	uint32_t spp_count;        // samples of the view in this launch's queue (nrs_render_nerf_spp; 1: a single frame): n_packets = spp_count * spp_packets and, hybrid, p_big = spp_count * spp_big
+	uint32_t spp_packets;      // packets of ONE sample (what n_packets is for a single frame)
+	uint32_t spp_big;          // hybrid launches: 8x8 packets of one sample (what p_big is for a single frame)
+	uint32_t slab_stride;      // pixels from one sample's slab of frame / depth / steps to the next (0 for a single frame)
 	uint32_t max_steps;
 	uint32_t dbg;              // NRS_DEBUG ablation bits (profiling only; 0 in production): 1 = all gathers hit entry 0, 2 = skip the MLPs
 	float*    frame;           // f32x4
@@ -185,6 +189,7 @@ struct RenderArgs {
 
 // kernel launchers (nrs_kernels.hip).  stream is a hipStream_t.
 int launch_render(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
+unsigned long long launch_render_dispatches(); // render-kernel dispatches of this process so far (nrs_ctx_render_launches counts with it)
 // render mode Slice (Testbed::render_nerf's branch, testbed_nerf.cu:3111-3175): one network evaluation per owned pixel on the slice plane
 int launch_slice(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
 int launch_trace_samples(const DeviceModel& m, const nrs_render_params& p, uint32_t n_pixels, const uint32_t* d_pixel_idx,
@@ -229,6 +234,7 @@ int launch_occ_accel(const uint8_t* d_bitfield, uint32_t* d_masks, float* d_out,
 int launch_grid_update(const DeviceModel& m, const DeviceEdit* d_edits, int n_edits, const nrs_grid_update& u, uint64_t rng_state_nonuniform,
                        float* d_grid, uint32_t* d_grid_tmp, int n_cus, void* stream);
 int launch_accumulate(uint32_t n_pixels, const float* d_frame, float* d_accum, uint32_t sample_count, int color_space, void* stream);
+int launch_accumulate_spp(uint32_t n_pixels, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count, float* d_accum, uint32_t sample_count, int color_space, void* stream);
 int launch_detile(const nrs_render_params& p, uint32_t n_ranks, size_t rank_stride_floats, const float* d_tiles, uint32_t channels,
                   float* d_image, void* stream);
 const char* launch_last_error();

@@ -63,6 +63,12 @@ class Context:
         check(self.lib.nrs_ctx_ray_handovers(self.h, C.byref(n), C.byref(k)))
         return n.value, k.value
 
+    def render_launches(self):
+        """(render-kernel dispatches enqueued through this context, schedule word of the last one) -- nrs_ctx_render_launches."""
+        n, sched = C.c_uint64(), C.c_uint32()
+        check(self.lib.nrs_ctx_render_launches(self.h, C.byref(n), C.byref(sched)))
+        return n.value, sched.value
+
     def close(self):
         if self.h:
             self.lib.nrs_ctx_destroy(self.h)
@@ -376,6 +382,32 @@ class RenderBuffer:
         self._spp += 1
         return self._accumulate
 
+    def spp_slabs(self, spp_count):
+        """Frame [K, H, W, 4], depth [K, H, W] and (with_steps) steps [K, H, W] slabs for Testbed.render_nerf_spp: allocated on first use, the frame slabs cleared on every call."""
+        k = int(spp_count)
+        if getattr(self, "_slabs", None) is None or self._slabs[0].shape[0] != k:
+            dev = self._frame.device
+            self._slabs = (torch.zeros((k, self.height, self.width, 4), dtype=torch.float32, device=dev),
+                           torch.zeros((k, self.height, self.width), dtype=torch.float32, device=dev),
+                           torch.zeros((k, self.height, self.width), dtype=torch.int32, device=dev) if self._steps is not None else None)
+        else:
+            self._slabs[0].zero_()
+        return self._slabs
+
+    def accumulate_spp(self, ctx, frames, stream=None, color_space=0):
+        """The K slabs of `frames` [K, H, W, 4] (Testbed.render_nerf_spp) join the running mean in sample order, bit-equal to K accumulate() calls, in one pass
+        over the accumulate buffer (nrs_accumulate_spp); spp() advances by K."""
+        _require_cuda(frames, torch.float32, "frames")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (self.height, self.width, 4):
+            raise ValueError(f"frames must be [K, {self.height}, {self.width}, 4], got {tuple(frames.shape)}")
+        if getattr(self, "_accumulate", None) is None:
+            self._accumulate = torch.zeros_like(self._frame)
+        k = int(frames.shape[0])
+        check(_abi.load().nrs_accumulate_spp(ctx.h, _stream_handle(stream), self.width, self.height, frames.data_ptr(), self.width * self.height, k,
+                                             self._accumulate.data_ptr(), int(self._spp), int(color_space)))
+        self._spp += k
+        return self._accumulate
+
     def clear_frame(self, stream=None):
         self._frame.zero_()
         self._depth.zero_()
@@ -470,6 +502,31 @@ class Testbed:
         check(self.lib.nrs_render_nerf(network.h, C.byref(p), arr, n, frame.data_ptr(), depth.data_ptr(),
                                        steps.data_ptr() if steps is not None else None, _stream_handle(stream),
                                        C.byref(stats) if stats is not None else None))
+        self.last_stats = stats
+        return stats
+
+    def render_nerf_spp(self, network, render_buffer, spp_count, focal_length, camera_matrix0, camera_matrix1, rolling_shutter, screen_center,
+                        apply_operators, stream=None, want_stats=False):
+        """Samples spp() .. spp() + spp_count - 1 of the view in ONE launch (what the spp loop of the reference's render_to_cpu does in spp_count launches): returns
+        (frames [K, H, W, 4], depths [K, H, W], steps or None, stats).  Follow with render_buffer.accumulate_spp(ctx, frames), which advances spp() by K."""
+        p = self.make_params(render_buffer, focal_length, camera_matrix0, camera_matrix1, rolling_shutter, screen_center,
+                             apply_operators and self.enable_edits)
+        frames, depths, steps = render_buffer.spp_slabs(spp_count)
+        stats = self.render_spp_with_params(network, p, spp_count, frames, depths, steps, None, stream, want_stats)
+        return frames, depths, steps, stats
+
+    def render_spp_with_params(self, network, p, spp_count, frames, depths, steps=None, slab_stride_pixels=None, stream=None, want_stats=False):
+        """nrs_render_nerf_spp: slab k of frames / depths / steps (slab_stride_pixels apart; default: the elements of frames[0] / 4) receives sample p.spp_index + k."""
+        _require_cuda(frames, torch.float32, "frames")
+        _require_cuda(depths, torch.float32, "depths")
+        if slab_stride_pixels is None:
+            slab_stride_pixels = frames[0].numel() // 4 if frames.dim() > 1 and frames.shape[0] else 0
+        n = len(self.edit_operators)
+        arr = (C.c_void_p * max(n, 1))(*[op.h for op in self.edit_operators])
+        stats = RenderStats() if want_stats else None
+        check(self.lib.nrs_render_nerf_spp(network.h, C.byref(p), arr, n, int(spp_count), frames.data_ptr(), depths.data_ptr(),
+                                           steps.data_ptr() if steps is not None else None, int(slab_stride_pixels), _stream_handle(stream),
+                                           C.byref(stats) if stats is not None else None))
         self.last_stats = stats
         return stats
 
