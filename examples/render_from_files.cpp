@@ -5,7 +5,9 @@
 //   Testbed::load_edits               src/testbed.cu:3205   -> nrs_edits_open + CageDeformation / AffineDuplication
 //   Testbed::render_nerf              src/testbed_nerf.cu:3066 -> nrs::compat::Testbed::render_nerf
 //
-//   usage: render_from_files <snapshot> <edits.json | -> <width> <height> <camera_angle_x radians> <out.raw>
+//   usage: render_from_files <snapshot> <edits.json | -> <width> <height> <camera_angle_x radians> <out.raw> [<light x> <light y> <light z>]
+//
+// A snapshot trained with light directions is opened too (NRS_SNAPSHOT_ALLOW_LIGHT_DIRS); the optional light direction is Testbed::m_nerf.light_dir.
 //
 // out.raw = float32 RGBA [H][W][4] followed by float32 depth [H][W].  Device memory comes straight from the HIP runtime (hipMalloc); the library takes the
 // pointers as they are.  tests/test_gpu_cpp_host.py builds this file, runs it on the GPU and compares out.raw bit for bit with the Python host's frame.
@@ -29,7 +31,7 @@ void hip_check(hipError_t e, const char* what) {
 
 struct Snapshot {
 	nrs_snapshot* s = nullptr;
-	explicit Snapshot(const char* path) { nrs::compat::check(nrs_snapshot_open(path, &s), "nrs_snapshot_open"); }
+	explicit Snapshot(const char* path) { nrs::compat::check(nrs_snapshot_open_ex(path, NRS_SNAPSHOT_ALLOW_LIGHT_DIRS, &s), "nrs_snapshot_open_ex"); }
 	~Snapshot() { nrs_snapshot_close(s); }
 };
 
@@ -50,8 +52,8 @@ struct DeviceBuffer {
 };
 
 int run(int argc, char** argv) {
-	if (argc != 7) {
-		std::fprintf(stderr, "usage: %s <snapshot.ingp|.msgpack> <edits.json|-> <width> <height> <camera_angle_x> <out.raw>\n", argv[0]);
+	if (argc != 7 && argc != 10) {
+		std::fprintf(stderr, "usage: %s <snapshot.ingp|.msgpack> <edits.json|-> <width> <height> <camera_angle_x> <out.raw> [<light x> <light y> <light z>]\n", argv[0]);
 		return 2;
 	}
 	const int width = std::atoi(argv[3]), height = std::atoi(argv[4]);
@@ -64,7 +66,7 @@ int run(int argc, char** argv) {
 	uint32_t aabb_scale = 1;
 	nrs::compat::check(nrs_snapshot_model_desc(snap.s, &desc, &aabb_scale), "nrs_snapshot_model_desc");
 	nrs::compat::Context ctx(0);
-	nrs::compat::NerfNetwork network(ctx, desc);
+	nrs::compat::NerfNetwork network(ctx, desc, nrs_snapshot_n_extra_dims(snap.s));
 	size_t n_params = 0, n_grid = 0;
 	const void* params = nrs_snapshot_params_fp16(snap.s, &n_params);
 	network.set_params(params, n_params);
@@ -104,6 +106,8 @@ int run(int argc, char** argv) {
 
 	// ---- the Testbed members render_nerf reads
 	testbed.m_nerf.cone_angle_constant = aabb_scale <= 1 ? 0.f : 1.f / 256.f; // testbed_nerf.cu:3410-3425
+	if (argc == 10)
+		for (int i = 0; i < 3; ++i) testbed.m_nerf.light_dir[i] = (float)std::atof(argv[7 + i]);
 	const float half = 0.5f * (float)aabb_scale;                              // m_render_aabb = the dataset's box: centred on 0.5, aabb_scale wide
 	for (int i = 0; i < 3; ++i) {
 		testbed.m_render_aabb_min[i] = 0.5f - half;

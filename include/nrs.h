@@ -495,6 +495,7 @@ int nrs_trace_samples(nrs_model* model, const nrs_render_params* params, void* s
  * .dataset.aabb_scale), snapshot.params_binary (tcnn Trainer::serialize, fp16 or float), snapshot.density_grid_binary
  * (float [5*128^3] from save_snapshot, fp16 [(max_cascade+1)*128^3] from export_snapshot), snapshot.camera.matrix. */
 typedef struct nrs_snapshot nrs_snapshot;
+/* (a snapshot trained with light directions is refused here: nrs_snapshot_open_ex with NRS_SNAPSHOT_ALLOW_LIGHT_DIRS, at the end of this header, reads it) */
 int          nrs_snapshot_open(const char* path, nrs_snapshot** out);
 void         nrs_snapshot_close(nrs_snapshot* snapshot);
 int          nrs_snapshot_model_desc(const nrs_snapshot* snapshot, nrs_model_desc* desc_out, uint32_t* aabb_scale_out);
@@ -570,6 +571,41 @@ int nrs_accumulate_spp(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t heig
 /* Introspection: render-kernel dispatches this context has enqueued so far (a batch of any size is one), and the schedule of the last one:
  * lanes per ray (0 = sized per generation) | lanes on a pixel during the fill << 8 | small-launch schedule << 16 | hybrid queue << 17 | BATCH twin << 18.  Either may be NULL. */
 int nrs_ctx_render_launches(const nrs_ctx* ctx, uint64_t* n_dispatches_out, uint32_t* last_schedule_out);
+
+/* ---- networks trained with light directions (n_extra_dims = 3) ----------------------------------------------------------------------- */
+/* dataset.has_light_dirs sets n_extra_dims = 3 (src/testbed.cu:2318): NerfNetworkFull builds the direction encoding over n_dir_dims + n_extra_dims inputs
+ * (nerf_network_full.h:43), every sample carries three more floats behind its NerfCoordinate (nerf.h:73-96, set_with_optional_light_dir), and rendering passes ONE light
+ * direction per frame, m_nerf.light_dir.normalized() (testbed.h:639, src/testbed_nerf.cu:3135, :649, :690), as do the selection and Poisson callers
+ * (growing_selection.cu:1914, :2230).  Callers detect these entry points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.
+ *
+ * The network (tiny-cuda-nn as recalled; unpinned like the rest of that boundary): the direction encoding is configs/nerf/base.json:37-51's Composite
+ * [SphericalHarmonics(3 dims, degree 4) | Identity(the remaining 3 dims)] = 19 outputs, padded to 32.  The rgb network's input is 48 wide: columns 0..15 the density network's
+ * outputs, 16..31 the SH coefficients, 32..34 warp_direction(l) = (l + 1) / 2 in fp32 rounded to fp16, 35..47 padding that the Identity kernel writes as 1 -- those weight
+ * columns act as a learned bias.  The first rgb matrix is [64 x 48] row-major, the blob 64 * 16 halfs longer; nothing else of the network changes.
+ * Supported: sh_degree = 4 with rgb_hidden_layers 1..3.  NerfNetworkNoDir and the 0-layer CutlassMLP rgb network with extra dims: NRS_ERR_UNSUPPORTED.
+ *
+ * nrs_model_create_ex: n_extra_dims 0 (= nrs_model_create) or 3; anything else is NRS_ERR_UNSUPPORTED.  nrs_model_set_params / _device then take the longer blob.
+ * nrs_model_n_params_ex: the plain count + 1024 for n_extra_dims = 3 (0 for what nrs_model_create_ex refuses).
+ * nrs_model_set_light_dir <- m_nerf.light_dir: normalised at use, default (0.5, 0.5, 0.5); a zero (or non-finite) vector is NRS_ERR_INVALID_ARG; on a model without extra dims the
+ *   call is accepted and has no effect.  The current light direction is what EVERY entry point feeds to every sample when the caller gives no per-sample values:
+ *   nrs_render_nerf / _spp (Slice included), nrs_network_inference (7-float records), nrs_rgba_on_grid, nrs_poisson_boundary, nrs_network_visualize_activation and render mode
+ *   EncodingVis (layer 2 is 48 wide: units 32..34 the warped light, 35..47 are 1).  Density-only entry points are unaffected.  Edit operators rotate the view direction only
+ *   (cage_deformation.cu:547-572 touches floats 4..6).
+ * nrs_render_nerf with such a model: every combination is served except the membrane correction (an edit with apply_poisson while apply_operators is set) and the
+ *   measurement routes (NRS_DEV_KNOBS: the wave log, NRS_RENDER_CFG), which return NRS_ERR_UNSUPPORTED -- such a model is never rendered without its light term.
+ * nrs_network_inference_strided <- inference with PitchedPtr<NerfCoordinate> + extra_stride: records of ld_in >= 7 floats; with ld_in >= 10 on a model with extra dims, floats
+ *   7..9 of a record are that sample's ALREADY-WARPED light direction; with ld_in 7..9 the model's light direction is used; on a model without extra dims floats beyond 6 are ignored. */
+int    nrs_model_create_ex(nrs_ctx* ctx, const nrs_model_desc* desc, uint32_t n_extra_dims, nrs_model** out);
+size_t nrs_model_n_params_ex(const nrs_model_desc* desc, uint32_t n_extra_dims);
+int    nrs_model_n_extra_dims(const nrs_model* model);
+int    nrs_model_set_light_dir(nrs_model* model, const float dir[3]);
+int    nrs_network_inference_strided(nrs_model* model, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out_fp16, uint32_t ld_out, int layout);
+/* nrs_snapshot_open with flags.  NRS_SNAPSHOT_ALLOW_LIGHT_DIRS: a snapshot trained with light directions -- recognised by the keys a writer may add (has_light_dirs /
+ * n_extra_dims) and by the size of its parameter blob, exactly as nrs_snapshot_open recognises (and refuses) it -- is read: nrs_snapshot_n_extra_dims answers 3 and
+ * nrs_snapshot_params_fp16 hands out the longer blob for nrs_model_create_ex(..., 3, ...).  flags = 0 is nrs_snapshot_open. */
+#define NRS_SNAPSHOT_ALLOW_LIGHT_DIRS 1u
+int      nrs_snapshot_open_ex(const char* path, uint32_t flags, nrs_snapshot** out);
+uint32_t nrs_snapshot_n_extra_dims(const nrs_snapshot* snapshot);
 
 #ifdef __cplusplus
 }

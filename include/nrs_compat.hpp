@@ -50,7 +50,10 @@ struct OutputMatrix {
 
 class NerfNetwork {
 public:
-	NerfNetwork(Context& ctx, const nrs_model_desc& desc) : m_desc(desc) { check(nrs_model_create(ctx.get(), &desc, &m_model), "nrs_model_create"); }
+	// n_extra_dims: 0, or 3 for a network trained with light directions (dataset.has_light_dirs, testbed.cu:2318)
+	NerfNetwork(Context& ctx, const nrs_model_desc& desc, uint32_t n_extra_dims = 0) : m_desc(desc) {
+		check(nrs_model_create_ex(ctx.get(), &desc, n_extra_dims, &m_model), "nrs_model_create_ex");
+	}
 	~NerfNetwork() { nrs_model_destroy(m_model); }
 	NerfNetwork(const NerfNetwork&) = delete;
 	NerfNetwork& operator=(const NerfNetwork&) = delete;
@@ -58,8 +61,8 @@ public:
 	// tcnn::Network interface subset used on the path (nerf_network.h:97-120)
 	uint32_t padded_output_width() const { return NRS_NETWORK_OUTPUT_WIDTH; }
 	uint32_t input_width() const { return NRS_NETWORK_INPUT_FLOATS; }
-	uint32_t n_extra_dims() const { return 0; }
-	size_t n_params() const { return nrs_model_n_params(&m_desc); }
+	uint32_t n_extra_dims() const { return (uint32_t)nrs_model_n_extra_dims(m_model); }
+	size_t n_params() const { return nrs_model_n_params_ex(&m_desc, n_extra_dims()); }
 
 	// set_params(params, inference_params, ...) of the reference takes device pointers into the trainer's blob; here the fp16
 	// blob (density MLP | rgb MLP | hash grid, nerf_network_full.h:316-349) is handed over from the host once.
@@ -173,6 +176,7 @@ public:
 		float cone_angle_constant = 0.f;            // 0 for aabb_scale 1, 1/256 otherwise (testbed_nerf.cu:3410-3425)
 		float rendering_min_transmittance = 0.01f;
 		bool training_linear_colors = false;
+		float light_dir[3] = {0.5f, 0.5f, 0.5f};    // testbed.h:639; render_nerf passes light_dir.normalized() to every sample of a network with extra dims (:3135)
 	} m_nerf;
 	float m_render_aabb_min[3] = {0, 0, 0}, m_render_aabb_max[3] = {1, 1, 1};
 	bool m_snap_to_pixel_centers = true;
@@ -253,6 +257,7 @@ public:
 		p.glow_mode = (uint32_t)m_glow_mode;
 		p.glow_y_cutoff = m_glow_y_cutoff;
 		for (int i = 0; i < 2; ++i) { p.distortion_resolution[i] = m_distortion_resolution[i]; p.envmap_resolution[i] = m_envmap_resolution[i]; }
+		check(nrs_model_set_light_dir(network.get(), m_nerf.light_dir), "nrs_model_set_light_dir"); // (no effect on a network without extra dims)
 		std::vector<nrs_edit*> edits;
 		for (const EditOperator* op : m_edit_operators) edits.push_back(op->get());
 		check(nrs_render_nerf(network.get(), &p, edits.data(), (int)edits.size(), render_buffer.frame_buffer, render_buffer.depth_buffer, nullptr, stream,

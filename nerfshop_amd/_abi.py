@@ -156,7 +156,10 @@ EXPORTS = [
     "nrs_tet_lut_idx", "nrs_tet_lut_bitfield", "nrs_tet_lut_destroy",
     "nrs_mvc_compute", "nrs_mvc_apply", "nrs_tet_local_rotations",
     "nrs_render_nerf_spp", "nrs_accumulate_spp", "nrs_ctx_render_launches",
+    "nrs_model_create_ex", "nrs_model_n_params_ex", "nrs_model_n_extra_dims", "nrs_model_set_light_dir", "nrs_network_inference_strided",
+    "nrs_snapshot_open_ex", "nrs_snapshot_n_extra_dims",
 ]
+SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
 
 _lib = None
@@ -261,6 +264,17 @@ def load():
         lib.nrs_render_nerf_spp.argtypes = [P, C.POINTER(RenderParams), C.POINTER(P), I, U32, P, P, P, C.c_size_t, P, C.POINTER(RenderStats)]
         lib.nrs_accumulate_spp.argtypes = [P, P, U32, U32, P, C.c_size_t, U32, P, U32, U32]
         lib.nrs_ctx_render_launches.argtypes = [P, C.POINTER(C.c_uint64), C.POINTER(U32)]
+    # networks trained with light directions (appended exports, detected by symbol like the spp batch)
+    if hasattr(lib, "nrs_model_create_ex"):
+        lib.nrs_model_create_ex.argtypes = [P, C.POINTER(ModelDesc), U32, C.POINTER(P)]
+        lib.nrs_model_n_params_ex.argtypes = [C.POINTER(ModelDesc), U32]
+        lib.nrs_model_n_params_ex.restype = C.c_size_t
+        lib.nrs_model_n_extra_dims.argtypes = [P]
+        lib.nrs_model_set_light_dir.argtypes = [P, C.POINTER(C.c_float * 3)]
+        lib.nrs_network_inference_strided.argtypes = [P, P, U32, P, U32, P, U32, I]
+        lib.nrs_snapshot_open_ex.argtypes = [C.c_char_p, U32, C.POINTER(P)]
+        lib.nrs_snapshot_n_extra_dims.argtypes = [P]
+        lib.nrs_snapshot_n_extra_dims.restype = U32
     lib.nrs_snapshot_open.argtypes = [C.c_char_p, C.POINTER(P)]
     lib.nrs_snapshot_close.argtypes = [P]
     lib.nrs_snapshot_close.restype = None

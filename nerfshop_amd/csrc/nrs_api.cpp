@@ -80,6 +80,8 @@ struct nrs_ctx {
 struct nrs_model {
 	nrs_ctx* ctx = nullptr;
 	nrs_model_desc desc{};
+	uint32_t n_extra_dims = 0;      // 0, or 3: trained with light directions (nrs_model_create_ex)
+	float light_dir[3] = {0.5f, 0.5f, 0.5f}; // m_nerf.light_dir as the caller set it (testbed.h:639); normalised at use -> dm.light01
 	DeviceModel dm{};
 	uint32_t total_entries = 0;
 	uint32_t* d_grid = nullptr;
@@ -171,12 +173,12 @@ static uint32_t kernel_layer(const nrs_model_desc& d, uint32_t layer) {
 	if (layer >= 8u) return 0xFFu;
 	return (d.density_hidden_layers == 0u && layer >= 1u) ? layer + 1u : layer;
 }
-static uint32_t network_layer_width(const nrs_model_desc& d, uint32_t layer) {
+static uint32_t network_layer_width(const nrs_model_desc& d, uint32_t layer, uint32_t n_extra_dims = 0) {
 	const uint32_t k = kernel_layer(d, layer);
 	if (k == 0u) return 32u;
 	if (k == 1u) return 64u;
 	if (d.sh_degree == 0u) return 0u;
-	if (k == 2u) return 32u;
+	if (k == 2u) return n_extra_dims ? 48u : 32u; // (light directions: 16 density outputs | 16 SH coefficients | Identity(light 3) padded with ones to 16)
 	return k - 3u < d.rgb_hidden_layers ? 64u : 0u;
 }
 // configs/nerf/base.json's family: hash grid of 16 x 2 features (any table size: base_14 / small / base / big.json), the 64-wide density network with one hidden
@@ -197,7 +199,16 @@ static uint32_t n_rgb_weights(const nrs_model_desc& d) {
 	return 64u * 32u + (d.rgb_hidden_layers - 1u) * 64u * 64u + 16u * 64u;
 }
 static uint32_t n_density_weights(const nrs_model_desc& d) { return d.density_hidden_layers == 0 ? 16u * 32u : kDensityW; }
-static uint32_t n_mlp_weights(const nrs_model_desc& d) { return n_density_weights(d) + n_rgb_weights(d); }
+// n_extra_dims = 3 (light directions): the direction encoding is Composite[SH(3 dims, degree 4) | Identity(3 dims)] = 19 outputs padded to the rgb network's
+// alignment, 32, so the first rgb matrix is [64 x 48] instead of [64 x 32] (nerf_network_full.h:43; tiny-cuda-nn as recalled)
+static uint32_t n_mlp_weights(const nrs_model_desc& d, uint32_t n_extra_dims = 0) { return n_density_weights(d) + n_rgb_weights(d) + (n_extra_dims ? 64u * 16u : 0u); }
+// nrs_model_create_ex / nrs_model_n_params_ex: which networks may carry extra dims.  nullptr = fine.
+static const char* extra_dims_refusal(const nrs_model_desc& d, uint32_t n_extra_dims) {
+	if (n_extra_dims == 0u) return nullptr;
+	if (d.sh_degree == 0u) return "NerfNetworkNoDir (no direction encoding, base_nodir.json) with extra input dimensions is not supported";
+	if (d.rgb_hidden_layers == 0u) return "the 0-layer CutlassMLP rgb network (base_0layer.json) with extra input dimensions is not supported";
+	return nullptr;
+}
 
 // ---- lowering of the family onto the kernels' network (kCanonW entries, nrs_internal.h) -------------------------------------------------------------
 // Entries are opaque 16-bit words: fp16 bit patterns (nrs_model_set_params) or weight indices (nrs_model_set_params_device's permutation); `ops` says what
@@ -210,7 +221,7 @@ static uint32_t n_mlp_weights(const nrs_model_desc& d) { return n_density_weight
 //   three hidden layers: Wr2b, the kernels' optional layer (DeviceModel::rgb_deep).
 // (A value of -0 comes out as +0: equal, not bit-identical.)
 struct LowerOps { uint16_t one, minus_one; uint16_t (*negate)(uint16_t); };
-static void lower_weights(const nrs_model_desc& d, const uint16_t* w, uint16_t* canon, const LowerOps& ops) {
+static void lower_weights(const nrs_model_desc& d, const uint16_t* w, uint16_t* canon, const LowerOps& ops, uint32_t n_extra_dims = 0) {
 	memset(canon, 0, kCanonW * sizeof(uint16_t));
 	if (d.density_hidden_layers == 0) {
 		// no hidden layer in the density network (linear.json): y = W f by the first layer as (W, -W), the output layer subtracts relu(y) and relu(-y) -- as for the
@@ -233,6 +244,20 @@ static void lower_weights(const nrs_model_desc& d, const uint16_t* w, uint16_t* 
 	uint16_t* Wr2b = Wr3 + 16 * 64;      // [64 x 64]
 	auto identity = [&](uint16_t* M) { for (int i = 0; i < 64; ++i) M[i * 64 + i] = ops.one; };
 	const uint32_t L = d.rgb_hidden_layers;
+	std::vector<uint16_t> narrow;
+	if (n_extra_dims && d.sh_degree != 0 && L >= 1) {
+		// light directions: the first rgb matrix is [64 x 48].  Columns 0..31 take Wr1's place, columns 32..47 (light 3 | padding 13) go to Wr1x; the rest of the
+		// rgb part follows as in the plain network
+		uint16_t* Wr1x = Wr2b + 64 * 64; // [64 x 16]
+		const uint32_t n_rest = n_rgb_weights(d) - 64u * 32u;
+		narrow.resize(n_rgb_weights(d));
+		for (int row = 0; row < 64; ++row) {
+			memcpy(narrow.data() + row * 32, r + row * 48, 32 * 2);
+			memcpy(Wr1x + row * 16, r + row * 48 + 32, 16 * 2);
+		}
+		memcpy(narrow.data() + 64 * 32, r + 64 * 48, (size_t)n_rest * 2);
+		r = narrow.data();
+	}
 	if (d.sh_degree == 0 || L == 0) {
 		for (int row = 0; row < 8; ++row) {
 			if (d.sh_degree == 0) {
@@ -298,6 +323,7 @@ static void make_weight_fragments(const uint16_t* w, uint16_t* frag, uint16_t on
 	const uint16_t* Wr2 = Wr1 + 64 * 32;     // [64 x 64]
 	const uint16_t* Wr3 = Wr2 + 64 * 64;     // [16 x 64]
 	const uint16_t* Wr2b = Wr3 + 16 * 64;    // [64 x 64] (kCanonW: lower_weights' layout)
+	const uint16_t* Wr1x = Wr2b + 64 * 64;   // [64 x 16] columns 32..47 of a [64 x 48] first rgb matrix (light directions), else zeros
 	auto hidden_row = [](int mb, int g, int r) { return 32 * mb + (r & 3) + 8 * (r >> 2) + 4 * g; }; // D-tile row of reg r
 	auto at = [&](int f, int lane, int e) -> uint16_t& { return frag[((size_t)f * 64 + lane) * 8 + e]; };
 	memset(frag, 0, kWfragDeviceBytes);
@@ -326,6 +352,7 @@ static void make_weight_fragments(const uint16_t* w, uint16_t* frag, uint16_t on
 				const int kd = (e & 3) + 8 * (e >> 2) + 4 * g; // density-output row in element e
 				at(8 + mb * 2 + 0, lane, e) = Wr1[(32 * mb + i) * 32 + kd];
 				at(8 + mb * 2 + 1, lane, e) = Wr1[(32 * mb + i) * 32 + 16 + 8 * g + e]; // SH coefficient 8g+e
+				at(38 + mb, lane, e) = Wr1x[(32 * mb + i) * 16 + 8 * g + e];            // R1L: light component / padding one 8g+e (rows as in R1)
 			}
 		}
 	}
@@ -487,11 +514,35 @@ int nrs_model_level_table(const nrs_model_desc* d, float* scale, uint32_t* resol
 	return NRS_OK;
 }
 
-int nrs_model_create(nrs_ctx* ctx, const nrs_model_desc* desc, nrs_model** out) {
-	if (!ctx || !desc || !out) return fail(NRS_ERR_INVALID_ARG, "nrs_model_create: NULL argument");
+size_t nrs_model_n_params_ex(const nrs_model_desc* d, uint32_t n_extra_dims) {
+	if (!d || !desc_supported(*d) || (n_extra_dims != 0u && n_extra_dims != 3u) || extra_dims_refusal(*d, n_extra_dims)) return 0;
+	return nrs_model_n_params(d) + (n_extra_dims ? 64u * 16u : 0u);
+}
+static int model_create(nrs_ctx* ctx, const nrs_model_desc* desc, uint32_t n_extra_dims, nrs_model** out, const char* who);
+int nrs_model_create(nrs_ctx* ctx, const nrs_model_desc* desc, nrs_model** out) { return model_create(ctx, desc, 0u, out, "nrs_model_create"); }
+int nrs_model_create_ex(nrs_ctx* ctx, const nrs_model_desc* desc, uint32_t n_extra_dims, nrs_model** out) { return model_create(ctx, desc, n_extra_dims, out, "nrs_model_create_ex"); }
+static void update_light(nrs_model* m) { // m_nerf.light_dir.normalized() (testbed_nerf.cu:3135), then warp_direction in fp32 as the sample generators do (:649, :690)
+	const float* l = m->light_dir;
+	const float n = std::sqrt(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+	for (int k = 0; k < 3; ++k) m->dm.light01[k] = (l[k] / n + 1.0f) * 0.5f;
+}
+int nrs_model_n_extra_dims(const nrs_model* m) { return m ? (int)m->n_extra_dims : 0; }
+int nrs_model_set_light_dir(nrs_model* m, const float dir[3]) {
+	if (!m || !dir) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_light_dir: NULL argument");
+	const float n2 = dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2];
+	if (!std::isfinite(n2) || !(n2 > 0.f)) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_light_dir: the direction must be finite and non-zero (it is normalised at use)");
+	for (int k = 0; k < 3; ++k) m->light_dir[k] = dir[k];
+	update_light(m);
+	return NRS_OK;
+}
+static int model_create(nrs_ctx* ctx, const nrs_model_desc* desc, uint32_t n_extra_dims, nrs_model** out, const char* who) {
+	if (!ctx || !desc || !out) return fail(NRS_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	if (n_extra_dims != 0u && n_extra_dims != 3u) return fail(NRS_ERR_UNSUPPORTED, "nrs_model_create_ex: n_extra_dims must be 0 or 3 (light directions, dataset.has_light_dirs)");
+	if (desc_supported(*desc))
+		if (const char* why = extra_dims_refusal(*desc, n_extra_dims)) return fail(NRS_ERR_UNSUPPORTED, std::string("nrs_model_create_ex: ") + why);
 	if (!desc_supported(*desc)) return fail(NRS_ERR_UNSUPPORTED, "model description outside configs/nerf/base.json's family (hash grid 16 x 2, 64-wide density network of 0..1 hidden layers, rgb network of 0..3 hidden layers or none)");
 	for (int k = 0; k < 3; ++k)
-		if (!(desc->aabb_max[k] > desc->aabb_min[k])) return fail(NRS_ERR_INVALID_ARG, "nrs_model_create: empty aabb");
+		if (!(desc->aabb_max[k] > desc->aabb_min[k])) return fail(NRS_ERR_INVALID_ARG, std::string(who) + ": empty aabb");
 	HIP_TRY(hipSetDevice(ctx->device));
 	nrs_model* m = new (std::nothrow) nrs_model();
 	if (!m) return fail(NRS_ERR_STATE, "out of host memory");
@@ -508,6 +559,8 @@ int nrs_model_create(nrs_ctx* ctx, const nrs_model_desc* desc, nrs_model** out) 
 	}
 	m->dm.rgb_deep = desc->sh_degree != 0 && desc->rgb_hidden_layers == 3 ? 1u : 0u;
 	m->dm.no_dir = desc->sh_degree == 0 ? 1u : 0u;
+	m->n_extra_dims = m->dm.n_extra_dims = n_extra_dims;
+	update_light(m);
 	m->dm.rgb_activation = desc->rgb_activation;
 	m->dm.density_activation = desc->density_activation;
 	hipError_t he = hipMalloc((void**)&m->d_grid, (size_t)m->total_entries * 4);
@@ -519,7 +572,7 @@ int nrs_model_create(nrs_ctx* ctx, const nrs_model_desc* desc, nrs_model** out) 
 	if (he == hipSuccess) he = hipMemset(m->d_density_grid, 0, (size_t)kGridVol * kCascades * 4);
 	if (he != hipSuccess) {
 		nrs_model_destroy(m);
-		return fail_hip(he, "nrs_model_create: device allocation");
+		return fail_hip(he, n_extra_dims ? "nrs_model_create_ex: device allocation" : "nrs_model_create: device allocation");
 	}
 	m->dm.grid = m->d_grid;
 	m->dm.wfrag = m->d_wfrag;
@@ -705,7 +758,7 @@ size_t nrs_model_cell_cache_bytes(const nrs_model* m, uint32_t* n_levels) {
 
 int nrs_model_set_params(nrs_model* m, const void* h_params_fp16, size_t n_params) {
 	if (!m || !h_params_fp16) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_params: NULL argument");
-	const uint32_t n_mlp = n_mlp_weights(m->desc);
+	const uint32_t n_mlp = n_mlp_weights(m->desc, m->n_extra_dims);
 	const size_t expect = (size_t)n_mlp + (size_t)m->total_entries * 2;
 	if (n_params != expect) {
 		char buf[160];
@@ -715,7 +768,7 @@ int nrs_model_set_params(nrs_model* m, const void* h_params_fp16, size_t n_param
 	HIP_TRY(hipSetDevice(m->ctx->device));
 	const uint16_t* w = (const uint16_t*)h_params_fp16;
 	std::vector<uint16_t> canon(kCanonW), frag(kWfragDeviceBytes / 2);
-	lower_weights(m->desc, w, canon.data(), kLowerValues);
+	lower_weights(m->desc, w, canon.data(), kLowerValues, m->n_extra_dims);
 	make_weight_fragments(canon.data(), frag.data());
 	HIP_TRY(hipMemcpy(m->d_wfrag, frag.data(), kWfragDeviceBytes, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(m->d_grid, w + n_mlp, (size_t)m->total_entries * 4, hipMemcpyHostToDevice));
@@ -730,7 +783,7 @@ int nrs_model_set_params(nrs_model* m, const void* h_params_fp16, size_t n_param
 // this call.  Copy semantics: call it again after every optimiser step (the reference's renderer reads the blob in place; ours is a transformed copy).
 int nrs_model_set_params_device(nrs_model* m, const void* d_params_fp16, size_t n_params, void* stream) {
 	if (!m || !d_params_fp16) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_params_device: NULL argument");
-	const uint32_t n_mlp = n_mlp_weights(m->desc);
+	const uint32_t n_mlp = n_mlp_weights(m->desc, m->n_extra_dims);
 	const size_t expect = (size_t)n_mlp + (size_t)m->total_entries * 2;
 	if (n_params != expect) {
 		char buf[160];
@@ -741,10 +794,10 @@ int nrs_model_set_params_device(nrs_model* m, const void* d_params_fp16, size_t 
 	hipStream_t s = (hipStream_t)stream;
 	const uint16_t* d = (const uint16_t*)d_params_fp16;
 	if (!m->d_wfrag_src) { // the fragment permutation as indices: run the host routine on the identity (index + 1; 0 stays "padding")
-		static_assert(kDensityW + 64 * 32 + 2 * 64 * 64 + 16 * 64 < kFragNegate, "weight indices + 1 fit 15 bits");
+		static_assert(kDensityW + 64 * 48 + 2 * 64 * 64 + 16 * 64 < kFragNegate, "weight indices + 1 fit 15 bits");
 		std::vector<uint16_t> ident(n_mlp), canon(kCanonW), src(kWfragDeviceBytes / 2);
 		for (size_t i = 0; i < ident.size(); ++i) ident[i] = (uint16_t)(i + 1);
-		lower_weights(m->desc, ident.data(), canon.data(), kLowerIndices);
+		lower_weights(m->desc, ident.data(), canon.data(), kLowerIndices, m->n_extra_dims);
 		make_weight_fragments(canon.data(), src.data(), kFragOne);
 		HIP_TRY(hipMalloc((void**)&m->d_wfrag_src, kWfragDeviceBytes));
 		const hipError_t up = hipMemcpy(m->d_wfrag_src, src.data(), kWfragDeviceBytes, hipMemcpyHostToDevice);
@@ -880,6 +933,15 @@ int nrs_network_inference(nrs_model* m, void* stream, uint32_t n, const float* d
 	NRS_TRY(launch_network(m->dm, 0, n, d_in, NRS_NETWORK_INPUT_FLOATS, d_out, ld_out, layout, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
+int nrs_network_inference_strided(nrs_model* m, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout) {
+	int s = check_net(m, d_in, d_out, "nrs_network_inference_strided");
+	if (s != NRS_OK) return s;
+	if (ld_in < NRS_NETWORK_INPUT_FLOATS) return fail(NRS_ERR_INVALID_ARG, "nrs_network_inference_strided: ld_in < 7");
+	if (layout == NRS_PLANES && ld_out < n) return fail(NRS_ERR_INVALID_ARG, "nrs_network_inference_strided: ld_out < n");
+	HIP_TRY(hipSetDevice(m->ctx->device));
+	NRS_TRY(launch_network(m->dm, 0, n, d_in, ld_in, d_out, ld_out, layout, m->ctx->n_cus, stream, m->n_extra_dims != 0u && ld_in >= 10u));
+	return NRS_OK;
+}
 int nrs_network_density(nrs_model* m, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout) {
 	int s = check_net(m, d_in, d_out, "nrs_network_density");
 	if (s != NRS_OK) return s;
@@ -900,8 +962,8 @@ int nrs_network_input_gradient(nrs_model* m, void* stream, uint32_t n, const flo
 int nrs_network_visualize_activation(nrs_model* m, void* stream, uint32_t layer, uint32_t dimension, uint32_t n, const float* d_in, float* d_out) {
 	const int st = check_net(m, d_in, d_out, "nrs_network_visualize_activation");
 	if (st != NRS_OK) return st;
-	if (dimension >= network_layer_width(m->desc, layer))
-		return fail(NRS_ERR_INVALID_ARG, "nrs_network_visualize_activation: no such unit (layers: hash grid 32 | density hidden 64 | rgb input 32 | one of 64 per rgb hidden layer)");
+	if (dimension >= network_layer_width(m->desc, layer, m->n_extra_dims))
+		return fail(NRS_ERR_INVALID_ARG, "nrs_network_visualize_activation: no such unit (layers: hash grid 32 | density hidden 64 | rgb input 32, 48 with light directions | one of 64 per rgb hidden layer)");
 	HIP_TRY(hipSetDevice(m->ctx->device));
 	NRS_TRY(launch_network(m->dm, 4, n, d_in, NRS_NETWORK_INPUT_FLOATS, d_out, 1, (int)(kernel_layer(m->desc, layer) | (dimension << 8)), m->ctx->n_cus, stream));
 	return NRS_OK;
@@ -1488,7 +1550,7 @@ static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* co
 	if (!m->have_params) return fail(NRS_ERR_STATE, "nrs_render_nerf: parameters not set (nrs_model_set_params)");
 	if (!m->have_bitfield) return fail(NRS_ERR_STATE, "nrs_render_nerf: occupancy not set (nrs_model_set_density_bitfield/_grid)");
 	{ const int pc = check_march_params(*p, "nrs_render_nerf"); if (pc != NRS_OK) return pc; }
-	if (p->render_mode == NRS_RENDER_ENCODING_VIS && p->visualized_dimension >= network_layer_width(m->desc, p->visualized_layer))
+	if (p->render_mode == NRS_RENDER_ENCODING_VIS && p->visualized_dimension >= network_layer_width(m->desc, p->visualized_layer, m->n_extra_dims))
 		return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: EncodingVis: visualized_layer is hash grid 32 | density hidden 64 | rgb input 32 | one of 64 per rgb hidden layer (base.json: 0..4) and visualized_dimension a unit of it");
 	if (!std::isfinite(p->glow_y_cutoff) || p->glow_mode > 31u) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: glow_mode is a 5-bit mask and glow_y_cutoff must be finite");
 	if (p->distortion_mode > 2u) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: distortion_mode must be 0 (None), 1 (Iterative) or 2 (FTheta)");
@@ -1592,6 +1654,18 @@ static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* co
 		// roundings, no forced schedule); everything else of such a network runs the DEEP twins of the catch-all (launch_render)
 		static const bool env_sched = (dev_knob("NRS_TEAM") && atoi(dev_knob("NRS_TEAM")) != 0) || (dev_knob("NRS_HYBRID") && atoi(dev_knob("NRS_HYBRID")) == 0) || dev_knob("NRS_RENDER_CFG");
 		const bool plain = !a.any_poisson && !a.any_affine && m->dm.numerics == 0u && !ctx->lane_teams && !env_sched && !(a.dbg & 4u);
+		if (!plain) a.extra = 1u;
+	}
+	if (m->n_extra_dims) {
+		// Light directions: the automatic schedule has a LIGHT twin of the default kernel for the plain case (Shade / Cost with a pinhole camera, no operators or cage edits
+		// without the membrane correction, default roundings, no forced schedule); everything else such a network renders runs its catch-all instantiation (launch_render).
+		// The membrane correction and the measurement routes have no instantiation with the light term: refused, never rendered without it.
+		if (a.any_poisson && p->apply_operators) return fail(NRS_ERR_UNSUPPORTED, "nrs_render_nerf: the membrane correction (apply_poisson) is not supported for a network with light directions (n_extra_dims = 3)");
+		a.any_poisson = 0; // (operators switched off: the edits are not looked at)
+		if ((a.dbg & 4u) || dev_knob("NRS_RENDER_CFG")) return fail(NRS_ERR_UNSUPPORTED, "nrs_render_nerf: the wave log (NRS_DEBUG bit 2) and NRS_RENDER_CFG are not supported for a network with light directions (n_extra_dims = 3)");
+		a.gate = 0; // (the L2 phase gate is a schedule of the plain kernel alone: such a scene renders ungated)
+		static const bool env_sched = (dev_knob("NRS_TEAM") && atoi(dev_knob("NRS_TEAM")) != 0) || (dev_knob("NRS_HYBRID") && atoi(dev_knob("NRS_HYBRID")) == 0);
+		const bool plain = !a.any_affine && m->dm.numerics == 0u && !m->dm.rgb_deep && !ctx->lane_teams && !env_sched;
 		if (!plain) a.extra = 1u;
 	}
 	if (p->render_mode == NRS_RENDER_SLICE) { // tn:3109-3162: no marching at all; one network evaluation per owned pixel

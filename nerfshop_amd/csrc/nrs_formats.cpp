@@ -355,6 +355,7 @@ struct nrs_snapshot {
 	std::vector<uint16_t> params;   // fp16 bits, tcnn order
 	std::vector<float> density_grid; // [5 * 128^3]
 	uint32_t training_step = 0;
+	uint32_t n_extra_dims = 0;      // 3: trained with light directions (nrs_snapshot_open_ex with NRS_SNAPSHOT_ALLOW_LIGHT_DIRS)
 	bool have_camera = false;
 	float camera[12] = {0};
 };
@@ -372,8 +373,14 @@ struct nrs_edits {
 
 extern "C" {
 
-int nrs_snapshot_open(const char* path, nrs_snapshot** out) {
-	if (!path || !out) return fmt_fail(NRS_ERR_INVALID_ARG, "nrs_snapshot_open: NULL argument");
+static int snapshot_open(const char* path, uint32_t flags, nrs_snapshot** out, const char* who);
+int nrs_snapshot_open(const char* path, nrs_snapshot** out) { return snapshot_open(path, 0u, out, "nrs_snapshot_open"); }
+int nrs_snapshot_open_ex(const char* path, uint32_t flags, nrs_snapshot** out) { return snapshot_open(path, flags, out, "nrs_snapshot_open_ex"); }
+uint32_t nrs_snapshot_n_extra_dims(const nrs_snapshot* s) { return s ? s->n_extra_dims : 0u; }
+static int snapshot_open(const char* path, uint32_t flags, nrs_snapshot** out, const char* who) {
+	if (!path || !out) return fmt_fail(NRS_ERR_INVALID_ARG, std::string(who) + ": NULL argument");
+	if (flags & ~NRS_SNAPSHOT_ALLOW_LIGHT_DIRS) return fmt_fail(NRS_ERR_INVALID_ARG, "nrs_snapshot_open_ex: unknown flag");
+	const bool allow_light = (flags & NRS_SNAPSHOT_ALLOW_LIGHT_DIRS) != 0u;
 	try {
 		const std::string raw = maybe_inflate(read_file(path));
 		MsgpackReader rd{(const uint8_t*)raw.data(), (const uint8_t*)raw.data() + raw.size()};
@@ -432,11 +439,13 @@ int nrs_snapshot_open(const char* path, nrs_snapshot** out) {
 		// Light directions (NerfCoordinate::set_with_optional_light_dir, nerf.h:73-93; n_extra_dims = 3 when dataset.has_light_dirs, testbed.cu:2318): three more network
 		// inputs per sample that this path does not carry.  Neither save_snapshot nor the dataset's to_json stores the flag (json_binding.h:136-160), so it is
 		// recognised by the keys a writer MAY add and -- below -- by the size of the parameter blob, which such a network cannot hide.
+		bool light_keys = false;
 		{
 			const Value* nerf_v = snap->find("nerf");
 			const Value* ds = nerf_v ? nerf_v->find("dataset") : nullptr;
 			auto truthy = [](const Value* v) { return v && ((v->kind == Value::Bool && v->b) || (v->is_number() && v->number() != 0.0)); };
-			if ((ds && (truthy(ds->find("has_light_dirs")) || truthy(ds->find("n_extra_dims")))) || (nerf_v && truthy(nerf_v->find("n_extra_dims"))) || truthy(root.find("n_extra_dims")))
+			light_keys = (ds && (truthy(ds->find("has_light_dirs")) || truthy(ds->find("n_extra_dims")))) || (nerf_v && truthy(nerf_v->find("n_extra_dims"))) || truthy(root.find("n_extra_dims"));
+			if (light_keys && !allow_light)
 				throw Unsupported("the snapshot was trained with light directions (has_light_dirs / n_extra_dims = 3): this path renders position + view direction only");
 		}
 		// every hyper-parameter is validated BEFORE it is used in arithmetic (a crafted file must be refused, not divide by zero or shift by 200)
@@ -479,17 +488,25 @@ int nrs_snapshot_open(const char* path, nrs_snapshot** out) {
 		if (n_expected == 0) throw Unsupported("network architecture outside configs/nerf/base.json's family (hash grid 16 x 2, 64-wide density network with one hidden layer, rgb network of 0..3 hidden layers on SH degree 4 or none)");
 		{ // a network with 3 extra input dimensions: the direction encoding grows from 16 to 16 + 3 -> padded to 32, i.e. the rgb network's first matrix from [64 x 32] to [64 x 48]
 			const size_t n_light = n_expected + (size_t)d.n_neurons * 16u, bytes = ptype == "float" ? 4u : 2u;
-			if (has_dir && d.rgb_hidden_layers > 0 && pb.s.size() == n_light * bytes)
+			const bool light_size = has_dir && d.rgb_hidden_layers > 0 && pb.s.size() == n_light * bytes;
+			if (light_size && !allow_light)
 				throw Unsupported("params_binary has the size of this architecture WITH 3 extra input dimensions (light directions, n_extra_dims = 3): not rendered by this path");
+			if (light_keys || light_size) { // (allowed) the network nrs_model_create_ex(..., 3, ...) builds: sh_degree 4 with 1..3 rgb hidden layers
+				if (!has_dir) throw Unsupported("light directions (n_extra_dims = 3) with NerfNetworkNoDir (no direction encoding) are not supported");
+				if (d.rgb_hidden_layers == 0) throw Unsupported("light directions (n_extra_dims = 3) with the 0-layer CutlassMLP rgb network are not supported");
+				s->n_extra_dims = 3;
+			}
 		}
+		const size_t n_stored = s->n_extra_dims ? nrs_model_n_params_ex(&d, 3u) : n_expected;
+		if (n_stored == 0) throw Unsupported("network architecture with light directions outside the supported family (SH degree 4, rgb network of 1..3 hidden layers)");
 		if (ptype == "float") {
-			if (pb.s.size() != n_expected * 4) throw std::runtime_error("params_binary has the wrong size for this architecture");
-			s->params.resize(n_expected);
-			for (size_t k = 0; k < n_expected; ++k) { float f; memcpy(&f, pb.s.data() + 4 * k, 4); s->params[k] = float_to_half(f); }
+			if (pb.s.size() != n_stored * 4) throw std::runtime_error("params_binary has the wrong size for this architecture");
+			s->params.resize(n_stored);
+			for (size_t k = 0; k < n_stored; ++k) { float f; memcpy(&f, pb.s.data() + 4 * k, 4); s->params[k] = float_to_half(f); }
 		} else {
-			if (pb.s.size() != n_expected * 2) throw std::runtime_error("params_binary has the wrong size for this architecture");
-			s->params.resize(n_expected);
-			memcpy(s->params.data(), pb.s.data(), n_expected * 2);
+			if (pb.s.size() != n_stored * 2) throw std::runtime_error("params_binary has the wrong size for this architecture");
+			s->params.resize(n_stored);
+			memcpy(s->params.data(), pb.s.data(), n_stored * 2);
 		}
 		// density grid: float [5*128^3] from save_snapshot (:3097), fp16 [(max_cascade+1)*128^3] from export_snapshot (:3139-3146)
 		const Value& gb = snap->at("density_grid_binary");
@@ -514,9 +531,9 @@ int nrs_snapshot_open(const char* path, nrs_snapshot** out) {
 		*out = s.release();
 		return NRS_OK;
 	} catch (const Unsupported& e) {
-		return fmt_fail(NRS_ERR_UNSUPPORTED, std::string("nrs_snapshot_open('") + path + "'): unsupported: " + e.what());
+		return fmt_fail(NRS_ERR_UNSUPPORTED, (std::string(who) + "('") + path + "'): unsupported: " + e.what());
 	} catch (const std::exception& e) {
-		return fmt_fail(NRS_ERR_INVALID_ARG, std::string("nrs_snapshot_open('") + path + "'): " + e.what());
+		return fmt_fail(NRS_ERR_INVALID_ARG, (std::string(who) + "('") + path + "'): " + e.what());
 	}
 }
 void nrs_snapshot_close(nrs_snapshot* s) { delete s; }

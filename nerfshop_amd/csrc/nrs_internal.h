@@ -30,7 +30,9 @@ constexpr uint32_t kRgbW = 64 * 32 + 64 * 64 + 16 * 64;     // rgb MLP params (b
 // other members of configs/nerf/'s family -- rgb network with 0 / 1 / 3 hidden layers, no rgb network at all -- are LOWERED onto it when their parameters
 // arrive (lower_weights, nrs_api.cpp): matrices of 0 / +-1 that reproduce the smaller network's values exactly.  The canonical blob the MFMA fragments are
 // cut from: [Wd1 64x32 | Wd2 16x64 | Wr1 64x32 | Wr2 64x64 | Wr3 16x64 | Wr2b 64x64 (third hidden layer, base_3layer.json)].
-constexpr uint32_t kCanonW = kDensityW + kRgbW + 64 * 64;
+// A network trained with light directions (n_extra_dims = 3) appends Wr1x [64 x 16]: columns 32..47 of its [64 x 48] first rgb matrix (the warped light
+// direction and the Identity encoding's padding ones); zeros for every other network.
+constexpr uint32_t kCanonW = kDensityW + kRgbW + 64 * 64 + 64 * 16;
 
 // One hash-grid level as the kernels consume it (staged in LDS, 48 B).
 struct LevelParams {
@@ -55,9 +57,10 @@ struct LevelParams {
 // 0..7, hi = 8..15) back into fp32 accumulator registers exactly -- the fp16-accumulator model (NRS_MLP_ACC_FP16) rounds the running sum after every k step,
 // and the way back from packed halfs through the matrix core costs two MFMA issues (the pipe is 10 % busy) instead of sixteen VALU conversions.
 // These 26 fragments are staged into LDS.  Behind them, in HBM only: Bwd[ks] (4), the A operands of dL/dfeatures = W1^T dL/dhidden (render mode Normals),
-// and R2b[mb][ks] (8), the third hidden layer of an rgb network that has one (DeviceModel::rgb_deep; base_3layer.json).
+// R2b[mb][ks] (8), the third hidden layer of an rgb network that has one (DeviceModel::rgb_deep; base_3layer.json), and R1L[mb] (2), the third k block of
+// rgb layer 0 of a network trained with light directions (DeviceModel::n_extra_dims; rows in R1's order, k = 8 g + e <-> input column 32 + k).
 constexpr uint32_t kNumFrags = 26;
-constexpr uint32_t kNumFragsDevice = 38;
+constexpr uint32_t kNumFragsDevice = 40;
 constexpr uint32_t kFragBytes = 64 * 8 * 2;
 constexpr uint32_t kWfragBytes = kNumFrags * kFragBytes; // 26 KiB: the LDS image
 constexpr uint32_t kWfragDeviceBytes = kNumFragsDevice * kFragBytes;
@@ -96,6 +99,8 @@ struct DeviceModel {
 	uint32_t        numerics;  // bit 0: nrs_grid_acc NETWORK, bit 1: nrs_mlp_acc FP16 (nrs_model_set_numerics); 0 = the default roundings
 	uint32_t        rgb_deep;  // the rgb network has a third hidden layer (fragments R2b, read from wfrag in HBM): base_3layer.json
 	uint32_t        no_dir;    // NerfNetworkNoDir (base_nodir.json): the direction rows of caller batches are not read
+	uint32_t        n_extra_dims; // 0, or 3: the network was trained with light directions (fragments R1L, read from wfrag in HBM)
+	float           light01[3];   // warp_direction(normalised nrs_model_set_light_dir) in fp32: what every sample gets that brings no light direction of its own
 };
 
 // AffineBoundingBox as the kernels test it (affine_bounding_box.cuh:83-88): u.(p - min) in [0, u.u) etc.
@@ -195,8 +200,9 @@ int launch_slice(const DeviceModel& m, const RenderArgs& a, int n_cus, void* str
 int launch_trace_samples(const DeviceModel& m, const nrs_render_params& p, uint32_t n_pixels, const uint32_t* d_pixel_idx,
                          uint32_t max_samples, float* d_t, float* d_dt, uint32_t* d_count, void* stream);
 // mode 0: full inference (16 channels, c3 = density), 1: density MLP outputs, 2: hash-grid features [n x 32]
+// ld_light: floats 7..9 of a record are that sample's warped light direction (a model with n_extra_dims = 3 and ld_in >= 10); else DeviceModel::light01
 int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out,
-                   int layout, int n_cus, void* stream);
+                   int layout, int n_cus, void* stream, bool per_sample_light = false);
 int launch_selection_rays(const DeviceModel& m, const nrs_render_params& p, const int32_t* d_pixels, uint32_t n, float threshold,
                           float* d_positions, uint32_t* d_cells, uint8_t* d_found, void* stream);
 int launch_poisson_fit(const DeviceModel& m, uint32_t n_verts, uint32_t n_sh, const float* d_coords, const void* d_net, int is_inside, float scale,

@@ -237,7 +237,11 @@ constexpr uint32_t kBatchXYBits = 13u, kBatchXYMask = (1u << kBatchXYBits) - 1u;
 static_assert((NRS_SPP_BATCH_MAX - 1u) >> (32u - 2u * kBatchXYBits) == 0u, "a ring entry holds the sample index beside the pixel");
 template <int WAVES, int OCC, bool PROF, bool POISSON, bool AFFINE, int TEAM, int NUM = 0, int XTRA = 0, bool BATCH = false>
 __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const RenderArgs& a_arg) {
-	constexpr bool EXTRA = XTRA >= 1 && XTRA <= 4, INTRO = XTRA == 2 || XTRA == 4, DEEP = XTRA >= 3 && XTRA <= 5; // (3 / 4: 1 / 2 for a network whose rgb MLP has a third hidden layer, base_3layer.json; 5: that layer alone)
+	constexpr bool EXTRA = (XTRA >= 1 && XTRA <= 4) || XTRA == 8, INTRO = XTRA == 2 || XTRA == 4 || XTRA == 8, DEEP = (XTRA >= 3 && XTRA <= 5) || XTRA == 8; // (3 / 4: 1 / 2 for a network whose rgb MLP has a third hidden layer, base_3layer.json; 5: that layer alone)
+	// 7 / 8: a network trained with light directions (DeviceModel::n_extra_dims = 3; rgb_mlp's LIGHT).  7 = the light term and nothing else: the twin of the default kernel
+	// (plain frames and cage edits on the automatic schedule); 8 = the catch-all of such a network: EXTRA + INTRO, the third hidden layer where the network has one
+	// (DeviceModel::rgb_deep, a wave-uniform run-time branch here), every numerics, AffineDuplication -- whatever 7 does not serve.
+	constexpr bool LIGHT = XTRA == 7 || XTRA == 8;
 	// four levels per round trip in the gathers (encode_to_lds QUADS): the automatic schedule's instantiations with the default or the fully tiny-cuda-nn roundings -- since
 	// round 6 the membrane instantiation too (both of its gathers: 9.68 -> 10.06 Gsamples/s, same registers; profiles/r06/ab_poisson_quads.txt)
 	constexpr bool kQuads = TEAM == 0 && !EXTRA && NUM >= 0;
@@ -670,7 +674,10 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 		  asm volatile("" :: "v"(sink)); }
 #endif
 		uint32_t res_d = 0, res_rg = 0, res_b = 0;
-		const half8* deep_w = DEEP ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr; // (the third rgb hidden layer's fragments are read from HBM)
+		const half8* deep_w = (DEEP && (XTRA != 8 || m2.rgb_deep)) ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr; // (the third rgb hidden layer's fragments are read from HBM)
+		// LIGHT: the frame's light direction (nrs_model_set_light_dir), the same for every sample: the B operand of layer 0's third k step, its A fragments in HBM
+		const half8* light_w = (LIGHT && (XTRA != 8 || m2.n_extra_dims)) ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr;
+		const half8 lb = LIGHT ? light_operand(g, m2.light01[0], m2.light01[1], m2.light01[2]) : half8{};
 		#pragma unroll 1
 		for (int b = 0; b < 2; ++b) {
 			const int sel = (b != g) ? 1 : 0;
@@ -678,7 +685,7 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 			half8 dout = x0, rout = x1;
 			if (!(a2.dbg & 2u)) {
 				dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, x0, x1);
-				rout = rgb_mlp_num<NUM, DEEP>(nm, sm.ml.w, lane, dout, sel ? sh_par : sh_own, deep_w);
+				rout = rgb_mlp_num<NUM, DEEP, LIGHT>(nm, sm.ml.w, lane, dout, sel ? sh_par : sh_own, deep_w, light_w, lb);
 			}
 			const u32x4 dd = __builtin_bit_cast(u32x4, dout), rr = __builtin_bit_cast(u32x4, rout);
 			// rows 0..2 of a block sit in its lanes 0..31; block 1's samples belong to the rays of lanes 32..63
@@ -704,6 +711,8 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 					const uint32_t L = dim >> 1;
 					const uint32_t w = ((L & 1u) == (uint32_t)g) ? fl.feat[L >> 1][0][lane] : fl.feat[L >> 1][1][lane ^ 32];
 					v = (float)__builtin_bit_cast(half2v, w)[dim & 1u];
+				} else if (LIGHT && layer == 2u && dim >= 32u) { // the Identity encoding of the light direction: units 32..34, then its padding ones
+					v = dim < 35u ? (float)(_Float16)m2i.light01[dim - 32u] : 1.0f;
 				} else if (layer == 2u && dim >= 16u) { // an SH coefficient of the own direction: 8 g .. 8 g + 7 are here, the others in the partner lane's sh_par
 					const uint32_t cidx = dim - 16u;
 					const float mine = (float)pick8(sh_own, (int)(cidx & 7u)), theirs = xchg32((float)pick8(sh_par, (int)(cidx & 7u)));
@@ -724,7 +733,7 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 							half8 din = x0;
 							if (layer >= 3u) din = acc16 ? density_mlp<true>(sm.ml.w, lane, x0, x1) : density_mlp<false>(sm.ml.w, lane, x0, x1);
 							const half8 shb = sel ? sh_par : sh_own;
-							val = acc16 ? mlp_hidden_activation<true>(sm.ml.w, lane, x0, x1, din, shb, layer, dim, deep_w) : mlp_hidden_activation<false>(sm.ml.w, lane, x0, x1, din, shb, layer, dim, deep_w);
+							val = acc16 ? mlp_hidden_activation<true, LIGHT>(sm.ml.w, lane, x0, x1, din, shb, layer, dim, deep_w, light_w, lb) : mlp_hidden_activation<false, LIGHT>(sm.ml.w, lane, x0, x1, din, shb, layer, dim, deep_w, light_w, lb);
 							half_of_row = tile_half(dim);
 						}
 						// the value of sample (b, j) sits in lane j + 32 * half_of_row; its ray is lane j + 32 * b
@@ -1162,10 +1171,11 @@ static int check_route(const DeviceModel& m, const RenderArgs& a, int waves, int
 	else if (a.any_affine && !affine) why = "an AffineDuplication operator needs AFFINE";
 	else if (a.any_poisson && !poisson) why = "the membrane correction needs POISSON";
 	else if (num != kNumRuntime && (uint32_t)num != m.numerics) why = "NUM does not match the model's numerics";
-	else if ((a.extra != 0u) != (extra >= 1 && extra <= 4)) why = "a.extra needs EXTRA 1..4 and only it";
-	else if ((m.rgb_deep != 0u) != (extra >= 3 && extra <= 5)) why = "a third rgb hidden layer needs EXTRA 3..5 and only it";
+	else if ((m.n_extra_dims != 0u) != (extra == 7 || extra == 8)) why = "a network with light directions needs EXTRA 7 or 8 and only they";
+	else if ((a.extra != 0u) != ((extra >= 1 && extra <= 4) || extra == 8)) why = "a.extra needs EXTRA 1..4 (8 with light directions) and only it";
+	else if (extra != 8 && (m.rgb_deep != 0u) != (extra >= 3 && extra <= 5)) why = "a third rgb hidden layer needs EXTRA 3..5 and only it";
 	else if (extra == 6 && !a.gate) why = "EXTRA 6 (GATE) without a.gate";
-	else if (intro && extra != 2 && extra != 4) why = "Normals / EncodingVis need EXTRA 2 or 4";
+	else if (intro && extra != 2 && extra != 4 && extra != 8) why = "Normals / EncodingVis need EXTRA 2, 4 or 8";
 	else if (prof && !(a.dbg & 4u)) why = "PROF without NRS_DEBUG bit 2";
 	else if (a.spp_count > 1u && !batch) why = "a batch of samples (spp_count > 1) needs BATCH";
 	else if (a.spp_count == 0u || a.spp_packets == 0u || a.n_packets != a.spp_count * a.spp_packets) why = "the queue is not spp_count times the packets of one sample";
@@ -1194,7 +1204,8 @@ static int launch_render_c128(const DeviceModel& m, const RenderArgs& a, int n_c
 	// amdgpu_num_vgpr is a target, not a limit: when the allocator went past 128 registers for this instantiation (3 waves per SIMD: 7.3 instead of 9.8
 	// Gsamples/s), the __launch_bounds__(512, 4) build of the same body -- which cannot -- is the one to launch
 	// (a batch twin that went past 128 runs where it is, at 3 waves per SIMD: no third build of the body for it)
-	if constexpr (!BATCH) { if (blocks_per_cu * WAVES < 16) return launch_render_cfg<false, WAVES, 4, PROF, POISSON, AFFINE, TEAM, NUM, XTRA>(m, a, n_cus, stream); }
+	// (the LIGHT twin, XTRA 7, has no third build either)
+	if constexpr (!BATCH && XTRA != 7) { if (blocks_per_cu * WAVES < 16) return launch_render_cfg<false, WAVES, 4, PROF, POISSON, AFFINE, TEAM, NUM, XTRA>(m, a, n_cus, stream); }
 	if (blocks_per_cu < 1) blocks_per_cu = 1;
 	uint32_t grid = (uint32_t)(n_cus * blocks_per_cu);
 	const uint32_t max_useful = (a.n_packets + WAVES - 1) / WAVES; // at least one packet per wave
@@ -1243,6 +1254,12 @@ int launch_render(const DeviceModel& m, const RenderArgs& a, int n_cus, void* st
 		return NRS_ERR_STATE;
 	}
 	#define NRS_ROUTE(fn, ...) (batch ? fn<true, __VA_ARGS__>(m, a, n_cus, s) : fn<false, __VA_ARGS__>(m, a, n_cus, s))
+	if (m.n_extra_dims) {
+		// light directions: the LIGHT twin of the default kernel, or the catch-all of such a network when a.extra is set (nrs_render_nerf decides, and refuses what neither
+		// serves; check_route turns away anything else that arrives here)
+		if (a.extra) return NRS_ROUTE(launch_render_cfg, 12, 3, false, false, true, 1, R, 8);
+		return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0, 0, 7);
+	}
 	if (a.extra) // render modes / show_accel / depth of field: the catch-all instantiation (every operator kind, membrane correction, one lane per ray)
 	{
 		// Normals / EncodingVis: the INTRO instantiation (145 / 165 VGPRs, no scratch: 12-wave workgroups at 3 waves per SIMD like the other modes)
@@ -1375,7 +1392,9 @@ __global__ __launch_bounds__(256) void slice_kernel(const DeviceModel m, const R
 			const int sel = (b != g) ? 1 : 0;
 			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
 			const half8 dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, x0, x1);
-			const half8 rout = rgb_mlp_num<NUM, true>(nm, sm.ml.w, lane, dout, sel ? sh_par : sh_own, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr);
+			// (a network trained with light directions: the frame's light direction for every pixel -- a wave-uniform branch, rgb_mlp's LIGHT)
+			const half8 rout = rgb_mlp_num<NUM, true, true>(nm, sm.ml.w, lane, dout, sel ? sh_par : sh_own, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
+			                                                m.n_extra_dims ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_operand(g, m.light01[0], m.light01[1], m.light01[2]));
 			const u32x4 dd = __builtin_bit_cast(u32x4, dout), rr = __builtin_bit_cast(u32x4, rout);
 			uint32_t vd = dd[0], vrg = rr[0], vb = rr[1];
 			if (b == 1) { vd = xchg32u(vd); vrg = xchg32u(vrg); vb = xchg32u(vb); }
@@ -1794,10 +1813,15 @@ constexpr int kNetWaves = 12;
 // MODE 3: NerfNetwork::input_gradient(stream, 3, ...) -> d density_raw / d position, f32 [n x 3]; MODE 4: visualize_activation(layer, dim) -> f32 [n]
 // (layout = layer | dim << 8); both as restated in oracle/nrs_oracle.cpp -- the callers of the render path's Normals / EncodingVis modes and of
 // compute_mesh_vertex_normals (tn:4491).
-template <int MODE, int NUM = 0>
-__global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4) ? 3 : 6) void network_kernel(const DeviceModel m, uint32_t n, const float* __restrict__ in, uint32_t ld_in,
-                                                      _Float16* __restrict__ out, uint32_t ld_out, int layout) {
+// LIGHT (modes 0 and 4): a network trained with light directions (DeviceModel::n_extra_dims = 3; rgb_mlp's LIGHT) -- every sample gets DeviceModel::light01, or, with
+// ld_light != 0, floats 7..9 of its own record (already warped: the reference's PitchedPtr<NerfCoordinate> with extra_stride).  Its MODE 0 serves the third hidden layer
+// too (a wave-uniform branch on DeviceModel::rgb_deep).  The instantiations without the flag are what they were before it existed.
+template <int MODE, int NUM = 0, bool LIGHT = false>
+__global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4 || LIGHT) ? 3 : 6) void network_kernel(const DeviceModel m, uint32_t n, const float* __restrict__ in, uint32_t ld_in,
+                                                      _Float16* __restrict__ out, uint32_t ld_out, int layout, uint32_t ld_light = 0u) {
 	constexpr bool FULL = MODE == 0 || MODE == 5; // (5: the full network with a third rgb hidden layer, DeviceModel::rgb_deep -- base_3layer.json)
+	const half8* light_w = LIGHT ? reinterpret_cast<const half8*>(m.wfrag) : nullptr;
+	const half8* deep_w = (MODE == 5 || (LIGHT && m.rgb_deep)) ? reinterpret_cast<const half8*>(m.wfrag) : nullptr;
 	__shared__ NetSmemT<kNetWaves> sm;
 	stage_model_to_lds(m, sm.ml);
 	const int lane = threadIdx.x & 63;
@@ -1810,12 +1834,19 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4) ? 3 : 6) v
 	for (uint32_t tile = wave_global; tile < n_tiles; tile += n_waves) {
 		const uint32_t s = tile * 64 + lane;
 		const bool have = s < n;
-		f3 wpos = mk3(0, 0, 0), wdir = mk3(0.5f, 0.5f, 0.5f);
+		f3 wpos = mk3(0, 0, 0), wdir = mk3(0.5f, 0.5f, 0.5f), wlight = mk3(m.light01[0], m.light01[1], m.light01[2]);
 		if (have) {
 			const float* c = in + (size_t)s * ld_in;
 			wpos = mk3(c[0], c[1], c[2]);
 			// (NerfNetworkNoDir never looks at the direction rows: a caller may leave them unset, and 0-weights do not stop a NaN)
 			if ((FULL || MODE == 4) && !m.no_dir) wdir = mk3(c[4], c[5], c[6]);
+			if (LIGHT && ld_light) wlight = mk3(c[7], c[8], c[9]);
+		}
+		// the light operands of the lane's own sample and of its partner's (lane ^ 32): block b's comes from the lanes 0..31, as for the SH coefficients
+		half8 lb_own = half8{}, lb_par = half8{};
+		if (LIGHT) {
+			lb_own = light_operand(g, wlight.x, wlight.y, wlight.z);
+			lb_par = light_operand(g, xchg32(wlight.x), xchg32(wlight.y), xchg32(wlight.z));
 		}
 		encode_to_lds<(NUM & 1) != 0>(gv, m.levels, sm.ml, fl, lane, g, wpos, have); // (four levels per round trip measured here: ray-ordered batches +-0, random ones -3.5 %: profiles/r06/ab_net_quads.txt; six waves per SIMD hide the trips)
 
@@ -1852,6 +1883,9 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4) ? 3 : 6) v
 				const uint32_t L = dim >> 1;
 				const uint32_t w = ((L & 1u) == (uint32_t)g) ? fl.feat[L >> 1][0][lane] : fl.feat[L >> 1][1][lane ^ 32];
 				v = (float)__builtin_bit_cast(half2v, w)[dim & 1u];
+			} else if (LIGHT && layer == 2u && dim >= 32u) { // the Identity encoding of the light direction (units 32..34) and its padding ones
+				const float l = dim == 32u ? wlight.x : (dim == 33u ? wlight.y : wlight.z);
+				v = dim < 35u ? (float)(_Float16)l : 1.0f;
 			} else if (layer == 2u && dim >= 16u) {
 				const half8 sh_own = encode_sh4(g, wdir), sh_par = encode_sh4(g, mk3(xchg32(wdir.x), xchg32(wdir.y), xchg32(wdir.z)));
 				const uint32_t cidx = dim - 16u;
@@ -1872,7 +1906,8 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4) ? 3 : 6) v
 					} else {
 						half8 din = x0;
 						if (layer >= 3u) din = density_mlp<(NUM & 2) != 0>(sm.ml.w, lane, x0, x1);
-						val = mlp_hidden_activation<(NUM & 2) != 0>(sm.ml.w, lane, x0, x1, din, sel ? sh_par : sh_own, layer, dim, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr);
+						val = mlp_hidden_activation<(NUM & 2) != 0, LIGHT>(sm.ml.w, lane, x0, x1, din, sel ? sh_par : sh_own, layer, dim, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
+						                                                   light_w, sel ? lb_par : lb_own);
 						half_of_row = tile_half(dim);
 					}
 					if (half_of_row != b) val = xchg32(val);
@@ -1909,7 +1944,7 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4) ? 3 : 6) v
 			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
 			const half8 dout = density_mlp<(NUM & 2) != 0>(sm.ml.w, lane, x0, x1);
 			half8 rout = dout;
-			if (FULL) rout = rgb_mlp<(NUM & 2) != 0, MODE == 5>(sm.ml.w, lane, dout, sel ? sh_par : sh_own, reinterpret_cast<const half8*>(m.wfrag));
+			if (FULL) rout = rgb_mlp<(NUM & 2) != 0, MODE == 5 || LIGHT, LIGHT>(sm.ml.w, lane, dout, sel ? sh_par : sh_own, deep_w, light_w, sel ? lb_par : lb_own);
 			const uint32_t sb = tile * 64 + 32 * b + j;
 			if (sb < n) {
 				uint32_t ldo = ld_out; // (opaque per tile: the eight 64-bit row offsets were hoisted out of the tile loop and, in the fp16-accumulator twins, spilled)
@@ -1928,8 +1963,10 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4) ? 3 : 6) v
 }
 
 int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout,
-                   int n_cus, void* stream) {
+                   int n_cus, void* stream, bool per_sample_light) {
 	if (n == 0) return NRS_OK;
+	if (per_sample_light && (!m.n_extra_dims || ld_in < 10u)) { snprintf(g_launch_err, sizeof(g_launch_err), "launch_network: per-sample light directions need n_extra_dims = 3 and ld_in >= 10"); return NRS_ERR_STATE; }
+	const uint32_t ld_light = per_sample_light ? 1u : 0u;
 	const uint32_t n_tiles = (n + 63) / 64;
 	uint32_t grid = (n_tiles + kNetWaves - 1) / kNetWaves;
 	const uint32_t cap = (uint32_t)n_cus * 2; // resident workgroups: the tiles are strided over them
@@ -1944,12 +1981,24 @@ int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in
 		case 2: NRS_NET_LAUNCH(MODE, 2); break;                 \
 		default: NRS_NET_LAUNCH(MODE, 3); break;                \
 	}
-	if (mode == 0 && m.rgb_deep) { NRS_NET_MODE(5) }
+#define NRS_NET_LIGHT(MODE, NUM) hipLaunchKernelGGL((network_kernel<MODE, NUM, true>), dim3(grid), dim3(64 * kNetWaves), 0, s, m, n, d_in, ld_in, out, ld_out, layout, ld_light)
+#define NRS_NET_MODE_LIGHT(MODE)                                \
+	switch (m.numerics & 3u) {                                  \
+		case 0: NRS_NET_LIGHT(MODE, 0); break;                  \
+		case 1: NRS_NET_LIGHT(MODE, 1); break;                  \
+		case 2: NRS_NET_LIGHT(MODE, 2); break;                  \
+		default: NRS_NET_LIGHT(MODE, 3); break;                 \
+	}
+	if (mode == 0 && m.n_extra_dims) { NRS_NET_MODE_LIGHT(0) }
+	else if (mode == 4 && m.n_extra_dims) { NRS_NET_MODE_LIGHT(4) }
+	else if (mode == 0 && m.rgb_deep) { NRS_NET_MODE(5) }
 	else if (mode == 0) { NRS_NET_MODE(0) }
 	else if (mode == 1) { NRS_NET_MODE(1) }
 	else if (mode == 3) { NRS_NET_MODE(3) }
 	else if (mode == 4) { NRS_NET_MODE(4) }
 	else { NRS_NET_MODE(2) }
+#undef NRS_NET_MODE_LIGHT
+#undef NRS_NET_LIGHT
 #undef NRS_NET_MODE
 #undef NRS_NET_LAUNCH
 	NRS_LAUNCH_CHECK("network_kernel launch");
@@ -2002,7 +2051,8 @@ __global__ __launch_bounds__(256) void grid_eval_kernel(const DeviceModel m, con
 			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
 			const half8 dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, x0, x1);
 			half8 rout = dout;
-			if (MODE == 1) rout = rgb_mlp_num<NUM, true>(nm, sm.ml.w, lane, dout, sh, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr);
+			if (MODE == 1) rout = rgb_mlp_num<NUM, true, true>(nm, sm.ml.w, lane, dout, sh, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
+			                                                  m.n_extra_dims ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_operand(g, m.light01[0], m.light01[1], m.light01[2]));
 			const u32x4 dd = __builtin_bit_cast(u32x4, dout), rr = __builtin_bit_cast(u32x4, rout);
 			uint32_t vd = dd[0], vrg = rr[0], vb = rr[1]; // rows 0..2 of a block sit in lanes 0..31
 			if (b == 1) { vd = xchg32u(vd); vrg = xchg32u(vrg); vb = xchg32u(vb); }

@@ -55,6 +55,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define NRS_FRAG_R2(mb, ks) (12 + (mb) * 4 + (ks))
 #define NRS_FRAG_R3(ks) (20 + (ks))
 #define NRS_FRAG_R2B(mb, ks) (30 + (mb) * 4 + (ks)) // (HBM only, like NRS_FRAG_BWD: the third rgb hidden layer of base_3layer.json)
+#define NRS_FRAG_R1L(mb) (38 + (mb)) // (HBM only: the third k block of rgb layer 0 of a network trained with light directions, n_extra_dims = 3)
 
 enum { KIND_DENSE = 0, KIND_HASHED = 1, KIND_MIXED = 2, KIND_RECORD = 3, KIND_SPARSE = 4, KIND_SKIP = 5 };
 
@@ -732,14 +733,31 @@ __device__ __forceinline__ void hidden_layer_64(const half8* lds_w, const half8*
 // RGB MLP [density out 16 | SH 16] -> 64 -> 64 -> 16 (3 used) for one block.  Same output row map.
 // DEEP instantiations take `deep_w` (wave-uniform; DeviceModel::wfrag when DeviceModel::rgb_deep, else null): a third hidden layer between the second and the
 // output layer, its fragments read from HBM (base_3layer.json; the other members of the family are lowered onto the two-layer shape, nrs_api.cpp lower_weights).
-template <bool ACC16 = false, bool DEEP = false>
-__device__ __forceinline__ half8 rgb_mlp(const half8* lds_w, int lane, half8 din, half8 sh, const half8* deep_w = nullptr) {
-	floatx16 a = mfma_first(lds_w[NRS_FRAG_R1(0, 0) * 64 + lane], din);
-	a = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_R1(0, 1) * 64 + lane], sh, a);
+// LIGHT instantiations take `light_w` (wave-uniform; DeviceModel::wfrag when DeviceModel::n_extra_dims, else null) and `lb`: a network trained with light
+// directions has a 48-wide input -- [density out 16 | SH 16 | Identity(light 3) padded with ones to 16] -- i.e. one more k step in layer 0 (25 MFMA issues per
+// block instead of 24), k order density, SH, light; its two A fragments R1L are read from HBM like the DEEP ones.  The instantiations without the flag are what
+// they were before it existed.
+// B operand of that k step (k = 8 (lane >> 5) + e): lanes 0..31 hold the warped light direction of sample column j, rounded to fp16 by the Identity encoding
+// (scale 1, offset 0), and five of the thirteen padding ones; lanes 32..63 the other eight.
+__device__ __forceinline__ half8 light_operand(int g, float l0, float l1, float l2) {
+	const _Float16 one = (_Float16)1.0f;
+	half8 r = {one, one, one, one, one, one, one, one};
+	if (g == 0) { r[0] = (_Float16)l0; r[1] = (_Float16)l1; r[2] = (_Float16)l2; }
+	return r;
+}
+template <bool ACC16, bool LIGHT>
+__device__ __forceinline__ floatx16 rgb_layer0_tile(const half8* lds_w, int lane, int mb, half8 din, half8 sh, const half8* light_w, half8 lb) {
+	floatx16 a = mfma_first(lds_w[NRS_FRAG_R1(mb, 0) * 64 + lane], din);
+	a = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_R1(mb, 1) * 64 + lane], sh, a);
+	if (LIGHT && light_w) a = mfma_step<ACC16>(lds_w, lane, light_w[NRS_FRAG_R1L(mb) * 64 + lane], lb, a);
+	return a;
+}
+template <bool ACC16 = false, bool DEEP = false, bool LIGHT = false>
+__device__ __forceinline__ half8 rgb_mlp(const half8* lds_w, int lane, half8 din, half8 sh, const half8* deep_w = nullptr, const half8* light_w = nullptr, half8 lb = half8{}) {
+	floatx16 a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 0, din, sh, light_w, lb);
 	half8 b0 = relu_pack(a, 0), b1 = relu_pack(a, 8);
 	NRS_STAGE_FENCE();
-	a = mfma_first(lds_w[NRS_FRAG_R1(1, 0) * 64 + lane], din);
-	a = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_R1(1, 1) * 64 + lane], sh, a);
+	a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 1, din, sh, light_w, lb);
 	half8 b2 = relu_pack(a, 0), b3 = relu_pack(a, 8);
 	NRS_STAGE_FENCE();
 	hidden_layer_64<ACC16>(lds_w, lds_w + NRS_FRAG_R2(0, 0) * 64, lane, b0, b1, b2, b3);
@@ -770,23 +788,22 @@ __device__ __forceinline__ _Float16 pick8(const half8& h, int e) {
 // Activation `unit` of hidden layer `layer` (1: density MLP hidden, 3 / 4 / 5: rgb MLP hidden 1 / 2 / 3 -- 5 with deep_w only) for one 32-sample block: the value of sample column j sits,
 // after the call, in the lanes whose half (lane >> 5) equals tile_half(unit); the other half returns another row.  din = density_mlp's output (layers 3, 4).
 __device__ __forceinline__ int tile_half(uint32_t unit) { return (int)((unit >> 2) & 1u); }
-template <bool ACC16>
-__device__ __forceinline__ float mlp_hidden_activation(const half8* lds_w, int lane, half8 x0, half8 x1, half8 din, half8 sh, uint32_t layer, uint32_t unit, const half8* deep_w = nullptr) {
+// (LIGHT, light_w, lb: as for rgb_mlp)
+template <bool ACC16, bool LIGHT = false>
+__device__ __forceinline__ float mlp_hidden_activation(const half8* lds_w, int lane, half8 x0, half8 x1, half8 din, half8 sh, uint32_t layer, uint32_t unit, const half8* deep_w = nullptr,
+                                                       const half8* light_w = nullptr, half8 lb = half8{}) {
 	const int mb = (int)((unit >> 5) & 1u), R = (int)(unit & 31u), r = (R & 3) + 4 * (R >> 3); // D register of row R in its lane half
 	floatx16 t;
 	if (layer == 1u) {
 		t = mfma_first(lds_w[NRS_FRAG_D1(mb, 0) * 64 + lane], x0);
 		t = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D1(mb, 1) * 64 + lane], x1, t);
 	} else if (layer == 3u) {
-		t = mfma_first(lds_w[NRS_FRAG_R1(mb, 0) * 64 + lane], din);
-		t = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_R1(mb, 1) * 64 + lane], sh, t);
+		t = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, mb, din, sh, light_w, lb);
 	} else {
-		floatx16 a = mfma_first(lds_w[NRS_FRAG_R1(0, 0) * 64 + lane], din);
-		a = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_R1(0, 1) * 64 + lane], sh, a);
+		floatx16 a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 0, din, sh, light_w, lb);
 		half8 b0 = relu_pack(a, 0), b1 = relu_pack(a, 8);
 		NRS_STAGE_FENCE();
-		a = mfma_first(lds_w[NRS_FRAG_R1(1, 0) * 64 + lane], din);
-		a = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_R1(1, 1) * 64 + lane], sh, a);
+		a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 1, din, sh, light_w, lb);
 		half8 b2 = relu_pack(a, 0), b3 = relu_pack(a, 8);
 		NRS_STAGE_FENCE();
 		const half8* w = lds_w + NRS_FRAG_R2(mb, 0) * 64;
@@ -889,10 +906,10 @@ __device__ __forceinline__ half8 density_mlp_num(uint32_t nm, const half8* lds_w
 	if (NUM == kNumRuntime ? (nm & 2u) != 0u : (NUM & 2) != 0) return density_mlp<true>(lds_w, lane, x0, x1);
 	return density_mlp<false>(lds_w, lane, x0, x1);
 }
-template <int NUM, bool DEEP = false>
-__device__ __forceinline__ half8 rgb_mlp_num(uint32_t nm, const half8* lds_w, int lane, half8 din, half8 sh, const half8* deep_w = nullptr) {
-	if (NUM == kNumRuntime ? (nm & 2u) != 0u : (NUM & 2) != 0) return rgb_mlp<true, DEEP>(lds_w, lane, din, sh, deep_w);
-	return rgb_mlp<false, DEEP>(lds_w, lane, din, sh, deep_w);
+template <int NUM, bool DEEP = false, bool LIGHT = false>
+__device__ __forceinline__ half8 rgb_mlp_num(uint32_t nm, const half8* lds_w, int lane, half8 din, half8 sh, const half8* deep_w = nullptr, const half8* light_w = nullptr, half8 lb = half8{}) {
+	if (NUM == kNumRuntime ? (nm & 2u) != 0u : (NUM & 2) != 0) return rgb_mlp<true, DEEP, LIGHT>(lds_w, lane, din, sh, deep_w, light_w, lb);
+	return rgb_mlp<false, DEEP, LIGHT>(lds_w, lane, din, sh, deep_w, light_w, lb);
 }
 
 // Exchange a value with the partner lane (l ^ 32): one ds_bpermute.

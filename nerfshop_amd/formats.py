@@ -18,15 +18,20 @@ from ._abi import ModelDesc, TetMesh, check
 
 
 class Snapshot:
-    """desc, aabb_scale, params (uint16 fp16 bits), density_grid (float32 [5*128^3]), camera (12 floats or None)"""
+    """desc, aabb_scale, params (uint16 fp16 bits), density_grid (float32 [5*128^3]), camera (12 floats or None), n_extra_dims (0, or 3: light directions)"""
 
 
-def load_snapshot(path):
+def load_snapshot(path, allow_light_dirs=False):
+    """allow_light_dirs: read a snapshot trained with light directions (nrs_snapshot_open_ex with NRS_SNAPSHOT_ALLOW_LIGHT_DIRS) instead of refusing it."""
     lib = _abi.load()
     h = C.c_void_p()
-    check(lib.nrs_snapshot_open(str(path).encode(), C.byref(h)))
+    if allow_light_dirs:
+        check(lib.nrs_snapshot_open_ex(str(path).encode(), _abi.SNAPSHOT_ALLOW_LIGHT_DIRS, C.byref(h)))
+    else:
+        check(lib.nrs_snapshot_open(str(path).encode(), C.byref(h)))
     try:
         s = Snapshot()
+        s.n_extra_dims = int(lib.nrs_snapshot_n_extra_dims(h))
         s.desc = ModelDesc()
         scale = C.c_uint32()
         check(lib.nrs_snapshot_model_desc(h, C.byref(s.desc), C.byref(scale)))
@@ -63,10 +68,12 @@ def network_config(desc, explicit_per_level_scale=False):
     return cfg
 
 
-def save_snapshot(path, desc, aabb_scale, params_u16, density_grid, camera=None, exported=None, training_step=35000):
+def save_snapshot(path, desc, aabb_scale, params_u16, density_grid, camera=None, exported=None, training_step=35000, has_light_dirs=False):
     """Write the reference's snapshot schema.  exported=False: Testbed::save_snapshot (float grid, aabb_scale inside the
     dataset object); exported=True: Testbed::export_snapshot (fp16 grid of the used cascades, snapshot.nerf.aabb_scale);
-    default: exported iff the path ends in .ingp.  `.ingp` files are zlib-compressed (zstr)."""
+    default: exported iff the path ends in .ingp.  `.ingp` files are zlib-compressed (zstr).
+    has_light_dirs: params_u16 is the blob of a network trained with light directions (synth.make_light_params); the flag is also written into the dataset
+    object of a saved (not exported) snapshot -- the reference stores neither, a reader recognises such a file by the blob's size."""
     import msgpack
     path = str(path)
     if exported is None:
@@ -87,6 +94,8 @@ def save_snapshot(path, desc, aabb_scale, params_u16, density_grid, camera=None,
     else:
         snap["density_grid_binary"] = grid.tobytes()
         snap["nerf"] = {"rgb": rgb, "dataset": {"aabb_scale": int(aabb_scale), "scale": 0.33, "offset": [0.5, 0.5, 0.5], "n_images": 0}}
+        if has_light_dirs:
+            snap["nerf"]["dataset"]["has_light_dirs"] = True
     if camera is not None:
         cam = np.asarray(camera, np.float32).reshape(4, 3).T  # column-major 3x4 -> rows (Eigen's to_json, json_binding.h:30-43)
         snap["camera"] = {"matrix": [[float(v) for v in row] for row in cam], "fov_axis": 1, "zoom": 1.0, "scale": 1.0}

@@ -87,12 +87,16 @@ DEFAULT_CELL_CACHE_BYTES = 10 << 30  # levels 0..11 of base.json's table (9.2 GB
 class NerfNetwork:
     """pos-encoding (HashGrid) -> density MLP -> (SH dir-encoding | density features) -> RGB MLP -> extract_density."""
 
-    def __init__(self, ctx, desc, cell_cache_bytes=DEFAULT_CELL_CACHE_BYTES):
+    def __init__(self, ctx, desc, cell_cache_bytes=DEFAULT_CELL_CACHE_BYTES, n_extra_dims=0):
         """cell_cache_bytes: budget of the cell-record cache this HARNESS opts into (nrs_model_set_cell_cache: opt-in at the C-ABI since round 6; never more than a
-        quarter of the free HBM); 0 = none."""
+        quarter of the free HBM); 0 = none.  n_extra_dims: 0, or 3 for a network trained with light directions (nrs_model_create_ex)."""
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
         self.h = C.c_void_p()
-        check(self.lib.nrs_model_create(ctx.h, C.byref(desc), C.byref(self.h)))
+        self._n_extra_dims = int(n_extra_dims)
+        if self._n_extra_dims:
+            check(self.lib.nrs_model_create_ex(ctx.h, C.byref(desc), self._n_extra_dims, C.byref(self.h)))
+        else:
+            check(self.lib.nrs_model_create(ctx.h, C.byref(desc), C.byref(self.h)))
         if cell_cache_bytes and "NRS_CELL_CACHE_GB" not in os.environ:
             free_b = torch.cuda.mem_get_info(ctx.device)[0]
             try:
@@ -108,10 +112,14 @@ class NerfNetwork:
         return 7
 
     def n_extra_dims(self):
-        return 0
+        return int(self.lib.nrs_model_n_extra_dims(self.h))
 
     def n_params(self):
-        return int(self.lib.nrs_model_n_params(C.byref(self.desc)))
+        return int(self.lib.nrs_model_n_params_ex(C.byref(self.desc), self._n_extra_dims))
+
+    def set_light_dir(self, light_dir):
+        """m_nerf.light_dir (nrs_model_set_light_dir): normalised at use; what every sample gets that brings no light direction of its own."""
+        check(self.lib.nrs_model_set_light_dir(self.h, C.byref((C.c_float * 3)(*[float(v) for v in light_dir]))))
 
     def set_params(self, params_fp16):
         """fp16 parameter blob in tiny-cuda-nn order (density | rgb | grid), a host array (numpy uint16/float16)."""
@@ -195,6 +203,17 @@ class NerfNetwork:
         n = input.shape[0]
         layout, ld = self._out_layout(output, n)
         check(self.lib.nrs_network_inference(self.h, _stream_handle(stream), n, input.data_ptr(), output.data_ptr(), ld, layout))
+
+    def inference_strided(self, stream, input, output):
+        """inference_mixed_precision on [n, ld >= 7] f32 records (nrs_network_inference_strided): with ld >= 10 on a network with light directions, floats 7..9 of
+        a record are that sample's already-warped light direction; otherwise the model's light direction is used."""
+        _require_cuda(input, torch.float32, "input")
+        _require_cuda(output, torch.float16, "output")
+        if input.dim() != 2 or input.shape[1] < 7 or not input.is_contiguous():
+            raise NrsError("inference_strided input must be a contiguous [n, >= 7] tensor")
+        n = input.shape[0]
+        layout, ld = self._out_layout(output, n)
+        check(self.lib.nrs_network_inference_strided(self.h, _stream_handle(stream), n, input.data_ptr(), input.shape[1], output.data_ptr(), ld, layout))
 
     def density(self, stream, input, output):
         """input: [n, ld] f32 with ld in 3..7 (only the position is read); output as above, the density MLP's 16 outputs."""
@@ -433,9 +452,9 @@ def set_camera_extras(p, render_distortion=None, distortion_map=None, envmap=Non
 class Testbed:
     """The slice of ngp::Testbed the render path reads: network, occupancy, edit operators and the render knobs."""
 
-    def __init__(self, ctx, desc, aabb_scale=1):
+    def __init__(self, ctx, desc, aabb_scale=1, n_extra_dims=0):
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
-        self.nerf_network = NerfNetwork(ctx, desc)
+        self.nerf_network = NerfNetwork(ctx, desc, n_extra_dims=n_extra_dims)
         self.edit_operators = []          # NerfTracer::m_edit_operators, applied last-to-first
         self.enable_edits = True          # m_enable_edits
         self.snap_to_pixel_centers = True

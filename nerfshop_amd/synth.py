@@ -208,6 +208,25 @@ def make_params(desc, seed=SEED, sigma_raw=None, density_noise=0.25, shaped=Fals
     return blob.view(np.uint16)
 
 
+def add_light_columns(desc, params_u16, light_cols):
+    """The blob of the network trained with light directions (n_extra_dims = 3) that extends the plain network `params_u16`: the first rgb matrix [64 x 32]
+    becomes [64 x 48], its columns 32..47 = light_cols [64, 16] (3 light components | 13 padding columns, which see the constant 1: a learned bias)."""
+    if desc.sh_degree == 0 or desc.rgb_hidden_layers == 0:
+        raise ValueError("light directions need the SH direction encoding and an rgb network with hidden layers")
+    p = np.ascontiguousarray(params_u16, np.uint16)
+    cols = np.asarray(light_cols, np.float16).reshape(64, 16).view(np.uint16)
+    o = 16 * 32 if desc.density_hidden_layers == 0 else 64 * 32 + 16 * 64
+    w1 = np.concatenate([p[o: o + 64 * 32].reshape(64, 32), cols], axis=1)
+    return np.concatenate([p[:o], w1.ravel(), p[o + 64 * 32:]])
+
+
+def make_light_params(desc, seed=SEED, light_seed=7, **kw):
+    """make_params' network with 16 more Xavier-uniform columns ([64 x 48]) in the first rgb matrix: a network trained with light directions."""
+    rng = np.random.Generator(np.random.PCG64(light_seed))
+    lim = math.sqrt(6.0 / (48 + 64))
+    return add_light_columns(desc, make_params(desc, seed=seed, **kw), rng.uniform(-lim, lim, size=(64, 16)).astype(np.float32))
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # Occupancy: a lego-like solid (union of bricks + studs); NGP space, y is up (nerf_matrix_to_ngp cycles the axes)
 # ----------------------------------------------------------------------------------------------------------------
