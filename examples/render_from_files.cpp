@@ -5,12 +5,17 @@
 //   Testbed::load_edits               src/testbed.cu:3205   -> nrs_edits_open + CageDeformation / AffineDuplication
 //   Testbed::render_nerf              src/testbed_nerf.cu:3066 -> nrs::compat::Testbed::render_nerf
 //
-//   usage: render_from_files <snapshot> <edits.json | -> <width> <height> <camera_angle_x radians> <out.raw> [<light x> <light y> <light z>]
+//   CudaRenderBuffer::accumulate / tonemap  src/render_buffer.cu:540 / :562 -> nrs::compat::RenderBuffer::accumulate / tonemap   (with --pam only)
+//
+//   usage: render_from_files [--pam <out.pam>] <snapshot> <edits.json | -> <width> <height> <camera_angle_x radians> <out.raw> [<light x> <light y> <light z>]
 //
 // A snapshot trained with light directions is opened too (NRS_SNAPSHOT_ALLOW_LIGHT_DIRS); the optional light direction is Testbed::m_nerf.light_dir.
 //
 // out.raw = float32 RGBA [H][W][4] followed by float32 depth [H][W].  Device memory comes straight from the HIP runtime (hipMalloc); the library takes the
 // pointers as they are.  tests/test_gpu_cpp_host.py builds this file, runs it on the GPU and compares out.raw bit for bit with the Python host's frame.
+//
+// --pam <out.pam>: the display step as well -- the frame joins an accumulate buffer (1 spp), is tonemapped to 8 bits (Identity curve, exposure 0, transparent background,
+// sRGB output: render_frame's tail, src/testbed.cu:2761-2762), copied back (4 bytes per pixel instead of 16) and written as a binary PAM, TUPLTYPE RGB_ALPHA.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -52,8 +57,16 @@ struct DeviceBuffer {
 };
 
 int run(int argc, char** argv) {
+	const char* pam_path = nullptr;
+	std::vector<char*> args; // argv without "--pam <file>"
+	for (int i = 0; i < argc; ++i) {
+		if (i > 0 && std::strcmp(argv[i], "--pam") == 0 && i + 1 < argc) pam_path = argv[++i];
+		else args.push_back(argv[i]);
+	}
+	argc = (int)args.size();
+	argv = args.data();
 	if (argc != 7 && argc != 10) {
-		std::fprintf(stderr, "usage: %s <snapshot.ingp|.msgpack> <edits.json|-> <width> <height> <camera_angle_x> <out.raw> [<light x> <light y> <light z>]\n", argv[0]);
+		std::fprintf(stderr, "usage: %s [--pam <out.pam>] <snapshot.ingp|.msgpack> <edits.json|-> <width> <height> <camera_angle_x> <out.raw> [<light x> <light y> <light z>]\n", argv[0]);
 		return 2;
 	}
 	const int width = std::atoi(argv[3]), height = std::atoi(argv[4]);
@@ -130,6 +143,22 @@ int run(int argc, char** argv) {
 	FILE* f = std::fopen(argv[6], "wb");
 	if (!f || std::fwrite(host.data(), sizeof(float), host.size(), f) != host.size()) throw std::runtime_error(std::string("cannot write ") + argv[6]);
 	std::fclose(f);
+
+	// ---- accumulate + tonemap to 8 bits, and the PAM
+	if (pam_path) {
+		DeviceBuffer accumulate(n_pixels * 4 * sizeof(float)), rgba8(nrs_tonemap_output_bytes((uint32_t)width, (uint32_t)height, NRS_TONEMAP_RGBA8));
+		buffer.accumulate_buffer = (float*)accumulate.p;
+		buffer.accumulate(ctx, nullptr);
+		const float background[4] = {0.f, 0.f, 0.f, 0.f};
+		buffer.tonemap(ctx, 0.f, background, NRS_COLOR_SRGB, nullptr, rgba8.p, NRS_TONEMAP_RGBA8);
+		std::vector<unsigned char> bytes(rgba8.bytes);
+		hip_check(hipMemcpy(bytes.data(), rgba8.p, rgba8.bytes, hipMemcpyDeviceToHost), "hipMemcpy(rgba8)");
+		FILE* pam = std::fopen(pam_path, "wb");
+		if (!pam) throw std::runtime_error(std::string("cannot write ") + pam_path);
+		std::fprintf(pam, "P7\nWIDTH %d\nHEIGHT %d\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n", width, height);
+		const bool ok = std::fwrite(bytes.data(), 1, bytes.size(), pam) == bytes.size();
+		if (std::fclose(pam) != 0 || !ok) throw std::runtime_error(std::string("cannot write ") + pam_path);
+	}
 	std::printf("{\"width\": %d, \"height\": %d, \"operators\": %zu, \"n_samples\": %llu, \"n_rays_alive\": %u, \"n_rays_hit\": %u}\n", width, height,
 	            operators.size(), (unsigned long long)stats.n_samples, stats.n_rays_alive, stats.n_rays_hit);
 	return 0;

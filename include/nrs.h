@@ -30,6 +30,7 @@
  *   nrs_tet_local_rotations  <- TetMesh::update_local_rotations                    tet_mesh.cu:37           (host, "next" row f1)
  *   nrs_trace_samples        <- (test hook) the (t, dt) stream generate_next_nerf_network_inputs emits, testbed_nerf.cu:637
  *   nrs_accumulate           <- CudaRenderBuffer::accumulate / accumulate_kernel                                   src/render_buffer.cu:540 / :217
+ *   nrs_tonemap              <- CudaRenderBuffer::tonemap / tonemap_kernel                                         src/render_buffer.cu:562 / :471
  *   nrs_detile               <- (new) inverse of the multi-GPU tile packing, no reference counterpart
  *
  * Conventions: every function returns NRS_OK (0) or a negative nrs_status; nrs_last_error() returns a
@@ -606,6 +607,45 @@ int    nrs_network_inference_strided(nrs_model* model, void* stream, uint32_t n,
 #define NRS_SNAPSHOT_ALLOW_LIGHT_DIRS 1u
 int      nrs_snapshot_open_ex(const char* path, uint32_t flags, nrs_snapshot** out);
 uint32_t nrs_snapshot_n_extra_dims(const nrs_snapshot* snapshot);
+
+/* ---- tonemap: the display step after accumulate, with 8-bit output ------------------------------------------------------------------------- */
+/* Testbed::render_frame ends in render_buffer.accumulate(...) and render_buffer.tonemap(m_exposure, m_background_color, to_srgb ? SRGB : Linear, stream)
+ * (src/testbed.cu:2761-2762); render_to_cpu hands back the tonemapped surface (src/python_api.cu:129-175).  Callers detect these entry points by symbol (dlsym);
+ * NRS_ABI_VERSION is unchanged because no existing layout changes.
+ *
+ * nrs_tonemap <- CudaRenderBuffer::tonemap (src/render_buffer.cu:562-580; tonemap_kernel :471-501, tonemap and its curves :254-332, linear_to_srgb / srgb_to_linear
+ * common_device.cuh:31-61, EColorSpace / ETonemapCurve common.h:122-135).  Per pixel of d_accumulate [H*W] f32x4, in the reference's operation order:
+ *   background: rgb of background_color through srgb_to_linear unless color_space is SRGB; weight = (1 - a) * bg.a; rgb += bg.rgb * weight; a += weight;
+ *   srgb_to_linear if color_space is SRGB;  rgb *= 2^exposure;  the curve (Identity returns x untouched, the others start from max(x, 0));
+ *   linear_to_srgb if output_color_space is SRGB;  all four channels clamped to [0, 1] if clamp_output.
+ * Plain fp32 (bit-reproducible) except the powf of the two sRGB curves.  d_out [H*W]:
+ *   NRS_TONEMAP_RGBA32F  f32x4 per pixel, the reference's surface / lopi content.  d_out may be d_accumulate itself (in place).
+ *   NRS_TONEMAP_RGBA8    one packed dword per pixel, bytes R, G, B, A in memory, each (uint32_t)(min(max(c, 0), 1) * 255 + 0.5f): the clamp is implied.  Must not alias d_accumulate.
+ * nrs_tonemap_output_bytes: the size of d_out (16 or 4 bytes per pixel; 0 for an unknown format).
+ *
+ * nrs_accumulate_spp_tonemap: nrs_accumulate_spp (color_space taken from the params) followed by nrs_tonemap of the result, in one pass: the K slabs are read, d_accumulate
+ * is read once and written once, d_out is written once.  d_accumulate and d_out are bit-equal to what the two calls leave.  d_out must alias neither d_frames nor d_accumulate.
+ *
+ * NRS_ERR_INVALID_ARG before any device is touched, with the argument named in the message: a NULL ctx, buffer or params; struct_size smaller than the struct;
+ * width or height 0; color_space > 2; output_color_space > 1; tonemap_curve > 3; clamp_output > 1; an unknown output_format; a non-finite exposure; and, for the fused
+ * call, everything nrs_accumulate_spp refuses. */
+typedef enum nrs_tonemap_curve { NRS_TONEMAP_IDENTITY = 0, NRS_TONEMAP_ACES = 1, NRS_TONEMAP_HABLE = 2, NRS_TONEMAP_REINHARD = 3 } nrs_tonemap_curve;
+#define NRS_TONEMAP_RGBA32F 0u
+#define NRS_TONEMAP_RGBA8 1u
+typedef struct nrs_tonemap_params {
+	uint32_t struct_size;           /* sizeof(nrs_tonemap_params) */
+	float    exposure;              /* m_exposure: the colour is scaled by 2^exposure */
+	float    background_color[4];   /* sRGB-encoded, as m_background_color */
+	uint32_t color_space;           /* of the accumulate buffer: 0 Linear, 1 SRGB, 2 VisPosNeg (treated as linear) */
+	uint32_t output_color_space;    /* 0 Linear, 1 SRGB */
+	uint32_t tonemap_curve;         /* 0 Identity, 1 ACES, 2 Hable, 3 Reinhard */
+	uint32_t clamp_output;          /* 0 / 1 */
+	uint32_t output_format;         /* NRS_TONEMAP_RGBA32F, NRS_TONEMAP_RGBA8 */
+} nrs_tonemap_params;
+int nrs_tonemap(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_accumulate, const nrs_tonemap_params* params, void* d_out);
+int nrs_accumulate_spp_tonemap(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count,
+                               float* d_accumulate, uint32_t sample_count, const nrs_tonemap_params* params, void* d_out);
+size_t nrs_tonemap_output_bytes(uint32_t width, uint32_t height, uint32_t output_format);
 
 #ifdef __cplusplus
 }

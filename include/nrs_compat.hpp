@@ -167,6 +167,32 @@ struct RenderBuffer {
 		check(nrs_accumulate(ctx.get(), stream, (uint32_t)width, (uint32_t)height, frame_buffer, accumulate_buffer, spp, (uint32_t)color_space), "nrs_accumulate");
 		++spp;
 	}
+	// m_color_space / m_tonemap_curve and their setters (render_buffer.h:226-238): a change resets the accumulation, as there
+	nrs_color_space color_space = NRS_COLOR_LINEAR;
+	nrs_tonemap_curve tonemap_curve = NRS_TONEMAP_IDENTITY;
+	void set_color_space(nrs_color_space v) {
+		if (v != color_space) { color_space = v; spp = 0; }
+	}
+	void set_tonemap_curve(nrs_tonemap_curve v) {
+		if (v != tonemap_curve) { tonemap_curve = v; spp = 0; }
+	}
+	// void CudaRenderBuffer::tonemap(float exposure, const Array4f& background_color, EColorSpace output_color_space, cudaStream_t stream, Vector4f* lopi) -- render_buffer.h:205,
+	// render_buffer.cu:562-580.  The reference writes its surface (and lopi); here the caller names the output: d_out [H*W] f32x4 (NRS_TONEMAP_RGBA32F; may be the accumulate
+	// buffer itself) or one R, G, B, A dword per pixel (NRS_TONEMAP_RGBA8).  Reads the accumulate buffer in m_color_space.
+	void tonemap(Context& ctx, float exposure, const float background_color[4], nrs_color_space output_color_space, void* stream, void* d_out,
+	             uint32_t output_format = NRS_TONEMAP_RGBA32F, bool clamp_output_color = false) {
+		if (!accumulate_buffer) throw std::runtime_error("RenderBuffer::tonemap: no accumulate buffer");
+		nrs_tonemap_params t{};
+		t.struct_size = (uint32_t)sizeof(nrs_tonemap_params);
+		t.exposure = exposure;
+		for (int i = 0; i < 4; ++i) t.background_color[i] = background_color[i];
+		t.color_space = (uint32_t)color_space;
+		t.output_color_space = (uint32_t)output_color_space;
+		t.tonemap_curve = (uint32_t)tonemap_curve;
+		t.clamp_output = clamp_output_color ? 1u : 0u;
+		t.output_format = output_format;
+		check(nrs_tonemap(ctx.get(), stream, (uint32_t)width, (uint32_t)height, accumulate_buffer, &t, d_out), "nrs_tonemap");
+	}
 };
 
 // The slice of ngp::Testbed that render_nerf reads (SURVEY 8b "implicit inputs"), with the reference's member names.

@@ -138,6 +138,24 @@ class GridUpdate(C.Structure):
     ]
 
 
+class TonemapParams(C.Structure):
+    """nrs_tonemap_params; struct_size is filled in on construction."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("exposure", C.c_float),
+        ("background_color", C.c_float * 4),
+        ("color_space", C.c_uint32),
+        ("output_color_space", C.c_uint32),
+        ("tonemap_curve", C.c_uint32),
+        ("clamp_output", C.c_uint32),
+        ("output_format", C.c_uint32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(TonemapParams)
+
+
 # every symbol include/nrs.h declares; tests check the library exports exactly these
 EXPORTS = [
     "nrs_last_error", "nrs_abi_version", "nrs_edit_poisson_interpolate", "nrs_edit_download_poisson", "nrs_comm_unique_id", "nrs_comm_create", "nrs_comm_info", "nrs_comm_destroy", "nrs_gather_tiles", "nrs_comm_probe_self_p2p",
@@ -158,9 +176,13 @@ EXPORTS = [
     "nrs_render_nerf_spp", "nrs_accumulate_spp", "nrs_ctx_render_launches",
     "nrs_model_create_ex", "nrs_model_n_params_ex", "nrs_model_n_extra_dims", "nrs_model_set_light_dir", "nrs_network_inference_strided",
     "nrs_snapshot_open_ex", "nrs_snapshot_n_extra_dims",
+    "nrs_tonemap", "nrs_accumulate_spp_tonemap", "nrs_tonemap_output_bytes",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
+COLOR_LINEAR, COLOR_SRGB, COLOR_VISPOSNEG = 0, 1, 2  # nrs_color_space
+TONEMAP_IDENTITY, TONEMAP_ACES, TONEMAP_HABLE, TONEMAP_REINHARD = 0, 1, 2, 3  # nrs_tonemap_curve
+TONEMAP_RGBA32F, TONEMAP_RGBA8 = 0, 1  # NRS_TONEMAP_RGBA32F / _RGBA8
 
 _lib = None
 
@@ -275,6 +297,12 @@ def load():
         lib.nrs_snapshot_open_ex.argtypes = [C.c_char_p, U32, C.POINTER(P)]
         lib.nrs_snapshot_n_extra_dims.argtypes = [P]
         lib.nrs_snapshot_n_extra_dims.restype = U32
+    # the display step after accumulate (appended exports, detected by symbol like the spp batch)
+    if hasattr(lib, "nrs_tonemap"):
+        lib.nrs_tonemap.argtypes = [P, P, U32, U32, P, C.POINTER(TonemapParams), P]
+        lib.nrs_accumulate_spp_tonemap.argtypes = [P, P, U32, U32, P, C.c_size_t, U32, P, U32, C.POINTER(TonemapParams), P]
+        lib.nrs_tonemap_output_bytes.argtypes = [U32, U32, U32]
+        lib.nrs_tonemap_output_bytes.restype = C.c_size_t
     lib.nrs_snapshot_open.argtypes = [C.c_char_p, C.POINTER(P)]
     lib.nrs_snapshot_close.argtypes = [P]
     lib.nrs_snapshot_close.restype = None

@@ -427,6 +427,67 @@ class RenderBuffer:
         self._spp += k
         return self._accumulate
 
+    def set_color_space(self, color_space):
+        """CudaRenderBuffer::set_color_space (render_buffer.h:233): the EColorSpace of the accumulate buffer, read by tonemap() and accumulate_spp_tonemap()."""
+        if int(color_space) != getattr(self, "_color_space", 0):   # (a change resets the accumulation, as there)
+            self._color_space = int(color_space)
+            self._spp = 0
+
+    def set_tonemap_curve(self, curve):
+        """CudaRenderBuffer::set_tonemap_curve (render_buffer.h:233): ETonemapCurve, 0 Identity, 1 ACES, 2 Hable, 3 Reinhard."""
+        if int(curve) != getattr(self, "_tonemap_curve", 0):
+            self._tonemap_curve = int(curve)
+            self._spp = 0
+
+    _TONEMAP_FORMATS = {"rgba32f": _abi.TONEMAP_RGBA32F, "rgba8": _abi.TONEMAP_RGBA8}
+
+    def _tonemap_params(self, exposure, background, output_color_space, fmt, clamp_output):
+        if fmt not in self._TONEMAP_FORMATS:
+            raise ValueError(f"fmt is 'rgba32f' or 'rgba8', got {fmt!r}")
+        t = _abi.TonemapParams()
+        t.exposure = float(exposure)
+        t.background_color[:] = [float(v) for v in background]
+        t.color_space = getattr(self, "_color_space", 0)
+        t.output_color_space = int(output_color_space)
+        t.tonemap_curve = getattr(self, "_tonemap_curve", 0)
+        t.clamp_output = 1 if clamp_output else 0
+        t.output_format = self._TONEMAP_FORMATS[fmt]
+        return t
+
+    def _tonemap_output(self, fmt):
+        if fmt == "rgba8":
+            return torch.empty((self.height, self.width, 4), dtype=torch.uint8, device=self._frame.device)
+        return torch.empty((self.height, self.width, 4), dtype=torch.float32, device=self._frame.device)
+
+    def tonemap(self, ctx, exposure=0.0, background=(0.0, 0.0, 0.0, 0.0), output_color_space=1, fmt="rgba32f", stream=None, clamp_output=False):
+        """CudaRenderBuffer::tonemap(exposure, background_color, output_color_space, stream) (render_buffer.cu:562) of the accumulate buffer: background, exposure, the
+        curve of set_tonemap_curve, the output's colour space.  Returns a new tensor [H, W, 4]: float32 for fmt "rgba32f", uint8 (R, G, B, A; clamped) for "rgba8"."""
+        if getattr(self, "_accumulate", None) is None:
+            raise NrsError("RenderBuffer.tonemap: nothing has been accumulated")
+        t = self._tonemap_params(exposure, background, output_color_space, fmt, clamp_output)
+        out = self._tonemap_output(fmt)
+        check(_abi.load().nrs_tonemap(ctx.h, _stream_handle(stream), self.width, self.height, self._accumulate.data_ptr(), C.byref(t), out.data_ptr()))
+        return out
+
+    def accumulate_spp_tonemap(self, ctx, frames, exposure=0.0, background=(0.0, 0.0, 0.0, 0.0), output_color_space=1, fmt="rgba32f", stream=None, clamp_output=False):
+        """accumulate_spp(ctx, frames, color_space of set_color_space) followed by tonemap(...), in one pass over the accumulate buffer (nrs_accumulate_spp_tonemap):
+        bit-equal to the pair.  spp() advances by K; returns the output tensor as tonemap() does."""
+        _require_cuda(frames, torch.float32, "frames")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (self.height, self.width, 4):
+            raise ValueError(f"frames must be [K, {self.height}, {self.width}, 4], got {tuple(frames.shape)}")
+        if getattr(self, "_accumulate", None) is None:
+            self._accumulate = torch.zeros_like(self._frame)
+        t = self._tonemap_params(exposure, background, output_color_space, fmt, clamp_output)
+        out = self._tonemap_output(fmt)
+        k = int(frames.shape[0])
+        check(_abi.load().nrs_accumulate_spp_tonemap(ctx.h, _stream_handle(stream), self.width, self.height, frames.data_ptr(), self.width * self.height, k,
+                                                     self._accumulate.data_ptr(), int(self._spp), C.byref(t), out.data_ptr()))
+        self._spp += k
+        return out
+
+    def accumulate_buffer(self):
+        return getattr(self, "_accumulate", None)
+
     def clear_frame(self, stream=None):
         self._frame.zero_()
         self._depth.zero_()
@@ -548,6 +609,40 @@ class Testbed:
                                            C.byref(stats) if stats is not None else None))
         self.last_stats = stats
         return stats
+
+    def render_to_cpu(self, network, width, height, spp, linear, focal_length, camera_matrix0, camera_matrix1=None, rolling_shutter=(0.0, 0.0, 0.0, 0.0),
+                      screen_center=(0.5, 0.5), exposure=0.0, background=(0.0, 0.0, 0.0, 0.0), fmt="rgba32f", tonemap_curve=0, color_space=0, apply_operators=True,
+                      stream=None):
+        """Testbed::render_to_cpu(width, height, spp, linear, ...) (src/python_api.cu:129-175) for a still camera (its camera-path smoothing is out of scope): the
+        accumulation is reset, `spp` samples of the view are rendered in batches of at most NRS_SPP_BATCH_MAX (one launch each) and folded into the running mean, and
+        the last fold is fused with the display step (tonemap: `background`, `exposure`, `tonemap_curve`; sRGB output unless `linear`).  Returns a host array [H, W, 4]:
+        float32 for fmt "rgba32f", uint8 for "rgba8".  The accumulate buffer stays readable as render_to_cpu_buffer().accumulate_buffer()."""
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("spp must be at least 1")
+        buf = getattr(self, "_windowless", None)
+        if buf is None or buf.in_resolution() != (int(width), int(height)):
+            buf = self._windowless = RenderBuffer(width, height, device=f"cuda:{self.ctx.device}")   # m_windowless_render_surface.resize
+        buf.set_spp(0)                                                                                # reset_accumulation
+        buf.set_color_space(color_space)
+        buf.set_tonemap_curve(tonemap_curve)
+        cam1 = camera_matrix0 if camera_matrix1 is None else camera_matrix1
+        done, out = 0, None
+        while done < spp:
+            k = min(spp - done, _abi.SPP_BATCH_MAX)
+            frames = self.render_nerf_spp(network, buf, k, focal_length, camera_matrix0, cam1, rolling_shutter, screen_center, apply_operators, stream)[0]
+            if done + k < spp:
+                buf.accumulate_spp(self.ctx, frames, stream, color_space)
+            else:
+                out = buf.accumulate_spp_tonemap(self.ctx, frames, exposure, background, 0 if linear else 1, fmt, stream)
+            done += k
+        if stream is not None:
+            (stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream))).synchronize()
+        return out.cpu().numpy()
+
+    def render_to_cpu_buffer(self):
+        """The RenderBuffer render_to_cpu renders into (m_windowless_render_surface); None before the first call."""
+        return getattr(self, "_windowless", None)
 
     def get_density_on_grid(self, res3d, aabb_min, aabb_max, mask_with_density_grid=True, stream=None):
         """Testbed::get_density_on_grid(res3d, aabb) (testbed_nerf.cu:4538) -> float32 CUDA tensor [rz, ry, rx]"""
