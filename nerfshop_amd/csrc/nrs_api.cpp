@@ -1543,9 +1543,9 @@ uint32_t nrs_render_owned_tiles(const nrs_render_params* p) {
 	return owned;
 }
 
-// nrs_render_nerf and nrs_render_nerf_spp: spp_count samples of the view into slabs slab_stride pixels apart (a single frame: 1, 0)
-static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frame, float* d_depth,
-                          uint32_t* d_steps, size_t slab_stride, void* stream, nrs_render_stats* h_stats) {
+// ---- nrs_render_nerf and nrs_render_nerf_spp: spp_count samples of the view into slabs slab_stride pixels apart (a single frame: 1, 0) -----------------
+static int check_render_args(const nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, const float* d_frame,
+                             const float* d_depth, size_t slab_stride) {
 	if (!m || !p || !d_frame || !d_depth) return fail(NRS_ERR_INVALID_ARG, spp_count > 1u ? "nrs_render_nerf_spp: NULL argument (model, params, d_frames, d_depths)" : "nrs_render_nerf: NULL argument");
 	if (!m->have_params) return fail(NRS_ERR_STATE, "nrs_render_nerf: parameters not set (nrs_model_set_params)");
 	if (!m->have_bitfield) return fail(NRS_ERR_STATE, "nrs_render_nerf: occupancy not set (nrs_model_set_density_bitfield/_grid)");
@@ -1581,291 +1581,261 @@ static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* co
 		if ((uint64_t)np * 4ull * spp_count > (1ull << 30) || (uint64_t)np * 64ull * spp_count > (1ull << 30))
 			return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count times the packets / pixels of one sample overflows the 32-bit packet counter (limit 2^30)");
 	}
-	nrs_ctx* ctx = m->ctx;
-	HIP_TRY(hipSetDevice(ctx->device));
-	hipStream_t s = (hipStream_t)stream;
-	std::unique_lock<std::mutex> launch_lock(ctx->launch_mutex); // held until the launch is enqueued and the slot's book-keeping is written (released before the statistics' sync)
-	const uint32_t slot = ctx->launch_serial.fetch_add(1u) % (uint32_t)nrs_ctx::kInFlight;
-	if (ctx->slot_used[slot] && ctx->slot_stream[slot] != s) HIP_TRY(hipStreamWaitEvent(s, ctx->slot_done[slot], 0));
-	// The statistics / queue block of this launch.  A slot owns two: the render kernel's last workgroup zeroes the one it did NOT use, which the slot's next
-	// launch takes (launches of a slot are ordered: same stream, or the event wait above) -- so a frame costs no memset (two 5-us fill kernels per frame in
-	// the round-3 timeline: 2 % of a 1/8 share-frame).  The Slice path and a launch after a failed one still clear their block the plain way.
-	RenderCounters* d_counters_slot = ctx->d_counters + 2 * slot + ctx->counter_parity[slot];
-	RenderCounters* d_counters_other = ctx->d_counters + 2 * slot + (ctx->counter_parity[slot] ^ 1u);
-	DeviceEdit* d_edits_slot = ctx->d_edits + (size_t)slot * nrs_ctx::kMaxEdits;
+	return NRS_OK;
+}
 
-	RenderArgs a{};
-	a.p = *p;
-	if (p->render_mode == NRS_RENDER_ENCODING_VIS) a.p.visualized_layer = kernel_layer(m->desc, p->visualized_layer); // (the kernels number base.json's layers)
-	uint32_t owned_tiles = 0;
-	a.team = 1;
-	a.fill_lanes = 4;
-	int st = tile_geometry(*p, 1, a.tiles_x, owned_tiles, a.n_packets, a.packets_per_tile_x);
-	if (st != NRS_OK) return st;
-	a.n_edits = n_edits;
-	a.any_poisson = 0;
-	if (n_edits > 0) {
-		DeviceEdit host_edits[nrs_ctx::kMaxEdits];
-		for (int i = 0; i < n_edits; ++i) {
-			if (!edits[i]) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: NULL edit operator");
-			if (edits[i]->fine_stale && ++edits[i]->renders_since_move >= 2u) { // the cage has come to rest: its fine look-up table (nrs_edit::fine_stale)
-				edits[i]->fine_stale = false;
-				NRS_TRY(build_fine_lut(edits[i], s));
-			}
-			host_edits[i] = edits[i]->de;
-			a.any_poisson |= edits[i]->de.apply_poisson;
-			a.any_affine |= (edits[i]->de.kind == kEditAffine) ? 1u : 0u;
+// The development knobs of a render call, read once (dev_knob: a production process ignores them).
+struct RenderKnobs {
+	RouteKnobs route;
+	uint32_t dbg;      // RenderArgs::dbg: NRS_DEBUG | NRS_SKIP_PAIRS << 8 (bit it: level pair (2 it, 2 it + 1) is not gathered -- nrs_mlp.cuh: KIND_SKIP; measurement only)
+	uint32_t reteam;   // NRS_RETEAM bit 0: at the end of a wave's work, bit 1: whenever a tail generation has thinned out
+	uint32_t steal;    // NRS_STEAL
+	bool log_teams;    // NRS_TEAM_LOG
+};
+static const RenderKnobs& render_knobs() {
+	static const RenderKnobs knobs = []() {
+		RenderKnobs k{};
+		auto num = [](const char* name, int unset) { const char* e = dev_knob(name); return e ? atoi(e) : unset; };
+		const char* sk = dev_knob("NRS_SKIP_PAIRS");
+		k.dbg = ((uint32_t)num("NRS_DEBUG", 0) & 0xffu) | (sk ? ((uint32_t)strtoul(sk, nullptr, 0) & 0xffu) << 8 : 0u);
+		k.reteam = (uint32_t)num("NRS_RETEAM", 3);
+		k.steal = (uint32_t)num("NRS_STEAL", 1);
+		k.log_teams = dev_knob("NRS_TEAM_LOG") != nullptr;
+		k.route.team = num("NRS_TEAM", 0);
+		k.route.hybrid_on = num("NRS_HYBRID", 1) != 0;
+		k.route.render_cfg = num("NRS_RENDER_CFG", 0);
+		k.route.render_cfg_set = dev_knob("NRS_RENDER_CFG") != nullptr;
+		k.route.debug = k.dbg & 0xffu;
+		k.route.l2_gate = num("NRS_L2_GATE", 1) != 0;
+		// (<= kRing - 64: the fill adds up to 64 rays per packet to a 128-entry ring) 8 / 16 / 24 / 32 / 48: 8.92 / 8.91 / 9.11 / 9.01 / 8.47 Gsamples/s
+		k.route.tail_target = num("NRS_TAIL_TARGET", 0) >= 1 ? (uint32_t)std::min(num("NRS_TAIL_TARGET", 0), 64) : 24u;
+		k.route.alltail_target = num("NRS_ALLTAIL_TARGET", 0) >= 1 ? (uint32_t)std::min(num("NRS_ALLTAIL_TARGET", 0), 64) : 16u; // (<= kRing - 64, as above)
+		k.route.tail_every = num("NRS_TAIL_EVERY", 0) >= 2 ? (uint32_t)num("NRS_TAIL_EVERY", 0) : 3u;
+		const int tf = num("NRS_TAIL_FILL", 0);
+		k.route.tail_fill = (tf == 1 || tf == 2 || tf == 4) ? (uint32_t)tf : 4u;
+		return k;
+	}();
+	return knobs;
+}
+
+// The operator table of a launch: the operators' device structs and what the route needs to know of them.  The cage that has come to rest gets its fine
+// look-up table here (nrs_edit::fine_stale).
+struct EditTable { DeviceEdit host[nrs_ctx::kMaxEdits]; int n; uint32_t any_poisson, any_affine; };
+static int collect_edits(nrs_edit* const* edits, int n_edits, hipStream_t s, EditTable& t) {
+	t.n = n_edits;
+	t.any_poisson = t.any_affine = 0u;
+	for (int i = 0; i < n_edits; ++i) {
+		if (!edits[i]) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: NULL edit operator");
+		if (edits[i]->fine_stale && ++edits[i]->renders_since_move >= 2u) {
+			edits[i]->fine_stale = false;
+			NRS_TRY(build_fine_lut(edits[i], s));
 		}
-		// the operator table of a slot is re-sent only when it changed (a viewer renders many frames per gizmo move)
-		DeviceEdit* shadow = ctx->edits_shadow.data() + (size_t)slot * nrs_ctx::kMaxEdits;
-		if (ctx->shadow_n[slot] != n_edits || memcmp(shadow, host_edits, sizeof(DeviceEdit) * n_edits) != 0) {
-			HIP_TRY(hipMemcpyAsync(d_edits_slot, host_edits, sizeof(DeviceEdit) * n_edits, hipMemcpyHostToDevice, s));
-			memcpy(shadow, host_edits, sizeof(DeviceEdit) * n_edits);
-			ctx->shadow_n[slot] = n_edits;
-		}
+		t.host[i] = edits[i]->de;
+		t.any_poisson |= edits[i]->de.apply_poisson;
+		t.any_affine |= (edits[i]->de.kind == kEditAffine) ? 1u : 0u;
+	}
+	return NRS_OK;
+}
+
+// what plan_route is asked: the model, the operators, the parameters, and the context's state (slot: this launch's, not counted as busy)
+static RouteRequest route_request(const nrs_model* m, const nrs_render_params& p, const EditTable& t, uint32_t spp_count, uint32_t pixels_owned, uint32_t slot, hipStream_t s) {
+	const nrs_ctx* ctx = m->ctx;
+	RouteRequest q{};
+	q.n_extra_dims = m->n_extra_dims; q.rgb_deep = m->dm.rgb_deep; q.numerics = m->dm.numerics;
+	const LevelParams* lv = m->dm.levels;
+	for (int it = 7; it >= 0 && lv[2 * it].hashed && lv[2 * it + 1].hashed && !lv[2 * it].cached && !lv[2 * it + 1].cached; --it) ++q.hashed_pairs;
+	q.any_poisson = t.any_poisson; q.any_affine = t.any_affine; q.apply_operators = p.apply_operators;
+	q.render_mode = p.render_mode; q.show_accel = p.show_accel; q.dof_on = p.dof != 0.f; q.distortion_mode = p.distortion_mode; q.distortion_map = p.d_distortion_map != nullptr;
+	q.envmap = p.d_envmap != nullptr; q.glow_mode = p.glow_mode;
+	q.cone_angle_constant = p.cone_angle_constant;
+	q.tile_size = p.tile_size; q.height = (uint32_t)p.resolution[1]; q.spp_count = spp_count;
+	q.lane_teams = ctx->lane_teams; q.n_cus = ctx->n_cus; q.pixels_owned = pixels_owned;
+	const unsigned long long fb = ctx->h_feedback ? __atomic_load_n(ctx->h_feedback, __ATOMIC_RELAXED) : 0ull;
+	q.hit_share = (fb >> 32) ? (double)(uint32_t)fb / (double)(fb >> 32) : 0.25;
+	// busy = number of OTHER streams with an unfinished launch (launches queued behind one another on a stream do not overlap); a slice has no schedule to choose
+	hipStream_t seen[nrs_ctx::kInFlight];
+	for (int k = 0; k < nrs_ctx::kInFlight && p.render_mode != NRS_RENDER_SLICE; ++k) {
+		if ((uint32_t)k == slot || !ctx->slot_used[k] || ctx->slot_stream[k] == s) continue;
+		bool dup = false;
+		for (uint32_t i = 0; i < q.busy; ++i) dup = dup || seen[i] == ctx->slot_stream[k];
+		if (!dup && hipEventQuery(ctx->slot_done[k]) == hipErrorNotReady) seen[q.busy++] = ctx->slot_stream[k];
+	}
+	(void)hipGetLastError(); // hipErrorNotReady is an answer, not an error
+	q.knobs = render_knobs().route;
+	return q;
+}
+
+// Enqueues one launch on its slot of the context's rings: `launch` is the render kernel of plan->row, or the slice kernel (plan == nullptr).  -> the launch's statistics block.
+// A slot is reused every kInFlight launches, possibly from another stream: the stream waits for the slot's last launch first.
+// The statistics / queue block of a launch: a slot owns two, and the render kernel's last workgroup zeroes the one it did NOT use, which the slot's next
+// launch takes (launches of a slot are ordered: same stream, or the event wait) -- so a frame costs no memset (two 5-us fill kernels per frame in
+// the round-3 timeline: 2 % of a 1/8 share-frame).  The Slice path and a launch after a failed one still clear their block the plain way.
+static int enqueue(nrs_model* m, const nrs_render_params& p, hipStream_t s, uint32_t slot, const EditTable& t, RenderArgs& a, const RoutePlan* plan, RenderCounters** d_counters) {
+	nrs_ctx* ctx = m->ctx;
+	if (ctx->slot_used[slot] && ctx->slot_stream[slot] != s) HIP_TRY(hipStreamWaitEvent(s, ctx->slot_done[slot], 0));
+	// the operator table of a slot is re-sent only when it changed (a viewer renders many frames per gizmo move)
+	DeviceEdit* d_edits_slot = ctx->d_edits + (size_t)slot * nrs_ctx::kMaxEdits;
+	DeviceEdit* shadow = ctx->edits_shadow.data() + (size_t)slot * nrs_ctx::kMaxEdits;
+	if (t.n > 0 && (ctx->shadow_n[slot] != t.n || memcmp(shadow, t.host, sizeof(DeviceEdit) * t.n) != 0)) {
+		HIP_TRY(hipMemcpyAsync(d_edits_slot, t.host, sizeof(DeviceEdit) * t.n, hipMemcpyHostToDevice, s));
+		memcpy(shadow, t.host, sizeof(DeviceEdit) * t.n);
+		ctx->shadow_n[slot] = t.n;
 	}
 	a.edits = d_edits_slot;
-	{
-		static const uint32_t dbg = []() {
-			const char* e = dev_knob("NRS_DEBUG");
-			const char* sk = dev_knob("NRS_SKIP_PAIRS"); // bit it: level pair (2 it, 2 it + 1) is not gathered (nrs_mlp.cuh: KIND_SKIP; measurement only)
-			return (e ? (uint32_t)atoi(e) & 0xffu : 0u) | (sk ? ((uint32_t)strtoul(sk, nullptr, 0) & 0xffu) << 8 : 0u);
-		}();
-		a.dbg = dbg;
-	}
-	{ // Cone stepping is what the reference switches on for aabb_scale > 1 (tn:3410-3425): scenes whose fine hashed levels no two samples of a wave share, so that their
-	  // 8 MB of table lines thrash the 4 MB L2 of an XCD -- the GATE instantiation time-multiplexes it (nrs_mlp.cuh encode_to_lds; profiles/r06_garden.md: L2 misses per
-	  // sample 11.5 -> 7.2, +5 % on the garden frame).  A unit-cube scene (constant steps) never takes it: there the gate costs 18 %.
-		static const int gate_on = []() { const char* e = dev_knob("NRS_L2_GATE"); return e ? atoi(e) : 1; }(); // (0: off -- A/B)
-		// (only where the gate has something to separate: the two, three or four finest level PAIRS hashed without records -- one phase each -- and records below them;
-		// more hashed pairs than phases would run the GATE instantiation ungated, 5 % behind the default kernel: profiles/r06/ab_gate_phases_*.txt)
-		const LevelParams* lv = m->dm.levels;
-		int hashed_pairs = 0;
-		for (int it = 7; it >= 0 && lv[2 * it].hashed && lv[2 * it + 1].hashed && !lv[2 * it].cached && !lv[2 * it + 1].cached; --it) ++hashed_pairs;
-		// (= kGateMaxPhases of the kernels.  Six phases for a model without any records: 4.36 -> 4.18 Gsamples/s, profiles/r06/ab_gate6_garden_nocache.txt -- a frame's round has
-		// no time for six waits; the occupancy refresh, one gather per wave, gains with up to six: NRS_REFRESH_GATE_PHASES)
-		a.gate = (gate_on && p->cone_angle_constant > 0.f && hashed_pairs >= 2 && hashed_pairs <= 4) ? 1u : 0u;
-	}
-	// everything of render_nerf's surface beyond Shade / Cost with a pinhole camera runs the EXTRA instantiation (one lane per ray)
-	a.extra = ((p->render_mode != NRS_RENDER_SHADE && p->render_mode != NRS_RENDER_COST) || p->show_accel || p->dof != 0.f || p->distortion_mode || p->d_distortion_map ||
-	           p->d_envmap || p->glow_mode) ? 1u : 0u;
-	if (m->dm.rgb_deep && !a.extra) {
-		// A third rgb hidden layer: the automatic schedule has a DEEP instantiation for the plain case (Shade / Cost, cage edits without the membrane correction, default
-		// roundings, no forced schedule); everything else of such a network runs the DEEP twins of the catch-all (launch_render)
-		static const bool env_sched = (dev_knob("NRS_TEAM") && atoi(dev_knob("NRS_TEAM")) != 0) || (dev_knob("NRS_HYBRID") && atoi(dev_knob("NRS_HYBRID")) == 0) || dev_knob("NRS_RENDER_CFG");
-		const bool plain = !a.any_poisson && !a.any_affine && m->dm.numerics == 0u && !ctx->lane_teams && !env_sched && !(a.dbg & 4u);
-		if (!plain) a.extra = 1u;
-	}
-	if (m->n_extra_dims) {
-		// Light directions: the automatic schedule has a LIGHT twin of the default kernel for the plain case (Shade / Cost with a pinhole camera, no operators or cage edits
-		// without the membrane correction, default roundings, no forced schedule); everything else such a network renders runs its catch-all instantiation (launch_render).
-		// The membrane correction and the measurement routes have no instantiation with the light term: refused, never rendered without it.
-		if (a.any_poisson && p->apply_operators) return fail(NRS_ERR_UNSUPPORTED, "nrs_render_nerf: the membrane correction (apply_poisson) is not supported for a network with light directions (n_extra_dims = 3)");
-		a.any_poisson = 0; // (operators switched off: the edits are not looked at)
-		if ((a.dbg & 4u) || dev_knob("NRS_RENDER_CFG")) return fail(NRS_ERR_UNSUPPORTED, "nrs_render_nerf: the wave log (NRS_DEBUG bit 2) and NRS_RENDER_CFG are not supported for a network with light directions (n_extra_dims = 3)");
-		a.gate = 0; // (the L2 phase gate is a schedule of the plain kernel alone: such a scene renders ungated)
-		static const bool env_sched = (dev_knob("NRS_TEAM") && atoi(dev_knob("NRS_TEAM")) != 0) || (dev_knob("NRS_HYBRID") && atoi(dev_knob("NRS_HYBRID")) == 0);
-		const bool plain = !a.any_affine && m->dm.numerics == 0u && !m->dm.rgb_deep && !ctx->lane_teams && !env_sched;
-		if (!plain) a.extra = 1u;
-	}
-	if (p->render_mode == NRS_RENDER_SLICE) { // tn:3109-3162: no marching at all; one network evaluation per owned pixel
-		a.frame = d_frame; a.depth = d_depth; a.steps = d_steps; a.counters = d_counters_slot;
-		HIP_TRY(hipMemsetAsync(d_counters_slot, 0, sizeof(RenderCounters), s));
-		ctx->counters_clean[slot] = false; // (slice_kernel leaves its statistics in the block and cleans nothing: the slot's next launch clears it)
+	a.counters = *d_counters = ctx->d_counters + 2 * slot + ctx->counter_parity[slot];
+	const bool clean = plan && ctx->counters_clean[slot];
+	ctx->counters_clean[slot] = false; // (until a render launch is known to be enqueued: its last workgroup cleans the other block; slice_kernel cleans nothing)
+	if (!clean) HIP_TRY(hipMemsetAsync(a.counters, 0, sizeof(RenderCounters), s));
+	if (!plan) { // tn:3109-3162: no marching at all; one network evaluation per owned pixel
 		NRS_TRY(launch_slice(m->dm, a, ctx->n_cus, s));
-		HIP_TRY(hipEventRecord(ctx->slot_done[slot], s));
-		ctx->slot_stream[slot] = s;
-		ctx->slot_used[slot] = true;
-		launch_lock.unlock();
-		if (h_stats) {
-			RenderCounters c;
-			HIP_TRY(hipMemcpyAsync(&c, d_counters_slot, sizeof(c), hipMemcpyDeviceToHost, s));
-			HIP_TRY(hipStreamSynchronize(s));
-			h_stats->n_samples = c.n_samples;
-			h_stats->n_rays_alive = c.n_rays_alive;
-			h_stats->n_rays_hit = c.n_rays_hit;
-		}
-		return NRS_OK;
-	}
-	{ // lane teams (render_kernel's TEAM) when the launch cannot fill the GPU with one ray per lane.  Rays per lane is
-	  // estimated from the share of pixels that became rays in the last finished launch (written by its last workgroup;
-	  // 0.25 until one has finished).  Measured on 1080p lego (0.22 of the pixels hit), frame shares 1/1 .. 1/8, ms per
-	  // launch with 1 / 2 / 4 lanes per ray: 3.09 2.89 3.31 | 2.07 1.78 1.95 | 1.56 1.25 1.21 | 1.19 0.93 0.88; 8 and 16
-	  // lanes lose everywhere (1.07, 1.72 at 1/8); 2560x1440: 4.31 4.52 5.64; aabb-16 1080p (every pixel hits): 9.64 9.76 10.9
-		static const bool hybrid_on = []() { const char* e = dev_knob("NRS_HYBRID"); return !e || atoi(e) != 0; }();
-		static const int env_forced = []() { const char* e = dev_knob("NRS_TEAM"); return e ? atoi(e) : 0; }();
-		const int forced = ctx->lane_teams ? ctx->lane_teams : env_forced;
-		const unsigned long long fb = ctx->h_feedback ? __atomic_load_n(ctx->h_feedback, __ATOMIC_RELAXED) : 0ull;
-		const double hit_share = (fb >> 32) ? (double)(uint32_t)fb / (double)(fb >> 32) : 0.25;
-		a.pixels_owned = (uint32_t)std::min<uint64_t>((uint64_t)a.n_packets * 64ull * spp_count, 0xffffffffull); // (a batch: the rays of all its samples decide the schedule)
-		// Launches of this context still running on OTHER streams (frames in flight: a rank of a multi-GPU job that overlaps its frames, a viewer that
-		// double-buffers) share the GPU with this one: the launch gets 1 / (1 + busy) of the lanes, and once three or more overlap the GPU is full
-		// whatever the size of one launch -- lane teams (a latency device) then only cost fill passes.  Measured, 1/8 share of the 1080p bench frame,
-		// ms per share-frame with 1 / 2 / 4 frames in flight: automatic choice before this rule 0.69 / 0.69 / 0.46, one lane per ray 0.99 / 0.54 / 0.36,
-		// two lanes 0.77 / 0.47 / 0.49 (tools/scale_probe_teams.py) -- i.e. 0.95 of the single-GPU per-GPU throughput at an eighth of the frame.
-		uint32_t busy = 0; // = number of OTHER streams with an unfinished launch (launches queued behind one another on a stream do not overlap)
-		hipStream_t seen[nrs_ctx::kInFlight];
-		for (int k = 0; k < nrs_ctx::kInFlight; ++k) {
-			if ((uint32_t)k == slot || !ctx->slot_used[k] || ctx->slot_stream[k] == s) continue;
-			bool dup = false;
-			for (uint32_t q = 0; q < busy; ++q) dup = dup || seen[q] == ctx->slot_stream[k];
-			if (!dup && hipEventQuery(ctx->slot_done[k]) == hipErrorNotReady) seen[busy++] = ctx->slot_stream[k];
-		}
-		(void)hipGetLastError(); // hipErrorNotReady is an answer, not an error
-		const double rays_per_lane = hit_share * (double)a.pixels_owned * (double)(1u + busy) / (64.0 * 16.0 * (double)ctx->n_cus);
-		// Round 3: team rounds test the team's next positions in parallel and waves hand rays over, so the small-launch schedule (packets of 16 / 32 / 64
-		// pixels = 4 / 2 / 1 lanes on a pixel during the fill, every generation sized by the rays its wave has pending) is the automatic choice up to
-		// the sizes where the hybrid schedule of whole images takes over.  tools/schedule_probe.py (profiles/r03_schedules.md), ms per frame with
-		// 16- / 32- / 64-pixel packets | hybrid | fixed 2 lanes per ray: 640x360 0.66 / 0.77 / 1.18 | 1.15 | 0.85, 960x540 0.93 / 0.96 / 1.16 | 1.20 | 1.12,
-		// 1280x720 1.40 / 1.28 / 1.51 | 1.43 | 1.44, 1600x900 2.02 / 1.76 / 1.85 | 1.83 | 1.90, 1080p 2.77 / 2.36 / 2.37 | 2.35 | 2.48, 1440p 4.66 / 3.86 / 3.71 |
-		// 3.79 | 3.96; a rank's tiles of the 1080p frame, N = 8: 0.53 / 0.57 / 0.89 | - | 0.57, N = 4: 0.85 / 0.82 / 1.01 | - | 0.94, N = 2: 1.49 / 1.32 / 1.43 | - | 1.47,
-		// N = 1: 2.78 / 2.36 / 2.37 | - | 2.49.  With frames in flight the thresholds hold for the rays of ALL overlapping launches.
-		uint32_t fill_lanes = rays_per_lane <= 0.6 ? 4u : (rays_per_lane <= 2.6 ? 2u : 1u);
-		// the fill runs once per pixel and lane on it: keep it to ~16 passes over the GPU (an all-miss 1080p frame is 8)
-		while (fill_lanes > 1 && (double)fill_lanes * (double)a.pixels_owned * (double)(1u + busy) > 17.0 * 64.0 * 16.0 * (double)ctx->n_cus) fill_lanes >>= 1;
-		// The hybrid schedule (64-ray generations at one lane per ray for the bulk of the queue, lane teams for its tail) was the choice for whole images with many
-		// rays per lane until the queue's chunks went from 8 to 2 packets; since then the small-launch schedule wins there too -- bench frames, Gsamples/s hybrid /
-		// 64-pixel packets: lego + cage 10.8 / 12.0, varied opacity 10.2 / 10.6, aabb-16 (7.9 rays per lane) 4.79 / 4.87 -- and hybrid runs only when forced (-1).
-		const bool small_launch = true;
-		uint32_t team = 1; // fixed lanes per ray: only when forced
-		if (forced == 1 || forced == 2 || forced == 4) team = (uint32_t)forced;
-		if (forced == -1) team = 1;
-		// (the EXTRA / run-time-numerics / mixed membrane + affine instantiations are built for one lane per ray; the membrane correction of cage edits
-		// alone runs the automatic schedule since round 4, AffineDuplication since round 6)
-		const bool poisson_teams = a.any_poisson && !a.any_affine && !a.extra && m->dm.numerics == 0u;
-		const bool affine_teams = a.any_affine && !a.any_poisson && !a.extra && m->dm.numerics == 0u; // (round 6: the AFFINE instantiation of the automatic schedule)
-		const bool one_lane_only = (a.any_poisson && !poisson_teams) || (a.any_affine && !affine_teams) || a.extra;
-		// (fixed 2 / 4 lanes per ray exist for the default kernel only: a forced size leaves the membrane path on the catch-all and AffineDuplication on its
-		// one-lane instantiation -- packets sized for 8x4 / 4x4 there would send packet_pixel<1> past the owned tiles; launch_render's route check refuses it)
-		if (one_lane_only || a.any_poisson || a.any_affine) team = 1;
-		static const bool log_teams = dev_knob("NRS_TEAM_LOG") != nullptr;
-		if (log_teams) fprintf(stderr, "[nrs team] pixels=%u hit_share=%.3f busy=%u rays/lane=%.3f small-launch=%d fill lanes=%u forced=%d\n", a.pixels_owned, hit_share, busy, rays_per_lane, (int)small_launch, fill_lanes, forced);
-		static const uint32_t tail_target = []() { const char* e = dev_knob("NRS_TAIL_TARGET"); return e && atoi(e) >= 1 ? (uint32_t)std::min(atoi(e), 64) : 24u; }(); // (<= kRing - 64: the fill adds up to 64 rays per packet to a 128-entry ring) 8 / 16 / 24 / 32 / 48: 8.92 / 8.91 / 9.11 / 9.01 / 8.47 Gsamples/s
-		a.tail_target = tail_target;
-		static const uint32_t reteam = []() { const char* e = dev_knob("NRS_RETEAM"); return e ? (uint32_t)atoi(e) : 3u; }(); // bit 0: at the end of a wave's work, bit 1: whenever a tail generation has thinned out
-		a.reteam = reteam;
-		static const uint32_t steal = []() { const char* e = dev_knob("NRS_STEAL"); return e ? (uint32_t)atoi(e) : 1u; }();
-		a.steal = ctx->handover >= 0 ? (uint32_t)ctx->handover : steal;
-		if (((small_launch && !forced && hybrid_on) || forced == -2 || forced == -3 || forced == -4) && !one_lane_only) {
-			// few rays for the GPU: 4x4 packets only, and every generation takes ALL the rays its wave has pending with as many
-			// lanes per ray as fit (4 up to 16 rays, 2 up to 32), so that no wave is left with a second, nearly empty generation
-			// (1/8 share of the bench frame: 0.88 -> 0.82 ms).
-			a.team = 0;
-			a.all_tail = 1;
-			a.fill_lanes = forced == -4 ? 1u : (forced == -3 ? 2u : (forced == -2 ? 4u : fill_lanes));
-			NRS_TRY(tile_geometry(*p, a.fill_lanes, a.tiles_x, owned_tiles, a.n_packets, a.packets_per_tile_x));
-			static const uint32_t all_tail_target = []() { const char* e = dev_knob("NRS_ALLTAIL_TARGET"); return e && atoi(e) >= 1 ? (uint32_t)std::min(atoi(e), 64) : 16u; }(); // (<= kRing - 64, as above)
-			a.tail_target = all_tail_target;
-		} else if (team > 1 && (forced > 0 || p->tile_size != 0 || !hybrid_on)) {
-			a.team = team;
-			NRS_TRY(tile_geometry(*p, team, a.tiles_x, owned_tiles, a.n_packets, a.packets_per_tile_x));
-		} else if (p->tile_size == 0 && !a.any_poisson && !a.any_affine && !a.extra && (forced == -1 || (!forced && hybrid_on))) { // (the hybrid schedule: forced only)
-			// whole images with more rays than the small-launch schedule is for: hybrid (one lane per ray, lane teams for the tail of the queue)
-			// hybrid: every 3rd packet row leaves the 8x8 list and joins the end of the queue as 4x4 tail packets (packet_pixel_bulk/_tail);
-			// measured on 1080p lego + cage, every 2nd / 3rd / 4th / 6th / 8th / 16th row: 8.88 / 8.89 / 8.79 / 8.75 / 8.65 / 8.65 Gsamples/s
-			static const uint32_t tail_every = []() { const char* e = dev_knob("NRS_TAIL_EVERY"); return e && atoi(e) >= 2 ? (uint32_t)atoi(e) : 3u; }();
-			const uint32_t rows = ((uint32_t)p->resolution[1] + 7u) / 8u, tail_rows = rows / tail_every;
-			a.tail_every = tail_every;
-			if (tail_rows) {
-				static const uint32_t tail_fill = []() { const char* e = dev_knob("NRS_TAIL_FILL"); return e && (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4) ? (uint32_t)atoi(e) : 4u; }();
-				a.team = 0;
-				a.fill_lanes = tail_fill; // lanes on a pixel while a tail packet is filled: packets of 4x4 / 8x4 / 8x8 pixels (packet_pixel_tail)
-				a.p_big = (rows - tail_rows) * a.tiles_x;
-				a.n_packets = a.p_big + tail_rows * a.tiles_x * tail_fill;
-			}
-		}
-		// a batch does not report: the feedback word sizes the caller's next single-frame launch, whose pixels_owned this launch's is not
-		a.feedback = spp_count > 1u ? nullptr : ctx->d_feedback;
-	}
-	// the queue of a batch: spp_count times the packets of one sample (hybrid: all samples' 8x8 packets, then all samples' tail packets -- one tail, one drain)
-	a.spp_count = spp_count;
-	a.spp_packets = a.n_packets;
-	a.spp_big = a.p_big;
-	a.slab_stride = spp_count > 1u ? (uint32_t)slab_stride : 0u;
-	a.n_packets *= spp_count;
-	a.p_big *= spp_count;
-	a.max_steps = p->max_march_steps ? p->max_march_steps : 10000u; // MARCH_ITER, testbed_nerf.cu:56
-	a.frame = d_frame;
-	a.depth = d_depth;
-	a.steps = d_steps;
-	a.counters = d_counters_slot;
-	a.counters_next = d_counters_other;
-	a.wave_log = (a.dbg & 4u) ? ctx->d_wave_log : nullptr;
-	if (a.wave_log) HIP_TRY(hipMemsetAsync(ctx->d_wave_log, 0, 8192 * 4 * 8, s));
-	if (!ctx->counters_clean[slot]) HIP_TRY(hipMemsetAsync(d_counters_slot, 0, sizeof(RenderCounters), s));
-	ctx->counters_clean[slot] = false; // (until the launch is known to be enqueued: its last workgroup cleans the other block)
-	if (a.n_packets == 0) { // nothing to launch (no owned tiles): the block stays as it is -- zero
-		ctx->counters_clean[slot] = true;
 	} else {
-		const unsigned long long dispatches0 = launch_render_dispatches();
-		NRS_TRY(launch_render(model_for_launch(m, *p), a, ctx->n_cus, s));
-		ctx->render_dispatches += launch_render_dispatches() - dispatches0;
-		ctx->last_schedule = a.team | (a.fill_lanes << 8) | (a.all_tail << 16) | ((a.p_big ? 1u : 0u) << 17) | ((spp_count > 1u ? 1u : 0u) << 18);
-		ctx->counter_parity[slot] ^= 1u;
+		a.counters_next = ctx->d_counters + 2 * slot + (ctx->counter_parity[slot] ^ 1u);
+		a.wave_log = (a.dbg & 4u) ? ctx->d_wave_log : nullptr;
+		if (a.wave_log) HIP_TRY(hipMemsetAsync(ctx->d_wave_log, 0, 8192 * 4 * 8, s));
+		if (a.n_packets != 0) { // (else nothing to launch, no owned tiles: the block stays as it is -- zero)
+			const unsigned long long dispatches0 = launch_render_dispatches();
+			NRS_TRY(launch_render((RouteId)plan->row, model_for_launch(m, p), a, ctx->n_cus, s));
+			ctx->render_dispatches += launch_render_dispatches() - dispatches0;
+			ctx->last_schedule = a.team | (a.fill_lanes << 8) | (a.all_tail << 16) | ((a.p_big ? 1u : 0u) << 17) | ((a.spp_count > 1u ? 1u : 0u) << 18);
+			ctx->counter_parity[slot] ^= 1u;
+		}
 		ctx->counters_clean[slot] = true;
 	}
 	HIP_TRY(hipEventRecord(ctx->slot_done[slot], s));
 	ctx->slot_stream[slot] = s;
 	ctx->slot_used[slot] = true;
-	launch_lock.unlock();
-	if (h_stats) {
-		RenderCounters c;
-		HIP_TRY(hipMemcpyAsync(&c, d_counters_slot, sizeof(c), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		h_stats->n_samples = c.n_samples;
-		h_stats->n_rays_alive = c.n_rays_alive;
-		h_stats->n_rays_hit = c.n_rays_hit;
-		ctx->last_handover = c.walk[7];
-		if (a.dbg & 12u) fprintf(stderr, "[nrs hand-over] %llu rays in %llu hand-overs\n", c.walk[7] & 0xffffffffull, c.walk[7] >> 32);
-		if (a.dbg & 4u) {
-			static const char* names[8] = {"fill", "refill", "setup+warp", "gather", "sh+mlp", "composite+march+shade", "-", "exit"};
-			unsigned long long tot = 0;
-			for (int i = 0; i < 8; ++i) if (i != 6) tot += c.phase_cycles[i];
-			fprintf(stderr, "[nrs phases] samples=%llu", (unsigned long long)c.n_samples);
-			for (int i = 0; i < 8; ++i)
-				if (c.phase_cycles[i] && i != 6) fprintf(stderr, " %s=%.1f%%", names[i], 100.0 * (double)c.phase_cycles[i] / (double)tot);
-			fprintf(stderr, " | mean wave lifetime = %.1f%% of the longest (%.2f Mcycles)", 100.0 * ((double)tot / 4096.0) / (double)c.phase_cycles[6], (double)c.phase_cycles[6] / 1e6);
-			fprintf(stderr, "\n");
-			fprintf(stderr, "[nrs walk] fill: %llu lane iterations in %llu wave trips (%.1f lanes busy per trip); march: %llu lane iterations in %llu wave trips "
-			        "(%.1f lanes/trip), %llu of %llu rounds needed > 1 trip; live lanes per round %.1f\n",
-			        c.walk[0], c.walk[1], c.walk[1] ? (double)c.walk[0] / (double)c.walk[1] : 0.0, c.walk[2], c.walk[3],
-			        c.walk[3] ? (double)c.walk[2] / (double)c.walk[3] : 0.0, c.walk[6], c.walk[4], c.walk[4] ? (double)c.walk[5] / (double)c.walk[4] : 0.0);
-			if (c.walk[8])
-				fprintf(stderr, "[nrs cage scan] %llu samples inside a deformed box (%.1f %% of the samples), %llu of them found a tet; rounds with such a sample: %llu of %llu (%.1f %%); "
-				        "candidates tested %llu (%.2f per sample in the box), scan wave trips %llu (%.2f per round that scans)\n",
-				        c.walk[8], 100.0 * (double)c.walk[8] / (double)std::max<unsigned long long>(c.n_samples, 1), c.walk[12], c.walk[9], c.walk[4], 100.0 * (double)c.walk[9] / (double)std::max<unsigned long long>(c.walk[4], 1),
-				        c.walk[10], (double)c.walk[10] / (double)c.walk[8], c.walk[11], (double)c.walk[11] / (double)std::max<unsigned long long>(c.walk[9], 1));
-			// per-wave log: when did each wave finish (wall clock), when did it first find the frame's queue empty
-			std::vector<unsigned long long> wl(8192 * 4);
-			HIP_TRY(hipMemcpy(wl.data(), ctx->d_wave_log, wl.size() * 8, hipMemcpyDeviceToHost));
-			if (const char* dump = dev_knob("NRS_WAVE_LOG_FILE")) { // raw log of the LAST launch with statistics, for tools/wave_log_report.py
-				if (FILE* f = fopen(dump, "wb")) { fwrite(wl.data(), 8, wl.size(), f); fclose(f); }
-			}
-			std::vector<std::array<unsigned long long, 4>> rec; // {end tick (10 ns), rounds | rounds before queue-empty << 16 | t_queue_empty << 32, packets, xcc}
-			unsigned long long t0min = ~0ull;
-			for (size_t i = 0; i < 8192; ++i) if (wl[4 * i]) t0min = std::min(t0min, wl[4 * i + 3] >> 32);
-			for (size_t i = 0; i < 8192; ++i)
-				if (wl[4 * i]) {
-					const unsigned long long wall = wl[4 * i + 3] & 0xffffffffull, start = (wl[4 * i + 3] >> 32) - t0min;
-					const unsigned long long rq = (wl[4 * i + 1] >> 16) & 0xffff, tq = (wl[4 * i + 1] >> 32) + start;
-					rec.push_back({wall + start, (wl[4 * i + 1] & 0xffffull) | (rq << 16) | (tq << 32), wl[4 * i + 2] & 0xffffull, wl[4 * i + 2] >> 56});
-				}
-			std::sort(rec.begin(), rec.end());
-			if (!rec.empty()) {
-				auto pr = [&](const char* tag, size_t i) {
-					fprintf(stderr, "   %s: end=%.1f us, queue found empty at %.1f us, rounds=%llu (%llu after that), packets=%llu, xcc=%llu\n", tag, rec[i][0] / 100.0,
-					        (rec[i][1] >> 32) / 100.0, rec[i][1] & 0xffff, (rec[i][1] & 0xffff) - ((rec[i][1] >> 16) & 0xffff), rec[i][2], rec[i][3]);
-				};
-				double mean = 0;
-				for (auto& r : rec) mean += (double)r[0];
-				mean /= rec.size();
-				fprintf(stderr, "[nrs waves] n=%zu, mean end = %.1f%% of the last end\n", rec.size(), 100.0 * mean / (double)rec.back()[0]);
-				pr("min", 0); pr("p25", rec.size() / 4); pr("p50", rec.size() / 2); pr("p75", rec.size() * 3 / 4); pr("p95", rec.size() * 95 / 100);
-				pr("p99", rec.size() * 99 / 100); pr("max", rec.size() - 1);
-			}
+	return NRS_OK;
+}
+
+// the NRS_DEBUG bit-2 print-out of a launch: phase shares, walk statistics and the per-wave log
+static int report_wave_log(nrs_ctx* ctx, const RenderCounters& c) {
+	static const char* names[8] = {"fill", "refill", "setup+warp", "gather", "sh+mlp", "composite+march+shade", "-", "exit"};
+	unsigned long long tot = 0;
+	for (int i = 0; i < 8; ++i) if (i != 6) tot += c.phase_cycles[i];
+	fprintf(stderr, "[nrs phases] samples=%llu", (unsigned long long)c.n_samples);
+	for (int i = 0; i < 8; ++i)
+		if (c.phase_cycles[i] && i != 6) fprintf(stderr, " %s=%.1f%%", names[i], 100.0 * (double)c.phase_cycles[i] / (double)tot);
+	fprintf(stderr, " | mean wave lifetime = %.1f%% of the longest (%.2f Mcycles)", 100.0 * ((double)tot / 4096.0) / (double)c.phase_cycles[6], (double)c.phase_cycles[6] / 1e6);
+	fprintf(stderr, "\n");
+	fprintf(stderr, "[nrs walk] fill: %llu lane iterations in %llu wave trips (%.1f lanes busy per trip); march: %llu lane iterations in %llu wave trips "
+	        "(%.1f lanes/trip), %llu of %llu rounds needed > 1 trip; live lanes per round %.1f\n",
+	        c.walk[0], c.walk[1], c.walk[1] ? (double)c.walk[0] / (double)c.walk[1] : 0.0, c.walk[2], c.walk[3],
+	        c.walk[3] ? (double)c.walk[2] / (double)c.walk[3] : 0.0, c.walk[6], c.walk[4], c.walk[4] ? (double)c.walk[5] / (double)c.walk[4] : 0.0);
+	if (c.walk[8])
+		fprintf(stderr, "[nrs cage scan] %llu samples inside a deformed box (%.1f %% of the samples), %llu of them found a tet; rounds with such a sample: %llu of %llu (%.1f %%); "
+		        "candidates tested %llu (%.2f per sample in the box), scan wave trips %llu (%.2f per round that scans)\n",
+		        c.walk[8], 100.0 * (double)c.walk[8] / (double)std::max<unsigned long long>(c.n_samples, 1), c.walk[12], c.walk[9], c.walk[4], 100.0 * (double)c.walk[9] / (double)std::max<unsigned long long>(c.walk[4], 1),
+		        c.walk[10], (double)c.walk[10] / (double)c.walk[8], c.walk[11], (double)c.walk[11] / (double)std::max<unsigned long long>(c.walk[9], 1));
+	// per-wave log: when did each wave finish (wall clock), when did it first find the frame's queue empty
+	std::vector<unsigned long long> wl(8192 * 4);
+	HIP_TRY(hipMemcpy(wl.data(), ctx->d_wave_log, wl.size() * 8, hipMemcpyDeviceToHost));
+	if (const char* dump = dev_knob("NRS_WAVE_LOG_FILE")) { // raw log of the LAST launch with statistics, for tools/wave_log_report.py
+		if (FILE* f = fopen(dump, "wb")) { fwrite(wl.data(), 8, wl.size(), f); fclose(f); }
+	}
+	std::vector<std::array<unsigned long long, 4>> rec; // {end tick (10 ns), rounds | rounds before queue-empty << 16 | t_queue_empty << 32, packets, xcc}
+	unsigned long long t0min = ~0ull;
+	for (size_t i = 0; i < 8192; ++i) if (wl[4 * i]) t0min = std::min(t0min, wl[4 * i + 3] >> 32);
+	for (size_t i = 0; i < 8192; ++i)
+		if (wl[4 * i]) {
+			const unsigned long long wall = wl[4 * i + 3] & 0xffffffffull, start = (wl[4 * i + 3] >> 32) - t0min;
+			const unsigned long long rq = (wl[4 * i + 1] >> 16) & 0xffff, tq = (wl[4 * i + 1] >> 32) + start;
+			rec.push_back({wall + start, (wl[4 * i + 1] & 0xffffull) | (rq << 16) | (tq << 32), wl[4 * i + 2] & 0xffffull, wl[4 * i + 2] >> 56});
 		}
+	std::sort(rec.begin(), rec.end());
+	if (!rec.empty()) {
+		auto pr = [&](const char* tag, size_t i) {
+			fprintf(stderr, "   %s: end=%.1f us, queue found empty at %.1f us, rounds=%llu (%llu after that), packets=%llu, xcc=%llu\n", tag, rec[i][0] / 100.0,
+			        (rec[i][1] >> 32) / 100.0, rec[i][1] & 0xffff, (rec[i][1] & 0xffff) - ((rec[i][1] >> 16) & 0xffff), rec[i][2], rec[i][3]);
+		};
+		double mean = 0;
+		for (auto& r : rec) mean += (double)r[0];
+		mean /= rec.size();
+		fprintf(stderr, "[nrs waves] n=%zu, mean end = %.1f%% of the last end\n", rec.size(), 100.0 * mean / (double)rec.back()[0]);
+		pr("min", 0); pr("p25", rec.size() / 4); pr("p50", rec.size() / 2); pr("p75", rec.size() * 3 / 4); pr("p95", rec.size() * 95 / 100);
+		pr("p99", rec.size() * 99 / 100); pr("max", rec.size() - 1);
 	}
 	return NRS_OK;
+}
+
+// the statistics of the launch on stream s (synchronises it); march: the launch ran a render kernel (hand-over counts, the wave log)
+static int read_stats(nrs_ctx* ctx, hipStream_t s, const RenderCounters* d_counters, bool march, uint32_t dbg, nrs_render_stats* h_stats) {
+	RenderCounters c;
+	HIP_TRY(hipMemcpyAsync(&c, d_counters, sizeof(c), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	h_stats->n_samples = c.n_samples;
+	h_stats->n_rays_alive = c.n_rays_alive;
+	h_stats->n_rays_hit = c.n_rays_hit;
+	if (!march) return NRS_OK;
+	ctx->last_handover = c.walk[7];
+	if (dbg & 12u) fprintf(stderr, "[nrs hand-over] %llu rays in %llu hand-overs\n", c.walk[7] & 0xffffffffull, c.walk[7] >> 32);
+	return (dbg & 4u) ? report_wave_log(ctx, c) : NRS_OK;
+}
+
+static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frame, float* d_depth,
+                          uint32_t* d_steps, size_t slab_stride, void* stream, nrs_render_stats* h_stats) {
+	{ const int st = check_render_args(m, p, edits, n_edits, spp_count, d_frame, d_depth, slab_stride); if (st != NRS_OK) return st; }
+	nrs_ctx* ctx = m->ctx;
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = (hipStream_t)stream;
+	const RenderKnobs& knobs = render_knobs();
+	const bool slice = p->render_mode == NRS_RENDER_SLICE;
+	std::unique_lock<std::mutex> launch_lock(ctx->launch_mutex); // held until the launch is enqueued and the slot's book-keeping is written (released before the statistics' sync)
+	const uint32_t slot = ctx->launch_serial.fetch_add(1u) % (uint32_t)nrs_ctx::kInFlight;
+
+	RenderArgs a{};
+	a.p = *p;
+	if (p->render_mode == NRS_RENDER_ENCODING_VIS) a.p.visualized_layer = kernel_layer(m->desc, p->visualized_layer); // (the kernels number base.json's layers)
+	uint32_t owned_tiles = 0;
+	{ const int st = tile_geometry(*p, 1, a.tiles_x, owned_tiles, a.n_packets, a.packets_per_tile_x); if (st != NRS_OK) return st; } // (8x8 packets: the launch's pixels)
+	const uint32_t pixels_owned = (uint32_t)std::min<uint64_t>((uint64_t)a.n_packets * 64ull * spp_count, 0xffffffffull); // (a batch: the rays of all its samples decide the schedule)
+	EditTable table;
+	{ const int st = collect_edits(edits, n_edits, s, table); if (st != NRS_OK) return st; }
+	const RouteRequest request = route_request(m, *p, table, spp_count, pixels_owned, slot, s);
+	const RoutePlan plan = plan_route(request);
+	if (plan.status != NRS_OK) return fail(plan.status, plan.message);
+	a.n_edits = n_edits;
+	a.any_poisson = plan.any_poisson;
+	a.any_affine = table.any_affine;
+	a.dbg = knobs.dbg;
+	a.extra = plan.extra;
+	a.gate = plan.gate;
+	a.team = 1;
+	a.fill_lanes = 4;
+	a.frame = d_frame;
+	a.depth = d_depth;
+	a.steps = d_steps;
+	if (!slice) { // (a slice marches nothing: no schedule, no queue)
+		if (knobs.log_teams) fprintf(stderr, "[nrs team] pixels=%u hit_share=%.3f busy=%u rays/lane=%.3f small-launch=%d fill lanes=%u forced=%d\n", pixels_owned, request.hit_share, request.busy, plan.rays_per_lane, 1, plan.fill_lanes_auto, plan.forced);
+		a.pixels_owned = pixels_owned;
+		a.team = plan.team;
+		a.all_tail = plan.all_tail;
+		a.fill_lanes = plan.fill_lanes;
+		a.tail_every = plan.tail_every;
+		a.tail_target = plan.tail_target;
+		a.reteam = knobs.reteam;
+		a.steal = ctx->handover >= 0 ? (uint32_t)ctx->handover : knobs.steal;
+		// the packets of one sample, cut for the plan's lanes per pixel; hybrid: the tail rows leave the 8x8 list and follow it as tail packets
+		if (plan.packet_lanes() != 1u) NRS_TRY(tile_geometry(*p, plan.packet_lanes(), a.tiles_x, owned_tiles, a.n_packets, a.packets_per_tile_x));
+		if (plan.hybrid) {
+			const uint32_t rows = ((uint32_t)p->resolution[1] + 7u) / 8u, tail_rows = rows / plan.tail_every;
+			a.p_big = (rows - tail_rows) * a.tiles_x;
+			a.n_packets = a.p_big + tail_rows * a.tiles_x * plan.fill_lanes;
+		}
+		// a batch does not report: the feedback word sizes the caller's next single-frame launch, whose pixels_owned this launch's is not
+		a.feedback = spp_count > 1u ? nullptr : ctx->d_feedback;
+		// the queue of a batch: spp_count times the packets of one sample (hybrid: all samples' 8x8 packets, then all samples' tail packets -- one tail, one drain)
+		a.spp_count = spp_count;
+		a.spp_packets = a.n_packets;
+		a.spp_big = a.p_big;
+		a.slab_stride = spp_count > 1u ? (uint32_t)slab_stride : 0u;
+		a.n_packets *= spp_count;
+		a.p_big *= spp_count;
+		a.max_steps = p->max_march_steps ? p->max_march_steps : 10000u; // MARCH_ITER, testbed_nerf.cu:56
+	}
+	RenderCounters* d_counters = nullptr;
+	{ const int st = enqueue(m, *p, s, slot, table, a, slice ? nullptr : &plan, &d_counters); if (st != NRS_OK) return st; }
+	launch_lock.unlock();
+	return h_stats ? read_stats(ctx, s, d_counters, !slice, a.dbg, h_stats) : NRS_OK;
 }
 
 int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, float* d_frame, float* d_depth,
@@ -1884,6 +1854,22 @@ int nrs_ctx_render_launches(const nrs_ctx* ctx, uint64_t* n_dispatches, uint32_t
 	std::lock_guard<std::mutex> lock(const_cast<nrs_ctx*>(ctx)->launch_mutex);
 	if (n_dispatches) *n_dispatches = ctx->render_dispatches;
 	if (last_schedule) *last_schedule = ctx->last_schedule;
+	return NRS_OK;
+}
+int nrs_route_probe(const RouteRequest* requests, uint32_t request_size, uint32_t n, RouteProbe* out, uint32_t probe_size) {
+	if (!requests || !out || request_size != sizeof(RouteRequest) || probe_size != sizeof(RouteProbe)) return fail(NRS_ERR_INVALID_ARG, "nrs_route_probe: NULL argument, or the caller's structs are not this library's");
+	for (uint32_t i = 0; i < n; ++i) {
+		const RoutePlan plan = plan_route(requests[i]);
+		RouteProbe& o = out[i];
+		memset(&o, 0, sizeof(o));
+		o.status = plan.status;
+		o.row = plan.row;
+		memcpy(o.message, plan.message, sizeof(o.message));
+		if (plan.status != NRS_OK) continue;
+		o.team = plan.team; o.all_tail = plan.all_tail; o.fill_lanes = plan.fill_lanes; o.tail_every = plan.tail_every; o.tail_target = plan.tail_target; o.hybrid = plan.hybrid;
+		o.row_has_batch = kRoutes[plan.row].batch;
+		route_name(o.name, sizeof(o.name), kRoutes[plan.row].t, requests[i].spp_count > 1u);
+	}
 	return NRS_OK;
 }
 int nrs_accumulate_spp(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count, float* d_accumulate,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/nrs.h"
+#include "nrs_route.h"
 
 #include <stdlib.h>
 
@@ -193,7 +194,8 @@ struct RenderArgs {
 };
 
 // kernel launchers (nrs_kernels.hip).  stream is a hipStream_t.
-int launch_render(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
+// launches row `row` of kRoutes (nrs_route.h; the caller planned it: plan_route), or its batch twin when a.spp_count > 1
+int launch_render(RouteId row, const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
 unsigned long long launch_render_dispatches(); // render-kernel dispatches of this process so far (nrs_ctx_render_launches counts with it)
 // render mode Slice (Testbed::render_nerf's branch, testbed_nerf.cu:3111-3175): one network evaluation per owned pixel on the slice plane
 int launch_slice(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
@@ -274,7 +276,20 @@ int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t
 int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, void* stream);
 const char* cage_last_error();
 
+// The planner behind one C symbol (exported from libnrs.so, declared here only: not part of include/nrs.h): tests sweep it without a GPU.
+struct RouteProbe {
+	int32_t  status;
+	int32_t  row;              // RouteId, -1 when refused
+	uint32_t team, all_tail, fill_lanes, tail_every, tail_target, hybrid;
+	uint32_t row_has_batch;
+	char     name[96];         // the row as route_name prints it for this request (", batch" for spp_count > 1)
+	char     message[256];
+};
+
 // the thread-local message nrs_last_error() returns (nrs_api.cpp); used by the host-only translation units
 void set_last_error(const char* msg);
 
 } // namespace nrs
+
+// plans n requests; request_size / probe_size are the caller's sizeof of the two structs (a mirror that has drifted is refused: NRS_ERR_INVALID_ARG)
+extern "C" int nrs_route_probe(const nrs::RouteRequest* requests, uint32_t request_size, uint32_t n, nrs::RouteProbe* out, uint32_t probe_size);

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <utility>
 #include "nrs_internal.h"
 #include "nrs_device.cuh"
 #include "nrs_mlp.cuh"
@@ -237,15 +238,16 @@ constexpr uint32_t kBatchXYBits = 13u, kBatchXYMask = (1u << kBatchXYBits) - 1u;
 static_assert((NRS_SPP_BATCH_MAX - 1u) >> (32u - 2u * kBatchXYBits) == 0u, "a ring entry holds the sample index beside the pixel");
 template <int WAVES, int OCC, bool PROF, bool POISSON, bool AFFINE, int TEAM, int NUM = 0, int XTRA = 0, bool BATCH = false>
 __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const RenderArgs& a_arg) {
-	constexpr bool EXTRA = (XTRA >= 1 && XTRA <= 4) || XTRA == 8, INTRO = XTRA == 2 || XTRA == 4 || XTRA == 8, DEEP = (XTRA >= 3 && XTRA <= 5) || XTRA == 8; // (3 / 4: 1 / 2 for a network whose rgb MLP has a third hidden layer, base_3layer.json; 5: that layer alone)
+	constexpr XtraTraits kX = xtra_traits(XTRA); // (nrs_route.h: the host plans routes with the same decoder)
+	constexpr bool EXTRA = kX.extra, INTRO = kX.intro, DEEP = kX.deep; // (3 / 4: 1 / 2 for a network whose rgb MLP has a third hidden layer, base_3layer.json; 5: that layer alone)
 	// 7 / 8: a network trained with light directions (DeviceModel::n_extra_dims = 3; rgb_mlp's LIGHT).  7 = the light term and nothing else: the twin of the default kernel
 	// (plain frames and cage edits on the automatic schedule); 8 = the catch-all of such a network: EXTRA + INTRO, the third hidden layer where the network has one
 	// (DeviceModel::rgb_deep, a wave-uniform run-time branch here), every numerics, AffineDuplication -- whatever 7 does not serve.
-	constexpr bool LIGHT = XTRA == 7 || XTRA == 8;
+	constexpr bool LIGHT = kX.light;
 	// four levels per round trip in the gathers (encode_to_lds QUADS): the automatic schedule's instantiations with the default or the fully tiny-cuda-nn roundings -- since
 	// round 6 the membrane instantiation too (both of its gathers: 9.68 -> 10.06 Gsamples/s, same registers; profiles/r06/ab_poisson_quads.txt)
 	constexpr bool kQuads = TEAM == 0 && !EXTRA && NUM >= 0;
-	constexpr int GATE = XTRA == 6 ? (int)kGateMaxPhases : 0; // the plain kernel with the L2 phase gate on the four finest hashed levels (encode_to_lds): cone-stepping scenes
+	constexpr int GATE = kX.gate ? (int)kGateMaxPhases : 0; // the plain kernel with the L2 phase gate on the four finest hashed levels (encode_to_lds): cone-stepping scenes
 	// The two argument structs (~1.3 KB of wave-uniform values) live in the kernel-argument segment and are read with scalar loads.
 	// Left alone, the compiler hoists every such load out of the frame loop and then spills ~150 scalar registers into VGPR lanes
 	// (v_writelane / v_readlane: VALU slots in the round loop, 3 VGPRs).  NRS_FRESH_ARGS re-derives the two references from an
@@ -674,9 +676,9 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 		  asm volatile("" :: "v"(sink)); }
 #endif
 		uint32_t res_d = 0, res_rg = 0, res_b = 0;
-		const half8* deep_w = (DEEP && (XTRA != 8 || m2.rgb_deep)) ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr; // (the third rgb hidden layer's fragments are read from HBM)
+		const half8* deep_w = (DEEP && (XTRA != kXtraLightAll || m2.rgb_deep)) ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr; // (the third rgb hidden layer's fragments are read from HBM)
 		// LIGHT: the frame's light direction (nrs_model_set_light_dir), the same for every sample: the B operand of layer 0's third k step, its A fragments in HBM
-		const half8* light_w = (LIGHT && (XTRA != 8 || m2.n_extra_dims)) ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr;
+		const half8* light_w = (LIGHT && (XTRA != kXtraLightAll || m2.n_extra_dims)) ? reinterpret_cast<const half8*>(m2.wfrag) : nullptr;
 		const half8 lb = LIGHT ? light_operand(g, m2.light01[0], m2.light01[1], m2.light01[2]) : half8{};
 		#pragma unroll 1
 		for (int b = 0; b < 2; ++b) {
@@ -1148,193 +1150,104 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void render_kernel(const DeviceMod
 // (An attribute argument cannot depend on a template parameter, hence a second entry point rather than a template flag.)
 // Scheduled for TWO waves per SIMD measured +-0 on the lego scenes and +1 % on the garden frame (profiles/r06/ab_c128_occ2_*.txt): the GATE instantiation takes that.
 template <int WAVES, bool PROF, bool POISSON, bool AFFINE, int TEAM, int NUM = 0, int XTRA = 0, bool BATCH = false>
-__global__ __launch_bounds__(64 * WAVES, XTRA == 6 ? 2 : 3) __attribute__((amdgpu_num_vgpr(128))) void render_kernel_c128(const DeviceModel m_arg, const RenderArgs a_arg) {
+__global__ __launch_bounds__(64 * WAVES, XTRA == kXtraGate ? 2 : 3) __attribute__((amdgpu_num_vgpr(128))) void render_kernel_c128(const DeviceModel m_arg, const RenderArgs a_arg) {
 	render_body<WAVES, 3, PROF, POISSON, AFFINE, TEAM, NUM, XTRA, BATCH>(m_arg, a_arg);
 }
 #ifndef NRS_BODY_ONLY // (tools/one_kernel.sh compiles ONE explicit instantiation of render_kernel for register work: everything below is left out)
-// The precondition of every render launch: nrs_render_nerf sized the packets (a.team, tile_geometry) and launch_render picked the instantiation from flags of
-// its own -- the two must agree, or packet_pixel lays out pixels with another packet shape than the launch was sized for and writes past a tiled frame.
-// A route that fails it is refused (NRS_ERR_STATE) and nothing is launched.
-// route_name: the instantiation as the NRS_KERNEL_LOG line names it (occ < 0: the 128-register entry point render_kernel_c128, which has no OCC argument)
+// The precondition of every render launch: the packets were sized (a.team, tile_geometry) for the TEAM of the row that is launched.  Both come from one plan
+// (nrs_route.h plan_route), so this should never fire -- it stays as the last guard because a mismatch makes packet_pixel lay out pixels with another packet
+// shape than the launch was sized for and write past a tiled frame.  A route that fails it is refused (NRS_ERR_STATE) and nothing is launched.
 static std::atomic<unsigned long long> g_render_dispatches{0}; // render-kernel dispatches of this process (launch_render_dispatches)
 unsigned long long launch_render_dispatches() { return g_render_dispatches.load(); }
-static void route_name(char* buf, size_t n, int waves, int occ, bool prof, bool poisson, bool affine, int team, int num, int extra, bool batch = false) {
-	char head[32];
-	if (occ < 0) snprintf(head, sizeof(head), "render_kernel_c128<%d", waves);
-	else snprintf(head, sizeof(head), "render_kernel<%d, %d", waves, occ);
-	snprintf(buf, n, "%s, prof %d, poisson %d, affine %d, team %d, num %d, extra %d%s>", head, (int)prof, (int)poisson, (int)affine, team, num, extra, batch ? ", batch" : "");
-}
-static int check_route(const DeviceModel& m, const RenderArgs& a, int waves, int occ, bool prof, bool poisson, bool affine, int team, int num, int extra, bool batch = false) {
+static int check_route(const DeviceModel& m, const RenderArgs& a, const RouteTraits& t, bool batch) {
 	const bool intro = a.p.render_mode == NRS_RENDER_NORMALS || a.p.render_mode == NRS_RENDER_ENCODING_VIS;
+	const XtraTraits x = xtra_traits(t.xtra);
 	const char* why = nullptr;
-	if ((int)a.team != team) why = "lanes per ray of the packet geometry (a.team) differ from TEAM";
-	else if (a.any_affine && !affine) why = "an AffineDuplication operator needs AFFINE";
-	else if (a.any_poisson && !poisson) why = "the membrane correction needs POISSON";
-	else if (num != kNumRuntime && (uint32_t)num != m.numerics) why = "NUM does not match the model's numerics";
-	else if ((m.n_extra_dims != 0u) != (extra == 7 || extra == 8)) why = "a network with light directions needs EXTRA 7 or 8 and only they";
-	else if ((a.extra != 0u) != ((extra >= 1 && extra <= 4) || extra == 8)) why = "a.extra needs EXTRA 1..4 (8 with light directions) and only it";
-	else if (extra != 8 && (m.rgb_deep != 0u) != (extra >= 3 && extra <= 5)) why = "a third rgb hidden layer needs EXTRA 3..5 and only it";
-	else if (extra == 6 && !a.gate) why = "EXTRA 6 (GATE) without a.gate";
-	else if (intro && extra != 2 && extra != 4 && extra != 8) why = "Normals / EncodingVis need EXTRA 2, 4 or 8";
-	else if (prof && !(a.dbg & 4u)) why = "PROF without NRS_DEBUG bit 2";
+	if ((int)a.team != t.team) why = "lanes per ray of the packet geometry (a.team) differ from TEAM";
+	else if (a.any_affine && !t.affine) why = "an AffineDuplication operator needs AFFINE";
+	else if (a.any_poisson && !t.poisson) why = "the membrane correction needs POISSON";
+	else if (t.num != kNumRuntime && (uint32_t)t.num != m.numerics) why = "NUM does not match the model's numerics";
+	else if ((m.n_extra_dims != 0u) != x.light) why = "a network with light directions needs EXTRA 7 or 8 and only they";
+	else if ((a.extra != 0u) != x.extra) why = "a.extra needs EXTRA 1..4 (8 with light directions) and only it";
+	else if (t.xtra != kXtraLightAll && (m.rgb_deep != 0u) != x.deep) why = "a third rgb hidden layer needs EXTRA 3..5 and only it";
+	else if (x.gate && !a.gate) why = "EXTRA 6 (GATE) without a.gate";
+	else if (intro && !x.intro) why = "Normals / EncodingVis need EXTRA 2, 4 or 8";
+	else if (t.prof && !(a.dbg & 4u)) why = "PROF without NRS_DEBUG bit 2";
 	else if (a.spp_count > 1u && !batch) why = "a batch of samples (spp_count > 1) needs BATCH";
 	else if (a.spp_count == 0u || a.spp_packets == 0u || a.n_packets != a.spp_count * a.spp_packets) why = "the queue is not spp_count times the packets of one sample";
 	if (!why) return NRS_OK;
 	char name[160];
-	route_name(name, sizeof(name), waves, occ, prof, poisson, affine, team, num, extra, batch);
+	route_name(name, sizeof(name), t, batch);
 	snprintf(g_launch_err, sizeof(g_launch_err), "launch_render: route refused: %s for team %u, affine %u, poisson %u, numerics %u, extra %u, deep %u, gate %u, render mode %u: %s",
 	         name, a.team, a.any_affine, a.any_poisson, m.numerics, a.extra, m.rgb_deep, a.gate, (uint32_t)a.p.render_mode, why);
 	return NRS_ERR_STATE;
 }
-static void log_route(int waves, int occ, bool prof, bool poisson, bool affine, int team, int num, int extra, bool batch = false) {
-	char name[160];
-	route_name(name, sizeof(name), waves, occ, prof, poisson, affine, team, num, extra, batch);
-	fprintf(stderr, "[nrs kernel] %s\n", name);
+// The launcher of row ROW of kRoutes (nrs_route.h): the kernel is instantiated from the row's traits.  BATCH: the twin that serves a queue of several samples
+// (render_body).  TWIN: the __launch_bounds__(512, 4) build of a row of the 128-register entry point, see below.
+template <int ROW, bool TWIN>
+constexpr RouteTraits launched_traits() {
+	constexpr RouteTraits R = kRoutes[ROW].t;
+	return {TWIN ? kEntryCfg : R.entry, R.waves, TWIN ? 4 : R.occ, R.prof, R.poisson, R.affine, R.team, R.num, R.xtra};
 }
-// BATCH (first, so that the other arguments keep their defaults): the twin of the instantiation that serves a queue of several samples (render_body).  launch_render
-// picks it for a.spp_count > 1 and only then: a single frame runs the kernel it always ran.
-template <bool BATCH, int WAVES, int OCC, bool PROF, bool POISSON, bool AFFINE, int TEAM, int NUM, int EXTRA>
-static int launch_render_cfg(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream);
-template <bool BATCH, int WAVES, bool PROF = false, bool POISSON = false, bool AFFINE = false, int TEAM = 1, int NUM = 0, int XTRA = 0>
-static int launch_render_c128(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream) {
-	{ const int rc = check_route(m, a, WAVES, -1, PROF, POISSON, AFFINE, TEAM, NUM, XTRA, BATCH); if (rc != NRS_OK) return rc; }
+template <int ROW, bool BATCH, bool TWIN>
+constexpr auto route_kernel() {
+	constexpr RouteTraits T = launched_traits<ROW, TWIN>();
+	if constexpr (T.entry == kEntryC128) return &render_kernel_c128<T.waves, T.prof, T.poisson, T.affine, T.team, T.num, T.xtra, BATCH>;
+	else return &render_kernel<T.waves, T.occ, T.prof, T.poisson, T.affine, T.team, T.num, T.xtra, BATCH>;
+}
+template <int ROW, bool BATCH, bool TWIN = false>
+static int launch_row(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream) {
+	constexpr RouteTraits T = launched_traits<ROW, TWIN>();
+	constexpr bool C128 = T.entry == kEntryC128;
+	constexpr auto kernel = route_kernel<ROW, BATCH, TWIN>();
+	{ const int rc = check_route(m, a, T, BATCH); if (rc != NRS_OK) return rc; }
 	int blocks_per_cu = 0;
-	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, render_kernel_c128<WAVES, PROF, POISSON, AFFINE, TEAM, NUM, XTRA, BATCH>, 64 * WAVES, 0);
-	if (e != hipSuccess) return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor(render_kernel_c128)");
+	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, 64 * T.waves, 0);
+	if (e != hipSuccess) return hip_fail(e, C128 ? "hipOccupancyMaxActiveBlocksPerMultiprocessor(render_kernel_c128)" : "hipOccupancyMaxActiveBlocksPerMultiprocessor(render_kernel)");
 	// amdgpu_num_vgpr is a target, not a limit: when the allocator went past 128 registers for this instantiation (3 waves per SIMD: 7.3 instead of 9.8
 	// Gsamples/s), the __launch_bounds__(512, 4) build of the same body -- which cannot -- is the one to launch
 	// (a batch twin that went past 128 runs where it is, at 3 waves per SIMD: no third build of the body for it)
-	// (the LIGHT twin, XTRA 7, has no third build either)
-	if constexpr (!BATCH && XTRA != 7) { if (blocks_per_cu * WAVES < 16) return launch_render_cfg<false, WAVES, 4, PROF, POISSON, AFFINE, TEAM, NUM, XTRA>(m, a, n_cus, stream); }
+	// (the LIGHT twin has no third build either)
+	if constexpr (C128 && !BATCH && T.xtra != kXtraLight) { if (blocks_per_cu * T.waves < 16) return launch_row<ROW, false, true>(m, a, n_cus, stream); }
 	if (blocks_per_cu < 1) blocks_per_cu = 1;
 	uint32_t grid = (uint32_t)(n_cus * blocks_per_cu);
-	const uint32_t max_useful = (a.n_packets + WAVES - 1) / WAVES; // at least one packet per wave
+	const uint32_t max_useful = (a.n_packets + T.waves - 1) / T.waves; // at least one packet per wave
 	if (grid > max_useful) grid = max_useful;
 	if (grid == 0) return NRS_OK;
 	static const bool log_kernel = dev_knob("NRS_KERNEL_LOG") != nullptr;
-	if (log_kernel) log_route(WAVES, -1, PROF, POISSON, AFFINE, TEAM, NUM, XTRA, BATCH);
-	hipLaunchKernelGGL((render_kernel_c128<WAVES, PROF, POISSON, AFFINE, TEAM, NUM, XTRA, BATCH>), dim3(grid), dim3(64 * WAVES), 0, stream, m, a);
+	if (log_kernel) {
+		char name[160];
+		route_name(name, sizeof(name), T, BATCH);
+		fprintf(stderr, "[nrs kernel] %s\n", name);
+	}
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * T.waves), 0, stream, m, a);
 	NRS_LAUNCH_CHECK("render_kernel launch");
 	++g_render_dispatches;
 	return NRS_OK;
 }
 
-template <bool BATCH, int WAVES, int OCC, bool PROF = false, bool POISSON = false, bool AFFINE = false, int TEAM = 1, int NUM = 0, int EXTRA = 0>
-static int launch_render_cfg(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t stream) {
-	{ const int rc = check_route(m, a, WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA, BATCH); if (rc != NRS_OK) return rc; }
-	static const bool log_kernel = dev_knob("NRS_KERNEL_LOG") != nullptr;
-	if (log_kernel) log_route(WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA, BATCH);
-	int blocks_per_cu = 0;
-	hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, render_kernel<WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA, BATCH>, 64 * WAVES, 0);
-	if (e != hipSuccess) return hip_fail(e, "hipOccupancyMaxActiveBlocksPerMultiprocessor(render_kernel)");
-	if (blocks_per_cu < 1) blocks_per_cu = 1;
-	uint32_t grid = (uint32_t)(n_cus * blocks_per_cu);
-	const uint32_t max_useful = (a.n_packets + WAVES - 1) / WAVES; // at least one packet per wave
-	if (grid > max_useful) grid = max_useful;
-	if (grid == 0) return NRS_OK;
-	hipLaunchKernelGGL((render_kernel<WAVES, OCC, PROF, POISSON, AFFINE, TEAM, NUM, EXTRA, BATCH>), dim3(grid), dim3(64 * WAVES), 0, stream, m, a);
-	NRS_LAUNCH_CHECK("render_kernel launch");
-	++g_render_dispatches;
-	return NRS_OK;
+// one row per row of kRoutes: its traits, its single-frame launcher, its batch-twin launcher (null where the row has none: the measurement rows)
+typedef int (*RouteLauncher)(const DeviceModel&, const RenderArgs&, int, hipStream_t);
+struct RouteLaunch { const RouteTraits* traits; RouteLauncher single, batch; };
+template <int ROW>
+static constexpr RouteLauncher batch_launcher() {
+	if constexpr (kRoutes[ROW].batch) return &launch_row<ROW, true>;
+	else return nullptr;
 }
+template <int... ROW>
+struct RouteLaunchTable { RouteLaunch row[sizeof...(ROW)] = {{&kRoutes[ROW].t, &launch_row<ROW, false>, batch_launcher<ROW>()}...}; };
+template <int... ROW>
+static RouteLaunchTable<ROW...> make_launch_table(std::integer_sequence<int, ROW...>) { return {}; }
+static const auto kLaunch = make_launch_table(std::make_integer_sequence<int, kRouteCount>{});
 
-int launch_render(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream) {
-	// launch shape: tuned default; NRS_RENDER_CFG = <waves per workgroup><waves per SIMD> (e.g. "84") overrides it for
-	// the A/B measurements recorded under profiles/
-	static const int cfg = []() {
-		const char* e = dev_knob("NRS_RENDER_CFG");
-		return e ? atoi(e) : 0;
-	}();
-	hipStream_t s = (hipStream_t)stream;
-	constexpr int R = kNumRuntime;
-	// a batch of samples runs the BATCH twin of the route a single frame takes; the measurement routes (the wave log's PROF twins, NRS_RENDER_CFG) serve single frames only
+int launch_render(RouteId row, const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream) {
 	const bool batch = a.spp_count > 1u;
-	if (batch && ((a.dbg & 4u) || cfg != 0)) {
-		snprintf(g_launch_err, sizeof(g_launch_err), "launch_render: route refused: the wave log (NRS_DEBUG bit 2) and NRS_RENDER_CFG have no instantiation for a batch of samples (spp_count %u)", a.spp_count);
+	const RouteLauncher fn = (int)row >= 0 && row < kRouteCount ? (batch ? kLaunch.row[row].batch : kLaunch.row[row].single) : nullptr;
+	if (!fn) {
+		snprintf(g_launch_err, sizeof(g_launch_err), "launch_render: route refused: row %d has no instantiation for spp_count %u", (int)row, a.spp_count);
 		return NRS_ERR_STATE;
 	}
-	#define NRS_ROUTE(fn, ...) (batch ? fn<true, __VA_ARGS__>(m, a, n_cus, s) : fn<false, __VA_ARGS__>(m, a, n_cus, s))
-	if (m.n_extra_dims) {
-		// light directions: the LIGHT twin of the default kernel, or the catch-all of such a network when a.extra is set (nrs_render_nerf decides, and refuses what neither
-		// serves; check_route turns away anything else that arrives here)
-		if (a.extra) return NRS_ROUTE(launch_render_cfg, 12, 3, false, false, true, 1, R, 8);
-		return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0, 0, 7);
-	}
-	if (a.extra) // render modes / show_accel / depth of field: the catch-all instantiation (every operator kind, membrane correction, one lane per ray)
-	{
-		// Normals / EncodingVis: the INTRO instantiation (145 / 165 VGPRs, no scratch: 12-wave workgroups at 3 waves per SIMD like the other modes)
-		const bool intro = a.p.render_mode == NRS_RENDER_NORMALS || a.p.render_mode == NRS_RENDER_ENCODING_VIS;
-		// (round 6: the common case -- a render mode / DoF / envmap / glow over plain cage edits or none, default roundings -- has a lean instantiation without the membrane and
-		// AffineDuplication code: 123 VGPRs on the 128-register entry point, 8-wave workgroups, 4 waves per SIMD instead of the catch-all's 145 at 3)
-		if (!intro && !m.rgb_deep && !m.numerics && !a.any_poisson && !a.any_affine && a.team == 1 && !(a.dbg & 4u) && cfg == 0) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 1, 0, 1);
-		if (m.rgb_deep) { // a network whose rgb MLP has a third hidden layer (base_3layer.json): the DEEP twins of the two catch-all instantiations, every mode
-			if (intro) return m.numerics ? NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, R, 4) : NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, 0, 4);
-			return m.numerics ? NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, R, 3) : NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, 0, 3);
-		}
-		if (intro)
-			return m.numerics ? NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, R, 2) : NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, 0, 2);
-		return m.numerics ? NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, R, 1) : NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, 0, 1);
-	}
-	if (m.rgb_deep) return NRS_ROUTE(launch_render_cfg, 8, 4, false, false, false, 0, 0, 5); // (nrs_render_nerf sends only the plain case here: a.team == 0, default roundings)
-	// cone-stepping scenes (aabb_scale > 1): the plain automatic schedule with the L2 phase gate (nrs_render_nerf sets a.gate for plain frames only; NRS_L2_GATE=0: A/B)
-	// (the entry point scheduled for 3 waves per SIMD and held to 128 registers, like the default kernel's: knee 4.99 -> 5.09, 64 GiB 5.34 -> 5.37 Gsamples/s, profiles/r06/ab_gate_c128_*.txt)
-	if (a.gate && !m.numerics && !a.any_poisson && !a.any_affine && a.team == 0 && !(a.dbg & 4u) && cfg == 0) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0, 0, 6);
-	if (m.numerics) { // tiny-cuda-nn's other roundings: the run-time twin of every schedule (nrs_render_nerf computed the packet geometry for a.team)
-		// ... except the pair a parity-minded integrator switches on -- per-corner fp16 grid accumulation + fp16 MLP accumulators, what tiny-cuda-nn's
-		// kernel_grid and fully fused MLP do as recalled -- on the automatic schedule: a compile-time instantiation like NUM = 0 (VERDICT r3 weak #1:
-		// the run-time twin carries both flavours, 131 VGPRs = 3 waves per SIMD)
-		if (!a.any_poisson && !a.any_affine && a.team == 0 && !(a.dbg & 4u) && cfg == 0) {
-			if ((m.numerics & 3u) == 3u) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0, 3);
-			// (round 6: one of the two roundings alone -- per-corner fp16 grid accumulation, or fp16 MLP accumulators -- has its compile-time instantiation too:
-			// 125 / 123 VGPRs at 4 waves per SIMD instead of the run-time twin's 131 at 3)
-			if ((m.numerics & 3u) == 1u) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0, 1);
-			if ((m.numerics & 3u) == 2u) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0, 2);
-		}
-		if (a.any_poisson) return NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true, 1, R);
-		if (a.any_affine) return NRS_ROUTE(launch_render_cfg, 8, 3, false, false, true, 1, R);
-		if (a.team == 0) return NRS_ROUTE(launch_render_cfg, 8, 3, false, false, false, 0, R);
-		if (a.team == 2) return NRS_ROUTE(launch_render_cfg, 8, 3, false, false, false, 2, R);
-		if (a.team == 4) return NRS_ROUTE(launch_render_cfg, 8, 3, false, false, false, 4, R);
-		return NRS_ROUTE(launch_render_cfg, 8, 3, false, false, false, 1, R);
-	}
-	// membrane correction: 142 VGPRs, no scratch, 3 waves per SIMD (the SH9 colour loop is kept rolled for that: unrolled it held 108 coefficient loads
-	// in flight, 250 VGPRs, 2 waves per SIMD: 6.1 Gsamples/s on the bench's lego_cage_membrane)
-	// (12-wave workgroups: at 3 waves per SIMD a CU holds 12 waves, i.e. ONE 8-wave workgroup and a half -- the first r03 profile showed 256 workgroups,
-	// 2 waves per SIMD; one 768-thread workgroup per CU uses all three)
-	// Round 4: with the membrane terms evaluated BEHIND the main network pass (render_body) a POISSON-only instantiation fits the default launch shape
-	// (8-wave workgroups, 128 VGPRs, 4 waves per SIMD) and runs the automatic schedule -- generations sized by the pending rays, re-teaming, ray hand-over
-	// (a.team == 0: nrs_render_nerf chose it because no edit is an AffineDuplication).  The catch-all stays for mixed operator lists.
-	if (a.any_poisson && !a.any_affine && a.team == 0) {
-		if (cfg == 124) return launch_render_cfg<false, 12, 3, false, true, false, 0>(m, a, n_cus, s); // (A/B: one 12-wave workgroup per CU at 3 waves per SIMD, 136 VGPRs, no scratch)
-		return NRS_ROUTE(launch_render_cfg, 8, 4, false, true, false, 0);
-	}
-	if (a.any_poisson) return NRS_ROUTE(launch_render_cfg, 12, 3, false, true, true);
-	// the wave log (NRS_DEBUG bit 2) has PROF twins of the default kernel for the automatic schedule and one lane per ray only: AffineDuplication and fixed
-	// 2 / 4 lanes per ray run their production instantiation below with an empty log
-	if ((a.dbg & 4u) && !a.any_affine && (a.team == 0 || a.team == 1))
-		return a.team == 0 ? launch_render_cfg<false, 8, 4, true, false, false, 0>(m, a, n_cus, s) : launch_render_cfg<false, 8, 4, true>(m, a, n_cus, s);
-	// Production instantiations: scheduled for 3 waves/SIMD, capped at 128 VGPRs = 4 waves/SIMD (render_kernel_c128).  Measured against the
-	// __launch_bounds__(512, 4) build of the same code (NRS_RENDER_CFG=84): 1080p lego + cage 9.43 -> 9.82 Gsamples/s, lego 10.7 -> 11.0,
-	// varied-opacity scene 7.65 -> 7.89, aabb-16 4.35 -> 4.72.  (Plain __launch_bounds__(512, 3), round 1's choice, now lets the allocator
-	// take 131 VGPRs = 3 waves/SIMD: 7.3.)
-	if (cfg == 84) {
-		if (a.any_affine) return a.team == 0 ? launch_render_cfg<false, 8, 4, false, false, true, 0>(m, a, n_cus, s) : launch_render_cfg<false, 8, 4, false, false, true>(m, a, n_cus, s);
-		if (a.team == 0) return launch_render_cfg<false, 8, 4, false, false, false, 0>(m, a, n_cus, s);
-		if (a.team == 2) return launch_render_cfg<false, 8, 4, false, false, false, 2>(m, a, n_cus, s);
-		if (a.team == 4) return launch_render_cfg<false, 8, 4, false, false, false, 4>(m, a, n_cus, s);
-		return launch_render_cfg<false, 8, 4>(m, a, n_cus, s);
-	}
-	// (the 10-wave / 5-waves-per-SIMD probe of rounds 1-3, NRS_RENDER_CFG=105, left the library in round 4: it spilled 77 registers at 96 VGPRs and, with the
-	// two selection fragments in the LDS image, ten waves no longer fit the LDS budget of two workgroups per CU either)
-	if (cfg == 42 && a.team == 1 && !a.any_affine) return launch_render_cfg<false, 4, 2>(m, a, n_cus, s);
-	// AffineDuplication (alone or with cage edits, no membrane correction, default roundings) on the automatic schedule since round 6 (nrs_render_nerf: a.team == 0)
-	if (a.any_affine && a.team == 0) return NRS_ROUTE(launch_render_c128, 8, false, false, true, 0); // (121 VGPRs on the 128-register entry point)
-	if (a.any_affine) return NRS_ROUTE(launch_render_cfg, 8, 4, false, false, true); // (its c128 build takes 133 VGPRs: the attribute is a target, not a limit)
-	if (a.team == 0) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 0);
-	if (a.team == 2) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 2);
-	if (a.team == 4) return NRS_ROUTE(launch_render_c128, 8, false, false, false, 4);
-	return NRS_ROUTE(launch_render_c128, 8);
-	#undef NRS_ROUTE
+	return fn(m, a, n_cus, (hipStream_t)stream);
 }
 
 // per-workgroup LDS of the kernels that run the network on caller batches: the weights + one feature slab per wave

@@ -895,7 +895,6 @@ __device__ __forceinline__ void level_input_gradient(const GridView& gv, const L
 
 // tiny-cuda-nn's roundings as a template value: NUM >= 0 fixes them at compile time (bit 0 grid accumulation in network precision, bit 1 fp16 MLP
 // accumulators), kNumRuntime reads them from `nm` (DeviceModel::numerics, wave-uniform) -- both flavours compiled in, one scalar branch.
-constexpr int kNumRuntime = -1;
 template <int NUM, bool QUADS = false, bool ZERO = true, int GATE = 0>
 __device__ __forceinline__ void encode_num(uint32_t nm, const GridView& gv, const LevelParams* __restrict__ lv, const ModelLds& ml, FeatLds& fl, int lane, int g, f3 pos, bool act) {
 	if (NUM == kNumRuntime ? (nm & 1u) != 0u : (NUM & 1) != 0) encode_to_lds<true, QUADS, ZERO, GATE>(gv, lv, ml, fl, lane, g, pos, act);

@@ -1,9 +1,10 @@
 """Every render route x every schedule x whole image and tiles.
 
-nrs_render_nerf sizes a launch (a.team: 0 = automatic schedule, 1 / 2 / 4 = fixed lanes per ray; the packet / tile geometry) and launch_render then picks
-one of ~30 render_kernel instantiations from flags of its own (TEAM, POISSON, AFFINE, NUM, EXTRA).  When the two disagree, packet_pixel lays out pixels
-with another packet shape than the host sized the launch for: whole images come out right with wasted packets, a tiled launch writes past its compact
-buffers.  launch_render's route check (nrs_kernels.hip check_route) refuses such a launch; these tests render every route the library has --
+plan_route (nrs_route.h) picks one row of the table of ~40 render_kernel instantiations (TEAM, POISSON, AFFINE, NUM, EXTRA) and nrs_render_nerf sizes the
+launch from that row (a.team: 0 = automatic schedule, 1 / 2 / 4 = fixed lanes per ray; the packet / tile geometry).  Were the packets sized for another TEAM
+than the kernel's, packet_pixel would lay out pixels with another packet shape than the launch was sized for: whole images come out right with wasted
+packets, a tiled launch writes past its compact buffers.  The last guard (nrs_kernels.hip check_route) refuses such a launch, and tests/test_route_plan_host.py
+asks the same of every plan without a GPU; these tests render every route the library has --
 
   R1 no edit            R2 cage                 R3 cage + membrane (target 0 / 1)   R4 AffineDuplication (hide_original)   R5 cage + affine
   R6 membrane + affine  R7 numerics (1,1) + cage R8 numerics (1,0) / (0,1)         R9 numerics + cage + affine           R10 3-layer rgb (DEEP) + cage
@@ -62,12 +63,12 @@ ROUTES = {
     "R20_deep_num11_normals": dict(rig="rgb3", edits=("cage",), numerics=(1, 1), fields={"render_mode": NORMALS}),
 }
 
-# Every instantiation launch_render (nrs_kernels.hip) can reach without development knobs, as its NRS_KERNEL_LOG line names it.  Entries on the 128-register
+# Every instantiation plan_route (nrs_route.h) can reach without development knobs, as its NRS_KERNEL_LOG line names it.  Entries on the 128-register
 # entry point (render_kernel_c128) fall back to their __launch_bounds__(512, 4) twin render_kernel<8, 4, ...> when the register allocator went past 128
 # VGPRs: either name is accepted for those, and the test reports which one ran.
 C128 = "render_kernel_c128<8, prof {p}, poisson {q}, affine {a}, team {t}, num {n}, extra {x}>"
 CFG = "render_kernel<{w}, {o}, prof {p}, poisson {q}, affine {a}, team {t}, num {n}, extra {x}>"
-R = -1  # kNumRuntime (nrs_mlp.cuh): the run-time numerics twin, printed as its value
+R = -1  # kNumRuntime (nrs_route.h): the run-time numerics twin, printed as its value
 REACHABLE_C128 = [  # (poisson, affine, team, num, extra)
     (0, 0, 0, 0, 0), (0, 0, 1, 0, 0), (0, 0, 2, 0, 0), (0, 0, 4, 0, 0),    # the default kernel: automatic schedule, fixed 1 / 2 / 4 lanes per ray
     (0, 1, 0, 0, 0),                                                       # AffineDuplication, automatic schedule
@@ -353,7 +354,7 @@ def test_affine_with_forced_lane_teams_on_tiles(rigs):
 @pytest.mark.gpu
 def test_every_reachable_instantiation_is_rendered(tmp_path):
     """the matrix's renders in a child process with the kernel log on (NRS_DEV_KNOBS=1 NRS_KERNEL_LOG=1 in its environment only): the set of
-    instantiations launched equals the list above of every instantiation launch_render can reach without development knobs -- a route added
+    instantiations launched equals the list above of every instantiation plan_route can reach without development knobs -- a route added
     without a test here fails this"""
     env = dict(os.environ, NRS_DEV_KNOBS="1", NRS_KERNEL_LOG="1")
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "route_worker.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
