@@ -1061,12 +1061,6 @@ int nrs_hashgrid_encode(nrs_model* m, void* stream, uint32_t n, const float* d_i
 
 // ---- edit operators ------------------------------------------------------------------------------------------------
 // ---- device-side tet LUT (nrs_cage.hip) ------------------------------------------------------------------------------
-#define CAGE_TRY(expr)                                                     \
-	do {                                                                   \
-		int st_ = (expr);                                                  \
-		if (st_ != NRS_OK) { g_err = cage_last_error(); return st_; }      \
-	} while (0)
-
 static int ensure_build_scratch(nrs_edit* e) {
 	const size_t n_cells = (size_t)kGridVol * kCascades;
 	if (!e->d_counts) {
@@ -1090,7 +1084,7 @@ static int build_lut_on_device(nrs_edit* e, const float* d_verts, uint8_t* d_bit
 		const double side = std::cbrt(vol / std::max<double>(e->n_tets / 6.0, 1.0)) * kGrid;
 		cells0 = (float)((side + 1.0) * (side + 1.0) * (side + 1.0));
 	}
-	CAGE_TRY(launch_lut_count_scan(e->n_tets, d_verts, e->de.tets, e->d_counts, e->d_tile_sums, e->d_lut_off, e->d_scratch + 6, e->d_hit_masks, cells0, s));
+	NRS_TRY(launch_lut_count_scan(e->n_tets, d_verts, e->de.tets, e->d_counts, e->d_tile_sums, e->d_lut_off, e->d_scratch + 6, e->d_hit_masks, cells0, s));
 	uint32_t total = 0;
 	HIP_TRY(hipMemcpyAsync(&total, e->d_scratch + 6, 4, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
@@ -1106,7 +1100,7 @@ static int build_lut_on_device(nrs_edit* e, const float* d_verts, uint8_t* d_bit
 		e->lut_idx_cap = cap;
 		e->de.lut_idx = fresh;
 	}
-	CAGE_TRY(launch_lut_fill(e->n_tets, d_verts, e->de.tets, e->d_counts, e->d_lut_off, e->d_lut_idx, d_bitfield_out, e->d_scratch + 7, e->d_big_cells, lut_big_list_capacity(e->lut_idx_cap), e->d_hit_masks, cells0, s));
+	NRS_TRY(launch_lut_fill(e->n_tets, d_verts, e->de.tets, e->d_counts, e->d_lut_off, e->d_lut_idx, d_bitfield_out, e->d_scratch + 7, e->d_big_cells, lut_big_list_capacity(e->lut_idx_cap), e->d_hit_masks, cells0, s));
 	e->lut_n_idx = total;
 	return NRS_OK;
 }
@@ -1123,7 +1117,7 @@ static int build_fine_lut(nrs_edit* e, hipStream_t s) {
 	if (off) return NRS_OK;
 	if (!e->d_fine_win) HIP_TRY(hipMalloc((void**)&e->d_fine_win, (kCascades * 8 + 8) * 4));
 	if (!e->d_fine_tiles) HIP_TRY(hipMalloc((void**)&e->d_fine_tiles, kFineScanTiles * 4));
-	CAGE_TRY(launch_fine_window(de.lut_off, e->d_fine_win, s));
+	NRS_TRY(launch_fine_window(de.lut_off, e->d_fine_win, s));
 	int32_t win[kCascades * 8];
 	HIP_TRY(hipMemcpyAsync(win, e->d_fine_win, sizeof(win), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
@@ -1161,7 +1155,7 @@ static int build_fine_lut(nrs_edit* e, hipStream_t s) {
 		HIP_TRY(hipMalloc((void**)&e->d_fine_counts, cap * 4));
 		e->fine_cells_cap = cap;
 	}
-	CAGE_TRY(launch_fine_count_scan(de, n_cells, e->d_fine_counts, e->d_fine_tiles, e->d_fine_off, (uint32_t*)e->d_fine_win + kCascades * 8, s));
+	NRS_TRY(launch_fine_count_scan(de, n_cells, e->d_fine_counts, e->d_fine_tiles, e->d_fine_off, (uint32_t*)e->d_fine_win + kCascades * 8, s));
 	uint32_t n_idx = 0;
 	HIP_TRY(hipMemcpyAsync(&n_idx, e->d_fine_win + kCascades * 8, 4, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
@@ -1173,7 +1167,7 @@ static int build_fine_lut(nrs_edit* e, hipStream_t s) {
 		HIP_TRY(hipMalloc((void**)&e->d_fine_idx, cap * 4));
 		e->fine_idx_cap = cap;
 	}
-	CAGE_TRY(launch_fine_fill(de, n_cells, e->d_fine_off, e->d_fine_idx, s));
+	NRS_TRY(launch_fine_fill(de, n_cells, e->d_fine_off, e->d_fine_idx, s));
 	e->fine_n_idx = n_idx;
 	de.fine_off = e->d_fine_off;
 	de.fine_idx = e->d_fine_idx;
@@ -1185,10 +1179,10 @@ static int build_fine_lut(nrs_edit* e, hipStream_t s) {
 // everything that follows new deformed vertices in e->d_verts: bbox, LUT, rotations.  Synchronous.
 static int rebuild_after_vertices(nrs_edit* e, hipStream_t s, bool build_fine_now = false) {
 	NRS_TRY(ensure_build_scratch(e));
-	CAGE_TRY(launch_bbox(e->n_vertices, e->d_verts, (float*)e->d_scratch, s));
+	NRS_TRY(launch_bbox(e->n_vertices, e->d_verts, (float*)e->d_scratch, s));
 	NRS_TRY(build_lut_on_device(e, e->d_verts, nullptr, s));
-	if (e->d_rot) CAGE_TRY(launch_local_rotations(e->n_tets, e->d_verts, e->de.orig, e->de.tets, e->d_rot, s));
-	CAGE_TRY(launch_tet_planes(e->n_tets, e->d_verts, e->de.tets, e->d_planes, s));
+	if (e->d_rot) NRS_TRY(launch_local_rotations(e->n_tets, e->d_verts, e->de.orig, e->de.tets, e->d_rot, s));
+	NRS_TRY(launch_tet_planes(e->n_tets, e->d_verts, e->de.tets, e->d_planes, s));
 	if (build_fine_now) NRS_TRY(build_fine_lut(e, s));
 	else { // (see nrs_edit::fine_stale)
 		e->de.fine_off = nullptr;
@@ -1294,7 +1288,7 @@ int nrs_edit_create(nrs_ctx* ctx, const nrs_model_desc* desc, const nrs_tet_mesh
 		de.lut_idx = e->d_lut_idx;
 		{
 			int st = launch_tet_planes(e->n_tets, e->d_verts, de.tets, e->d_planes, nullptr);
-			if (st != NRS_OK) return bail((g_err = cage_last_error(), st));
+			if (st != NRS_OK) return bail((g_err = launch_last_error(), st));
 			if (hipDeviceSynchronize() != hipSuccess) return bail(fail(NRS_ERR_HIP, "nrs_edit_create: tet_planes_kernel failed"));
 		}
 		{ // (the fine look-up table of the LUT that was handed over)
@@ -1306,7 +1300,7 @@ int nrs_edit_create(nrs_ctx* ctx, const nrs_model_desc* desc, const nrs_tet_mesh
 			if (he != hipSuccess) return bail(fail_hip(he, "nrs_edit_create: rotation upload"));
 		} else if (want_rot) {
 			int st = launch_local_rotations(e->n_tets, e->d_verts, de.orig, de.tets, e->d_rot, nullptr);
-			if (st != NRS_OK) return bail((g_err = cage_last_error(), st));
+			if (st != NRS_OK) return bail((g_err = launch_last_error(), st));
 			if (hipDeviceSynchronize() != hipSuccess) return bail(fail(NRS_ERR_HIP, "nrs_edit_create: rotation kernel failed"));
 		}
 	} else {
@@ -1406,7 +1400,7 @@ int nrs_edit_update_cage(nrs_edit* e, void* stream, const float* h_cage_vertices
 	HIP_TRY(hipSetDevice(e->ctx->device));
 	hipStream_t s = (hipStream_t)stream;
 	HIP_TRY(hipMemcpyAsync(e->d_cage, h_cage_vertices, (size_t)n_cage_vertices * 12, hipMemcpyHostToDevice, s));
-	CAGE_TRY(launch_mvc_apply(e->n_vertices, e->n_cv, e->d_mvc, e->d_cage, e->d_verts, s));
+	NRS_TRY(launch_mvc_apply(e->n_vertices, e->n_cv, e->d_mvc, e->d_cage, e->d_verts, s));
 	return rebuild_after_vertices(e, s);
 }
 // GrowingSelection::interpolate_poisson_boundary (growing_selection.cu:2350-2395): the link between nrs_poisson_boundary (per CAGE vertex) and the
@@ -1451,7 +1445,7 @@ int nrs_edit_poisson_interpolate(nrs_edit* e, void* stream, const float* h_gamma
 	}
 	const int rc = launch_poisson_interpolate(e->n_vertices, n_cage_vertices, h_gamma ? d_gamma : e->d_mvc, d_per_cage, (float*)e->de.shs, (float*)e->de.out_density,
 	                                          (float*)e->de.res_density, s);
-	if (rc != NRS_OK) { g_err = cage_last_error(); return bail(rc); }
+	if (rc != NRS_OK) { g_err = launch_last_error(); return bail(rc); }
 	if (hipStreamSynchronize(s) != hipSuccess) return bail(fail(NRS_ERR_HIP, "nrs_edit_poisson_interpolate: synchronise")); // the staging buffers are freed below
 	e->de.apply_poisson = 1u;
 	e->de.residual_amplitude = residual_amplitude;

@@ -13,21 +13,12 @@
 // box; the CSR scan streams the 42 MB count array twice.  Nothing here is GEMM-shaped.
 #include <hip/hip_runtime.h>
 #include "nrs_internal.h"
+#include "nrs_launch.h"
 #include "nrs_device.cuh"
 #include "nrs_svd3.h"
 
 namespace nrs {
 
-static thread_local char g_cage_err[512];
-const char* cage_last_error() { return g_cage_err; }
-#define NRS_CAGE_CHECK(what)                                                                          \
-	do {                                                                                              \
-		hipError_t e_ = hipGetLastError();                                                            \
-		if (e_ != hipSuccess) {                                                                       \
-			snprintf(g_cage_err, sizeof(g_cage_err), "%s: %s", what, hipGetErrorString(e_));          \
-			return NRS_ERR_HIP;                                                                       \
-		}                                                                                             \
-	} while (0)
 
 constexpr uint32_t kCells = kGridVol * kCascades;
 constexpr uint32_t kScanTile = 4096; // cells per scan block: 256 threads x 16
@@ -694,17 +685,17 @@ __global__ __launch_bounds__(256) void fine_lists_kernel(const DeviceEdit e, uin
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
 int launch_mvc_apply(uint32_t n_points, uint32_t n_cv, const float* d_weights, const float* d_cage, float* d_points, void* stream) {
 	hipLaunchKernelGGL(mvc_apply_kernel, dim3((n_points + 127) / 128), dim3(128), 0, (hipStream_t)stream, n_points, n_cv, d_weights, d_cage, d_points);
-	NRS_CAGE_CHECK("mvc_apply_kernel launch");
+	NRS_LAUNCH_CHECK("mvc_apply_kernel launch");
 	return NRS_OK;
 }
 int launch_poisson_interpolate(uint32_t n_points, uint32_t n_cv, const float* d_gamma, const float* d_per_cage, float* d_shs, float* d_out_density, float* d_res_density, void* stream) {
 	hipLaunchKernelGGL(poisson_interpolate_kernel, dim3((n_points + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_points, n_cv, d_gamma, d_per_cage, d_shs, d_out_density, d_res_density);
-	NRS_CAGE_CHECK("poisson_interpolate_kernel launch");
+	NRS_LAUNCH_CHECK("poisson_interpolate_kernel launch");
 	return NRS_OK;
 }
 int launch_bbox(uint32_t n, const float* d_verts, float* d_out6, void* stream) {
 	hipLaunchKernelGGL(bbox_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, d_verts, d_out6);
-	NRS_CAGE_CHECK("bbox_kernel launch");
+	NRS_LAUNCH_CHECK("bbox_kernel launch");
 	return NRS_OK;
 }
 // counts must be all zero on entry (it is again on exit of launch_lut_fill).  Writes offsets[kCells + 1] and *d_total.
@@ -715,7 +706,7 @@ int launch_lut_count_scan(uint32_t n_tets, const float* d_verts, const uint32_t*
 	hipLaunchKernelGGL(scan_tile_sum_kernel, dim3(kScanTiles), dim3(256), 0, s, d_counts, d_tile_sums);
 	hipLaunchKernelGGL(scan_tile_prefix_kernel, dim3(1), dim3(1024), 0, s, d_tile_sums, d_offsets + kCells, d_total, kScanTiles);
 	hipLaunchKernelGGL(scan_write_kernel, dim3(kScanTiles), dim3(256), 0, s, d_counts, d_tile_sums, d_offsets);
-	NRS_CAGE_CHECK("tet LUT count/scan launch");
+	NRS_LAUNCH_CHECK("tet LUT count/scan launch");
 	return NRS_OK;
 }
 // d_scratch_u32[0] = max tets per cell (out), [1] / [2] = counters of the two sort worklists; all zeroed here.  d_bitfield may be NULL.
@@ -723,24 +714,24 @@ int launch_lut_count_scan(uint32_t n_tets, const float* d_verts, const uint32_t*
 int launch_lut_fill(uint32_t n_tets, const float* d_verts, const uint32_t* d_tets, uint32_t* d_counts, const uint32_t* d_offsets, uint32_t* d_idx,
                     uint8_t* d_bitfield, uint32_t* d_scratch_u32, uint32_t* d_big_cells, uint32_t n_work, unsigned long long* d_hit_masks, float cells0, void* stream) {
 	hipStream_t s = (hipStream_t)stream;
-	if (hipMemsetAsync(d_scratch_u32, 0, 12, s) != hipSuccess) { snprintf(g_cage_err, sizeof(g_cage_err), "tet LUT fill: memset failed"); return NRS_ERR_HIP; }
+	if (hipMemsetAsync(d_scratch_u32, 0, 12, s) != hipSuccess) { snprintf(g_launch_err, sizeof(g_launch_err), "tet LUT fill: memset failed"); return NRS_ERR_HIP; }
 	launch_tet_mark<true>(n_tets, cells0, d_verts, d_tets, d_counts, d_offsets, d_idx, d_hit_masks, s);
 	hipLaunchKernelGGL(lut_finish_kernel, dim3(kCells / 256), dim3(256), 0, s, d_offsets, d_idx, d_bitfield, d_scratch_u32, d_big_cells,
 	                   d_scratch_u32 + 1, n_work);
 	hipLaunchKernelGGL(lut_sort_mid_kernel, dim3(512), dim3(1024), 0, s, d_offsets, d_idx, d_big_cells, d_scratch_u32 + 2, n_work);
 	hipLaunchKernelGGL(lut_sort_big_kernel, dim3(512), dim3(1024), 0, s, d_offsets, d_idx, d_big_cells, d_scratch_u32 + 1, n_tets);
-	NRS_CAGE_CHECK("tet LUT fill launch");
+	NRS_LAUNCH_CHECK("tet LUT fill launch");
 	return NRS_OK;
 }
 uint32_t lut_big_list_capacity(size_t idx_capacity) { return (uint32_t)(idx_capacity / kSmallList + 1); }
 int launch_tet_planes(uint32_t n_tets, const float* d_verts, const uint32_t* d_tets, float* d_planes, void* stream) {
 	hipLaunchKernelGGL(tet_planes_kernel, dim3((n_tets + 127) / 128), dim3(128), 0, (hipStream_t)stream, n_tets, d_verts, d_tets, d_planes);
-	NRS_CAGE_CHECK("tet_planes_kernel launch");
+	NRS_LAUNCH_CHECK("tet_planes_kernel launch");
 	return NRS_OK;
 }
 int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, void* stream) {
 	hipLaunchKernelGGL(local_rotations_kernel, dim3((n_tets + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_tets, d_verts, d_orig, d_tets, d_out);
-	NRS_CAGE_CHECK("local_rotations_kernel launch");
+	NRS_LAUNCH_CHECK("local_rotations_kernel launch");
 	return NRS_OK;
 }
 
@@ -748,9 +739,9 @@ int launch_fine_window(const uint32_t* d_lut_off, int32_t* d_window_out, void* s
 	hipStream_t s = (hipStream_t)stream;
 	static int32_t init[kCascades * 8];
 	for (uint32_t c = 0; c < kCascades; ++c) { int32_t* w = init + 8 * c; w[0] = w[1] = w[2] = 0x7fffffff; w[3] = w[4] = w[5] = -1; w[6] = w[7] = 0; }
-	if (hipMemcpyAsync(d_window_out, init, sizeof(init), hipMemcpyHostToDevice, s) != hipSuccess) { snprintf(g_cage_err, sizeof(g_cage_err), "fine look-up table: window init failed"); return NRS_ERR_HIP; }
+	if (hipMemcpyAsync(d_window_out, init, sizeof(init), hipMemcpyHostToDevice, s) != hipSuccess) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: window init failed"); return NRS_ERR_HIP; }
 	hipLaunchKernelGGL(fine_window_kernel, dim3(kCells / 16 / 256), dim3(256), 0, s, d_lut_off, d_window_out);
-	NRS_CAGE_CHECK("fine_window_kernel launch");
+	NRS_LAUNCH_CHECK("fine_window_kernel launch");
 	return NRS_OK;
 }
 template <bool FILL>
@@ -766,19 +757,19 @@ static void launch_fine_lists(const DeviceEdit& de, uint32_t* d_counts, const ui
 int launch_fine_count_scan(const DeviceEdit& de, uint32_t n_fine_cells, uint32_t* d_counts, uint32_t* d_tile_sums, uint32_t* d_fine_off, uint32_t* d_total, void* stream) {
 	hipStream_t s = (hipStream_t)stream;
 	const uint32_t n_tiles = (n_fine_cells + kScanTile - 1) / kScanTile, n_padded = n_tiles * kScanTile;
-	if (n_tiles == 0 || n_tiles > kMaxScanTiles) { snprintf(g_cage_err, sizeof(g_cage_err), "fine look-up table: %u fine cells", n_fine_cells); return NRS_ERR_INVALID_ARG; }
-	if (n_padded != n_fine_cells && hipMemsetAsync(d_counts + n_fine_cells, 0, (size_t)(n_padded - n_fine_cells) * 4, s) != hipSuccess) { snprintf(g_cage_err, sizeof(g_cage_err), "fine look-up table: memset failed"); return NRS_ERR_HIP; }
+	if (n_tiles == 0 || n_tiles > kMaxScanTiles) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: %u fine cells", n_fine_cells); return NRS_ERR_INVALID_ARG; }
+	if (n_padded != n_fine_cells && hipMemsetAsync(d_counts + n_fine_cells, 0, (size_t)(n_padded - n_fine_cells) * 4, s) != hipSuccess) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: memset failed"); return NRS_ERR_HIP; }
 	launch_fine_lists<false>(de, d_counts, nullptr, nullptr, s);
 	hipLaunchKernelGGL(scan_tile_sum_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums);
 	hipLaunchKernelGGL(scan_tile_prefix_kernel, dim3(1), dim3(1024), 0, s, d_tile_sums, d_fine_off + n_padded, d_total, n_tiles);
 	hipLaunchKernelGGL(scan_write_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums, d_fine_off);
-	NRS_CAGE_CHECK("fine look-up table count/scan launch");
+	NRS_LAUNCH_CHECK("fine look-up table count/scan launch");
 	return NRS_OK;
 }
 int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t* d_fine_off, uint32_t* d_fine_idx, void* stream) {
 	(void)n_fine_cells;
 	launch_fine_lists<true>(de, nullptr, d_fine_off, d_fine_idx, (hipStream_t)stream);
-	NRS_CAGE_CHECK("fine_lists_kernel launch");
+	NRS_LAUNCH_CHECK("fine_lists_kernel launch");
 	return NRS_OK;
 }
 

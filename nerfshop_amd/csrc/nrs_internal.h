@@ -1,4 +1,4 @@
-// nrs_internal.h -- PODs shared between the C++ host code (nrs_api.cpp) and the HIP kernels (nrs_kernels.hip).
+// nrs_internal.h -- PODs shared between the C++ host code (nrs_api.cpp) and the HIP kernels (nrs_render*.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip, nrs_cage.hip).
 // Nothing here is part of the public ABI (that is include/nrs.h).
 #pragma once
 #include <stdint.h>
@@ -193,7 +193,7 @@ struct RenderArgs {
 	unsigned long long* wave_log; // NRS_DEBUG & 4: 4 words per wave (see nrs_render_nerf)
 };
 
-// kernel launchers (nrs_kernels.hip).  stream is a hipStream_t.
+// kernel launchers (nrs_render.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip).  stream is a hipStream_t.
 // launches row `row` of kRoutes (nrs_route.h; the caller planned it: plan_route), or its batch twin when a.spp_count > 1
 int launch_render(RouteId row, const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
 unsigned long long launch_render_dispatches(); // render-kernel dispatches of this process so far (nrs_ctx_render_launches counts with it)
@@ -274,7 +274,6 @@ int launch_fine_window(const uint32_t* d_lut_off, int32_t* d_window_out, void* s
 int launch_fine_count_scan(const DeviceEdit& de, uint32_t n_fine_cells, uint32_t* d_counts, uint32_t* d_tile_sums, uint32_t* d_fine_off, uint32_t* d_total, void* stream);
 int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t* d_fine_off, uint32_t* d_fine_idx, void* stream);
 int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, void* stream);
-const char* cage_last_error();
 
 // The planner behind one C symbol (exported from libnrs.so, declared here only: not part of include/nrs.h): tests sweep it without a GPU.
 struct RouteProbe {

@@ -915,4 +915,13 @@ __device__ __forceinline__ half8 rgb_mlp_num(uint32_t nm, const half8* lds_w, in
 __device__ __forceinline__ float xchg32(float v) { return __shfl_xor(v, 32, 64); }
 __device__ __forceinline__ uint32_t xchg32u(uint32_t v) { return (uint32_t)__shfl_xor((int)v, 32, 64); }
 
+
+// per-workgroup LDS of the kernels that run the network on caller batches: the weights + one feature slab per wave
+template <int WAVES>
+struct NetSmemT {
+	ModelLds ml;
+	FeatLds fl[WAVES];
+};
+typedef NetSmemT<4> NetSmem;
+
 } // namespace nrs

@@ -1,5 +1,5 @@
 // nrs_route.h -- which render_kernel instantiation serves a frame, and with which schedule: the ONE place that knows.
-//   kRoutes      one row per instantiation the library reaches (nrs_kernels.hip instantiates the kernels and their launchers FROM this table)
+//   kRoutes      one row per instantiation the library reaches (nrs_render_rows.hip instantiates the kernels and their launchers FROM this table, nrs_render.hip the table of launchers)
 //   plan_route   a request (model, operators, parameters, context, development knobs) -> a refusal, or a row plus the schedule fields of RenderArgs
 // Host-only, plain C++17, no HIP types, no getenv, no statics: the planner is a pure function (tests/test_route_plan_host.py sweeps it without a GPU).
 #pragma once

@@ -1,0 +1,57 @@
+"""The library's Makefile rebuilds what an edit touches and nothing else: header dependencies come from the compiler (the .d files beside the objects), one object
+per subsystem, the render kernel's instantiations in shards of one source.  Dry runs only (`make -n -W <file>`: what WOULD be rebuilt if <file> were newer) -- nothing
+is compiled.  Runs after build(); skipped where there is no make or no finished build to ask."""
+import glob
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "nerfshop_amd", "csrc")
+
+
+def _rebuilt_if_touched(name):
+    """Objects (without .o) that make would recompile, and whether it would link libnrs.so, if csrc/<name> were newer than everything."""
+    if shutil.which("make") is None:
+        pytest.skip("no make on this machine")
+    deps = glob.glob(os.path.join(CSRC, "*.d"))
+    if not deps or not all(os.path.exists(d[:-2] + ".o") for d in deps) or not os.path.exists(os.path.join(CSRC, "libnrs.so")):
+        pytest.skip("no finished build beside the sources (.d files, their objects, libnrs.so): a dry run has nothing to compare with -- run build() first")
+    assert os.path.exists(os.path.join(CSRC, name)), name
+    up_to_date = subprocess.run(["make", "-n", "-C", CSRC], capture_output=True, text=True, check=True).stdout
+    assert " -o " not in up_to_date, "the build is not up to date: a dry run says nothing about one file\n" + up_to_date
+    out = subprocess.run(["make", "-n", "-W", name, "-C", CSRC], capture_output=True, text=True, check=True).stdout
+    objects = set(re.findall(r" -o (\S+)\.o\b", out))
+    return objects, re.search(r" -o libnrs\.so\b", out) is not None
+
+
+def _shards(objects):
+    return {o for o in objects if o.startswith("nrs_render_rows_")}
+
+
+def _all_shards():
+    n = int(subprocess.run(["make", "-s", "-C", CSRC, "--eval", "print-shards: ; @echo $(ROW_SHARDS)", "print-shards"], capture_output=True, text=True, check=True).stdout)
+    assert n >= 1
+    return {f"nrs_render_rows_{k}" for k in range(n)}
+
+
+def test_a_header_outside_any_hand_kept_list_reaches_its_includers():
+    objects, link = _rebuilt_if_touched("nrs_svd3.h")
+    assert objects == {"nrs_cage", "nrs_authoring"}, objects  # (and so neither the display object nor a render shard)
+    assert link
+
+
+def test_the_display_source_rebuilds_its_object_alone():
+    objects, link = _rebuilt_if_touched("nrs_display.hip")
+    assert objects == {"nrs_display"}, objects
+    assert link
+
+
+def test_the_render_kernel_header_rebuilds_every_shard_and_no_streaming_object():
+    objects, link = _rebuilt_if_touched("nrs_render.cuh")
+    assert _shards(objects) == _all_shards(), objects
+    assert not objects & {"nrs_display", "nrs_tables", "nrs_occupancy", "nrs_cage", "nrs_render", "nrs_api"}, objects
+    assert link

@@ -1,7 +1,7 @@
 """Short rays, saturated alpha and min_transmittance at its edges.
 
 Every other scene of the suite has default_sigma_raw's opacity (alpha ~ 0.14 per sample, ~26-33 samples per ray).  A trained snapshot lives where rays end
-within a few samples (VERDICT weak #4), and that is where lane teams end a ray at lane k < TEAM of a round (nrs_kernels.hip: the later samples of the round
+within a few samples (VERDICT weak #4), and that is where lane teams end a ray at lane k < TEAM of a round (nrs_render.cuh: the later samples of the round
 must be dropped).  Here the network's constant density channel is set for an opacity per sample of (synth.sigma_for_alpha)
 
   0.005   rays leave the box unsaturated (n* ~ 900 samples)        0.5    n* = ln(min_transmittance) / ln(1 - alpha) = 6.6 samples

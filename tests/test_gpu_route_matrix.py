@@ -3,7 +3,7 @@
 plan_route (nrs_route.h) picks one row of the table of ~40 render_kernel instantiations (TEAM, POISSON, AFFINE, NUM, EXTRA) and nrs_render_nerf sizes the
 launch from that row (a.team: 0 = automatic schedule, 1 / 2 / 4 = fixed lanes per ray; the packet / tile geometry).  Were the packets sized for another TEAM
 than the kernel's, packet_pixel would lay out pixels with another packet shape than the launch was sized for: whole images come out right with wasted
-packets, a tiled launch writes past its compact buffers.  The last guard (nrs_kernels.hip check_route) refuses such a launch, and tests/test_route_plan_host.py
+packets, a tiled launch writes past its compact buffers.  The last guard (nrs_render.hip check_route) refuses such a launch, and tests/test_route_plan_host.py
 asks the same of every plan without a GPU; these tests render every route the library has --
 
   R1 no edit            R2 cage                 R3 cage + membrane (target 0 / 1)   R4 AffineDuplication (hide_original)   R5 cage + affine

@@ -7,8 +7,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 INST="$1"; shift
 TMP=$(mktemp -d /tmp/one_kernel.XXXXXX)
 cat > "$TMP/k.hip" <<SRC
-#define NRS_BODY_ONLY 1
-#include "$ROOT/nerfshop_amd/csrc/nrs_kernels.hip"
+#include "$ROOT/nerfshop_amd/csrc/nrs_render.cuh"
 template __global__ void nrs::$INST(const nrs::DeviceModel, const nrs::RenderArgs);
 SRC
 OUT=/dev/null
