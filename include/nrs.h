@@ -570,8 +570,62 @@ int nrs_render_nerf_spp(nrs_model* model, const nrs_render_params* params, nrs_e
 int nrs_accumulate_spp(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count,
                        float* d_accumulate, uint32_t sample_count, uint32_t color_space);
 /* Introspection: render-kernel dispatches this context has enqueued so far (a batch of any size is one), and the schedule of the last one:
- * lanes per ray (0 = sized per generation) | lanes on a pixel during the fill << 8 | small-launch schedule << 16 | hybrid queue << 17 | BATCH twin << 18.  Either may be NULL. */
+ * lanes per ray (0 = sized per generation) | lanes on a pixel during the fill << 8 | small-launch schedule << 16 | hybrid queue << 17 | BATCH twin << 18 |
+ * a view per sample (nrs_render_nerf_spp_views) << 19.  Either may be NULL. */
 int nrs_ctx_render_launches(const nrs_ctx* ctx, uint64_t* n_dispatches_out, uint32_t* last_schedule_out);
+
+/* ---- a view per sample: motion-blurred frames of a moving camera in one launch ------------------------------------------------------------ */
+/* Testbed::render_to_cpu (src/python_api.cu:129-175) renders each of the `spp` samples of a frame with its own pair of cameras -- log_space_lerp of the frame's start and
+ * end camera at the sample's share of the shutter -- and, over a camera path, with its own fov, aperture and focus plane (set_camera_from_time per sample): the video loop
+ * of scripts/run.py.  Callers detect these entry points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.
+ *
+ * nrs_render_nerf_spp_views is nrs_render_nerf_spp with a view per sample: sample k renders as nrs_render_nerf does with `params` whose camera_matrix0 / camera_matrix1 /
+ * focal_length / dof / slice_plane_z are h_views[k]'s and whose spp_index is spp_index + k; slab k (frame, depth, steps) is bit-equal to that call's output and h_stats is
+ * the sum over the samples.  The six fields of `params` itself are not read.  h_views is a HOST array of spp_count records, copied inside the call (the caller may free it
+ * on return); the copy is ordered on `stream` and adds no synchronisation.  h_views == NULL is nrs_render_nerf_spp; spp_count == 1 is one nrs_render_nerf of that view.
+ * Refused like nrs_render_nerf_spp (the same code, the per-view fields checked for every view), and NRS_ERR_INVALID_ARG naming h_views[k].<field> for a non-finite value
+ * or a focal_length <= 0 in any view. */
+typedef struct nrs_sample_view {          /* what render_frame() receives per sample inside render_to_cpu's loop */
+	float camera_matrix0[12], camera_matrix1[12]; /* as in nrs_render_params */
+	float focal_length[2];
+	float dof;
+	float slice_plane_z;                  /* already m_slice_plane_z + m_scale, as in nrs_render_params */
+} nrs_sample_view;
+int nrs_render_nerf_spp_views(nrs_model* model, const nrs_render_params* params, nrs_edit* const* edits, int n_edits, uint32_t spp_count, const nrs_sample_view* h_views,
+                              float* d_frames, float* d_depths, uint32_t* d_steps, size_t slab_stride_pixels, void* stream, nrs_render_stats* h_stats);
+
+/* The cameras of render_to_cpu's loop: host-only functions (no GPU, no context).  The camera math is evaluated in double and rounded once to float: a restatement of the
+ * reference's formulas, not of Eigen's float evaluation of the matrix functions.  Camera matrices are 3x4 column-major [12], as everywhere in this header.
+ *
+ * nrs_log_space_lerp <- log_space_lerp (src/common_device.cu:27-36): exp(t * log(B * A^-1)) * A on the 4x4 completions of begin (A) and end (B).  begin == end returns it
+ *   exactly.  NRS_ERR_INVALID_ARG for a non-finite entry or a singular `begin`; NRS_ERR_UNSUPPORTED where B * A^-1 has no real logarithm the series can reach
+ *   (an eigenvalue on the negative real axis: a rotation by exactly 180 degrees).
+ * nrs_camera_keyframe <- CameraKeyframe (include/neural-graphics-primitives/camera_path.h:30-36); R is the quaternion (x, y, z, w).
+ * nrs_camera_keyframe_matrix <- CameraKeyframe::m() (:37-42): the normalised quaternion's rotation matrix beside T.
+ * nrs_camera_keyframe_from_matrix <- the constructor of :53 (Eigen's matrix -> quaternion conversion); slice / scale / fov / dof are copied from the arguments.
+ * nrs_camera_path_eval <- CameraPath::eval_camera_path (:74-81) and spline (src/camera_path.cu:50-68): the cubic B-spline over the four keyframes around t * (n - 1),
+ *   indices clamped, weights in float, p0 * a + p1 * b + p2 * c + p3 * d summed left to right with operator+'s sign flip of the right-hand quaternion (:55-59).
+ *   n == 0 returns the zero keyframe (a default-constructed one in the reference).
+ * nrs_camera_path_open / _count / _keyframes / _close <- CameraPath::load (src/camera_path.cu:114-136; load_relative_to_first = false): the
+ *   {"time", "path": [{"R", "T", "slice", "scale", "fov", "dof"}]} file CameraPath::save writes.  A missing "path" or an empty one gives zero keyframes; a keyframe without
+ *   one of its six keys is NRS_ERR_INVALID_ARG naming the key, as every unreadable file is.
+ * nrs_motion_views <- lines 148-158 of src/python_api.cu for samples i = first_sample .. first_sample + spp_count - 1 of spp_total: out_views[k].camera_matrix0 / 1 =
+ *   log_space_lerp(start, end, i / spp_total * shutter_fraction) / (..., (i + 1) / spp_total * shutter_fraction).  With n_keys > 0 and start_time >= 0 the keyframe at
+ *   start_time + (end_time - start_time) * (alpha0 + alpha1) / 2 gives focal_length (both axes fov_to_focal_length(1, fov) * resolution[fov_axis],
+ *   common_device.cuh:444-446 and Testbed::calc_focal_length with zoom 1), dof and slice_plane_z = slice + scale; otherwise they are base_view's. */
+typedef struct nrs_camera_keyframe { float R[4], T[3], slice, scale, fov, dof; } nrs_camera_keyframe;
+typedef struct nrs_camera_path nrs_camera_path;
+int nrs_log_space_lerp(const float begin[12], const float end[12], float t, float out[12]);
+int nrs_camera_keyframe_matrix(const nrs_camera_keyframe* key, float out[12]);
+int nrs_camera_keyframe_from_matrix(const float matrix[12], float slice, float scale, float fov, float dof, nrs_camera_keyframe* out);
+int nrs_camera_path_eval(const nrs_camera_keyframe* keys, uint32_t n_keys, float t, nrs_camera_keyframe* out);
+int nrs_camera_path_open(const char* path, nrs_camera_path** out);
+uint32_t nrs_camera_path_count(const nrs_camera_path* path);
+int nrs_camera_path_keyframes(const nrs_camera_path* path, nrs_camera_keyframe* out, uint32_t capacity);
+void nrs_camera_path_close(nrs_camera_path* path);
+int nrs_motion_views(const float start[12], const float end[12], float shutter_fraction, uint32_t spp_count, uint32_t first_sample, uint32_t spp_total,
+                     const int32_t resolution[2], int fov_axis, const nrs_camera_keyframe* keys, uint32_t n_keys, float start_time, float end_time,
+                     const nrs_sample_view* base_view, nrs_sample_view* out_views);
 
 /* ---- networks trained with light directions (n_extra_dims = 3) ----------------------------------------------------------------------- */
 /* dataset.has_light_dirs sets n_extra_dims = 3 (src/testbed.cu:2318): NerfNetworkFull builds the direction encoding over n_dir_dims + n_extra_dims inputs

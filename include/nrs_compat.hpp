@@ -5,10 +5,13 @@
 //   ngp::CageDeformation       include/neural-graphics-primitives/editing/edit_operator.h  -> nrs::compat::CageDeformation
 //   ngp::CudaRenderBuffer      include/neural-graphics-primitives/render_buffer.h:164      -> nrs::compat::RenderBuffer (view)
 //   ngp::Testbed::render_nerf  src/testbed_nerf.cu:3066                                    -> nrs::compat::Testbed::render_nerf
+//   ngp::Testbed::render_to_cpu src/python_api.cu:129-175                                  -> nrs::compat::Testbed::render_to_cpu (+ load_camera_path,
+//                                                                                             set_camera_from_time, apply_camera_smoothing)
 //
 // No Eigen / tiny-cuda-nn types: matrices are column-major float arrays (what Eigen::Matrix<float,3,4>::data() yields),
 // streams are passed as void* (hipStream_t), errors become std::runtime_error (the reference throws from CUDA_CHECK_THROW).
 #pragma once
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -247,21 +250,18 @@ public:
 		m_density_grid_update.reset_grid = 0;
 	}
 
-	// void Testbed::render_nerf(NerfNetwork<precision_t>&, CudaRenderBuffer&, const Vector2i& max_res, const Vector2f& focal_length,
-	//     const Matrix<float,3,4>& camera_matrix0, const Matrix<float,3,4>& camera_matrix1, const Vector4f& rolling_shutter,
-	//     const Vector2f& screen_center, bool apply_operators, cudaStream_t stream)              -- testbed.h:305
-	void render_nerf(NerfNetwork& network, RenderBuffer& render_buffer, const int /*max_res*/[2], const float focal_length[2],
-	                 const float camera_matrix0[12], const float camera_matrix1[12], const float rolling_shutter[4], const float screen_center[2],
-	                 bool apply_operators, void* stream, nrs_render_stats* stats = nullptr) {
+	// the nrs_render_params of a frame of this testbed: what render_nerf and render_to_cpu hand to the library
+	nrs_render_params make_params(int width, int height, uint32_t spp_index, const float focal_length[2], const float camera_matrix0[12], const float camera_matrix1[12],
+	                              const float rolling_shutter[4], const float screen_center[2], bool apply_operators) const {
 		nrs_render_params p{}; // = NRS_RENDER_PARAMS_INIT, spelled so that -Wextra stays quiet in C++
 		p.struct_size = (uint32_t)sizeof(nrs_render_params);
-		p.resolution[0] = render_buffer.width;
-		p.resolution[1] = render_buffer.height;
+		p.resolution[0] = width;
+		p.resolution[1] = height;
 		for (int i = 0; i < 2; ++i) { p.focal_length[i] = focal_length[i]; p.screen_center[i] = screen_center[i]; }
 		for (int i = 0; i < 12; ++i) { p.camera_matrix0[i] = camera_matrix0[i]; p.camera_matrix1[i] = camera_matrix1[i]; }
 		for (int i = 0; i < 4; ++i) p.rolling_shutter[i] = rolling_shutter[i];
 		for (int i = 0; i < 3; ++i) { p.render_aabb_min[i] = m_render_aabb_min[i]; p.render_aabb_max[i] = m_render_aabb_max[i]; }
-		p.spp_index = render_buffer.spp;
+		p.spp_index = spp_index;
 		p.snap_to_pixel_centers = m_snap_to_pixel_centers;
 		p.min_transmittance = m_nerf.rendering_min_transmittance;
 		p.cone_angle_constant = m_nerf.cone_angle_constant;
@@ -283,12 +283,154 @@ public:
 		p.glow_mode = (uint32_t)m_glow_mode;
 		p.glow_y_cutoff = m_glow_y_cutoff;
 		for (int i = 0; i < 2; ++i) { p.distortion_resolution[i] = m_distortion_resolution[i]; p.envmap_resolution[i] = m_envmap_resolution[i]; }
+		return p;
+	}
+
+	// void Testbed::render_nerf(NerfNetwork<precision_t>&, CudaRenderBuffer&, const Vector2i& max_res, const Vector2f& focal_length,
+	//     const Matrix<float,3,4>& camera_matrix0, const Matrix<float,3,4>& camera_matrix1, const Vector4f& rolling_shutter,
+	//     const Vector2f& screen_center, bool apply_operators, cudaStream_t stream)              -- testbed.h:305
+	void render_nerf(NerfNetwork& network, RenderBuffer& render_buffer, const int /*max_res*/[2], const float focal_length[2],
+	                 const float camera_matrix0[12], const float camera_matrix1[12], const float rolling_shutter[4], const float screen_center[2],
+	                 bool apply_operators, void* stream, nrs_render_stats* stats = nullptr) {
+		const nrs_render_params p = make_params(render_buffer.width, render_buffer.height, render_buffer.spp, focal_length, camera_matrix0, camera_matrix1, rolling_shutter,
+		                                        screen_center, apply_operators);
 		check(nrs_model_set_light_dir(network.get(), m_nerf.light_dir), "nrs_model_set_light_dir"); // (no effect on a network without extra dims)
 		std::vector<nrs_edit*> edits;
 		for (const EditOperator* op : m_edit_operators) edits.push_back(op->get());
 		check(nrs_render_nerf(network.get(), &p, edits.data(), (int)edits.size(), render_buffer.frame_buffer, render_buffer.depth_buffer, nullptr, stream,
 		                      stats),
 		      "nrs_render_nerf");
+	}
+
+	// ---- Testbed::render_to_cpu and the camera state it moves (src/python_api.cu:129-175, src/testbed.cu:2086-2111) ----
+	// m_windowless_render_surface: device arrays of the caller.  `frames` / `depths` hold n_slabs slabs, slab_stride_pixels apart (>= width * height), one per sample of a
+	// launch; the tonemapped image is left in d_out (nrs_tonemap_output_bytes) for the caller to copy to the host, where the reference copies its surface.
+	struct WindowlessSurface {
+		int width = 0, height = 0;
+		float* frames = nullptr;             // float4 [n_slabs][slab_stride_pixels]; the caller clears them (clear_frame, testbed.cu:2635)
+		float* depths = nullptr;             // float  [n_slabs][slab_stride_pixels]
+		size_t slab_stride_pixels = 0;
+		uint32_t n_slabs = 0;                // samples per launch: 1 .. NRS_SPP_BATCH_MAX
+		float* accumulate_buffer = nullptr;  // float4 [H*W]
+		void* d_out = nullptr;
+		uint32_t output_format = NRS_TONEMAP_RGBA32F;
+		nrs_color_space color_space = NRS_COLOR_LINEAR;
+		nrs_tonemap_curve tonemap_curve = NRS_TONEMAP_IDENTITY;
+		// clears the slabs before a launch.  Null: the caller's own device memset is not available to this header, so render_to_cpu refuses more than one batch per call
+		void (*clear_slabs)(WindowlessSurface&, void* stream) = nullptr;
+	};
+	float m_camera[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};          // m_camera, 3x4 column-major
+	float m_smoothed_camera[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}; // m_smoothed_camera: the camera the last frame ended on
+	bool m_camera_smoothing = false;
+	float m_fov = 50.625f;                                              // fov() in degrees, along m_fov_axis
+	int m_fov_axis = 1;
+	float m_screen_center[2] = {0.5f, 0.5f};
+	float m_exposure = 0.f;
+	float m_background_color[4] = {0, 0, 0, 0};
+	std::vector<nrs_camera_keyframe> m_camera_path;                     // m_camera_path.m_keyframes
+
+	// Testbed::load_camera_path -> CameraPath::load (src/camera_path.cu:114-136)
+	void load_camera_path(const char* path) {
+		nrs_camera_path* h = nullptr;
+		check(nrs_camera_path_open(path, &h), "nrs_camera_path_open");
+		m_camera_path.assign(nrs_camera_path_count(h), nrs_camera_keyframe{});
+		const int st = nrs_camera_path_keyframes(h, m_camera_path.data(), (uint32_t)m_camera_path.size());
+		nrs_camera_path_close(h);
+		check(st, "nrs_camera_path_keyframes");
+	}
+	// void Testbed::set_camera_from_time(float t) -- src/testbed.cu:2099-2111: nothing without keyframes
+	void set_camera_from_time(float t) {
+		if (m_camera_path.empty()) return;
+		nrs_camera_keyframe k{};
+		check(nrs_camera_path_eval(m_camera_path.data(), (uint32_t)m_camera_path.size(), t, &k), "nrs_camera_path_eval");
+		check(nrs_camera_keyframe_matrix(&k, m_camera), "nrs_camera_keyframe_matrix");
+		m_slice_plane_z = k.slice; m_scale = k.scale; m_fov = k.fov; m_dof = k.dof;
+	}
+	// void Testbed::apply_camera_smoothing(float elapsed_ms) -- src/testbed.cu:2086-2093
+	void apply_camera_smoothing(float elapsed_ms) {
+		if (m_camera_smoothing) {
+			const float decay = std::pow(0.02f, elapsed_ms / 1000.0f);
+			float out[12];
+			check(nrs_log_space_lerp(m_smoothed_camera, m_camera, 1.0f - decay, out), "nrs_log_space_lerp");
+			for (int i = 0; i < 12; ++i) m_smoothed_camera[i] = out[i];
+		} else {
+			for (int i = 0; i < 12; ++i) m_smoothed_camera[i] = m_camera[i];
+		}
+	}
+	// Testbed::calc_focal_length (src/testbed.cu:2556) with zoom 1: fov_to_focal_length(resolution[m_fov_axis], fov), evaluated as nrs_motion_views does
+	void calc_focal_length(int width, int height, float out[2]) const {
+		const double rel = 0.5 / std::tan(0.5 * (double)m_fov * 3.14159265358979323846 / 180.0);
+		out[0] = out[1] = (float)(rel * (double)(m_fov_axis == 0 ? width : height));
+	}
+
+	// py::array_t<float> Testbed::render_to_cpu(int width, int height, int spp, bool linear, float start_time, float end_time, float fps, float shutter_fraction)
+	//     -- src/python_api.cu:129-175.  The accumulation is reset; with start_time >= 0 the frame runs from m_smoothed_camera to the (smoothed) camera of end_time and every
+	// sample renders between its own two cameras, with the path's fov / dof / focus plane at its own time (nrs_motion_views), a view per sample and one launch per
+	// surface.n_slabs samples (nrs_render_nerf_spp_views); with start_time < 0 every sample renders m_camera (nrs_render_nerf_spp).  The slabs are folded into the running
+	// mean and the last fold is fused with the display step (m_exposure, m_background_color; sRGB unless `linear`).  m_smoothed_camera is left at the end camera.
+	// m_autofocus is not mirrored.  Not synchronised: the image is in surface.d_out once `stream` has run.
+	void render_to_cpu(Context& ctx, NerfNetwork& network, WindowlessSurface& surface, int spp, bool linear, float start_time = -1.f, float end_time = -1.f, float fps = 30.f,
+	                   float shutter_fraction = 1.0f, void* stream = nullptr, nrs_render_stats* stats = nullptr) {
+		if (spp < 1) throw std::runtime_error("Testbed::render_to_cpu: spp must be at least 1");
+		if (!surface.frames || !surface.depths || !surface.accumulate_buffer || !surface.d_out || surface.n_slabs == 0u || surface.n_slabs > NRS_SPP_BATCH_MAX)
+			throw std::runtime_error("Testbed::render_to_cpu: the surface needs frames, depths, an accumulate buffer, d_out and 1 .. NRS_SPP_BATCH_MAX slabs");
+		if ((uint32_t)spp > surface.n_slabs && !surface.clear_slabs)
+			throw std::runtime_error("Testbed::render_to_cpu: spp above the surface's slabs needs surface.clear_slabs between the launches");
+		if (end_time < 0.f) end_time = start_time;
+		float start_cam[12], end_cam[12];
+		for (int i = 0; i < 12; ++i) start_cam[i] = m_smoothed_camera[i];
+		if (start_time >= 0.f) {
+			set_camera_from_time(end_time);
+			apply_camera_smoothing(1000.f / fps);
+		} else {
+			for (int i = 0; i < 12; ++i) start_cam[i] = m_smoothed_camera[i] = m_camera[i];
+		}
+		for (int i = 0; i < 12; ++i) end_cam[i] = m_smoothed_camera[i];
+		const float rolling_shutter[4] = {0.f, 0.f, 0.f, 0.f};
+		nrs_sample_view base{};
+		calc_focal_length(surface.width, surface.height, base.focal_length);
+		base.dof = m_dof;
+		base.slice_plane_z = m_slice_plane_z + m_scale;
+		const int32_t resolution[2] = {surface.width, surface.height};
+		std::vector<nrs_edit*> edits;
+		for (const EditOperator* op : m_edit_operators) edits.push_back(op->get());
+		check(nrs_model_set_light_dir(network.get(), m_nerf.light_dir), "nrs_model_set_light_dir");
+		nrs_tonemap_params t{};
+		t.struct_size = (uint32_t)sizeof(nrs_tonemap_params);
+		t.exposure = m_exposure;
+		for (int i = 0; i < 4; ++i) t.background_color[i] = m_background_color[i];
+		t.color_space = (uint32_t)surface.color_space;
+		t.output_color_space = linear ? 0u : 1u;
+		t.tonemap_curve = (uint32_t)surface.tonemap_curve;
+		t.output_format = surface.output_format;
+		if (stats) *stats = nrs_render_stats{};
+		std::vector<nrs_sample_view> views(surface.n_slabs);
+		for (uint32_t done = 0; done < (uint32_t)spp;) {
+			const uint32_t k = (uint32_t)spp - done < surface.n_slabs ? (uint32_t)spp - done : surface.n_slabs;
+			if (done != 0u) surface.clear_slabs(surface, stream);
+			const bool moving = start_time >= 0.f;
+			if (moving)
+				check(nrs_motion_views(start_cam, end_cam, shutter_fraction, k, done, (uint32_t)spp, resolution, m_fov_axis, m_camera_path.data(), (uint32_t)m_camera_path.size(),
+				                       start_time, end_time, &base, views.data()), "nrs_motion_views");
+			const nrs_render_params p = make_params(surface.width, surface.height, done, base.focal_length, moving ? views[0].camera_matrix0 : start_cam,
+			                                        moving ? views[0].camera_matrix1 : end_cam, rolling_shutter, m_screen_center, true);
+			nrs_render_stats batch_stats{};
+			check(nrs_render_nerf_spp_views(network.get(), &p, edits.data(), (int)edits.size(), k, moving ? views.data() : nullptr, surface.frames, surface.depths, nullptr,
+			                                surface.slab_stride_pixels, stream, stats ? &batch_stats : nullptr), "nrs_render_nerf_spp_views");
+			if (stats) { stats->n_samples += batch_stats.n_samples; stats->n_rays_alive += batch_stats.n_rays_alive; stats->n_rays_hit += batch_stats.n_rays_hit; }
+			if (done + k < (uint32_t)spp)
+				check(nrs_accumulate_spp(ctx.get(), stream, (uint32_t)surface.width, (uint32_t)surface.height, surface.frames, surface.slab_stride_pixels, k, surface.accumulate_buffer,
+				                         done, (uint32_t)surface.color_space), "nrs_accumulate_spp");
+			else
+				check(nrs_accumulate_spp_tonemap(ctx.get(), stream, (uint32_t)surface.width, (uint32_t)surface.height, surface.frames, surface.slab_stride_pixels, k,
+				                                 surface.accumulate_buffer, done, &t, surface.d_out), "nrs_accumulate_spp_tonemap");
+			done += k;
+		}
+		if (start_time >= 0.f) { // the loop's last set_camera_from_time (:156): the testbed is left on the last sample's keyframe
+			const float a0 = ((float)(spp - 1)) / (float)spp * shutter_fraction, a1 = ((float)(spp - 1) + 1.0f) / (float)spp * shutter_fraction;
+			set_camera_from_time(start_time + (end_time - start_time) * (a0 + a1) / 2.0f);
+		}
+		for (int i = 0; i < 12; ++i) m_smoothed_camera[i] = end_cam[i]; // :167-168
 	}
 };
 

@@ -156,6 +156,16 @@ class TonemapParams(C.Structure):
         self.struct_size = C.sizeof(TonemapParams)
 
 
+class SampleView(C.Structure):
+    """nrs_sample_view: the view of one sample of nrs_render_nerf_spp_views"""
+    _fields_ = [("camera_matrix0", C.c_float * 12), ("camera_matrix1", C.c_float * 12), ("focal_length", C.c_float * 2), ("dof", C.c_float), ("slice_plane_z", C.c_float)]
+
+
+class CameraKeyframe(C.Structure):
+    """nrs_camera_keyframe: R is the quaternion (x, y, z, w)"""
+    _fields_ = [("R", C.c_float * 4), ("T", C.c_float * 3), ("slice", C.c_float), ("scale", C.c_float), ("fov", C.c_float), ("dof", C.c_float)]
+
+
 # every symbol include/nrs.h declares; tests check the library exports exactly these
 EXPORTS = [
     "nrs_last_error", "nrs_abi_version", "nrs_edit_poisson_interpolate", "nrs_edit_download_poisson", "nrs_comm_unique_id", "nrs_comm_create", "nrs_comm_info", "nrs_comm_destroy", "nrs_gather_tiles", "nrs_comm_probe_self_p2p",
@@ -177,6 +187,8 @@ EXPORTS = [
     "nrs_model_create_ex", "nrs_model_n_params_ex", "nrs_model_n_extra_dims", "nrs_model_set_light_dir", "nrs_network_inference_strided",
     "nrs_snapshot_open_ex", "nrs_snapshot_n_extra_dims",
     "nrs_tonemap", "nrs_accumulate_spp_tonemap", "nrs_tonemap_output_bytes",
+    "nrs_render_nerf_spp_views", "nrs_log_space_lerp", "nrs_camera_keyframe_matrix", "nrs_camera_keyframe_from_matrix", "nrs_camera_path_eval",
+    "nrs_camera_path_open", "nrs_camera_path_count", "nrs_camera_path_keyframes", "nrs_camera_path_close", "nrs_motion_views",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -303,6 +315,21 @@ def load():
         lib.nrs_accumulate_spp_tonemap.argtypes = [P, P, U32, U32, P, C.c_size_t, U32, P, U32, C.POINTER(TonemapParams), P]
         lib.nrs_tonemap_output_bytes.argtypes = [U32, U32, U32]
         lib.nrs_tonemap_output_bytes.restype = C.c_size_t
+    # a view per sample and the cameras of render_to_cpu's loop (appended exports, detected by symbol like the spp batch)
+    if hasattr(lib, "nrs_render_nerf_spp_views"):
+        F12 = C.POINTER(C.c_float * 12)
+        lib.nrs_render_nerf_spp_views.argtypes = [P, C.POINTER(RenderParams), C.POINTER(P), I, U32, P, P, P, P, C.c_size_t, P, C.POINTER(RenderStats)]
+        lib.nrs_log_space_lerp.argtypes = [F12, F12, C.c_float, F12]
+        lib.nrs_camera_keyframe_matrix.argtypes = [C.POINTER(CameraKeyframe), F12]
+        lib.nrs_camera_keyframe_from_matrix.argtypes = [F12, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(CameraKeyframe)]
+        lib.nrs_camera_path_eval.argtypes = [P, U32, C.c_float, C.POINTER(CameraKeyframe)]
+        lib.nrs_camera_path_open.argtypes = [C.c_char_p, C.POINTER(P)]
+        lib.nrs_camera_path_count.argtypes = [P]
+        lib.nrs_camera_path_count.restype = U32
+        lib.nrs_camera_path_keyframes.argtypes = [P, P, U32]
+        lib.nrs_camera_path_close.argtypes = [P]
+        lib.nrs_camera_path_close.restype = None
+        lib.nrs_motion_views.argtypes = [F12, F12, C.c_float, U32, U32, U32, C.POINTER(C.c_int32 * 2), I, P, U32, C.c_float, C.c_float, C.POINTER(SampleView), P]
     lib.nrs_snapshot_open.argtypes = [C.c_char_p, C.POINTER(P)]
     lib.nrs_snapshot_close.argtypes = [P]
     lib.nrs_snapshot_close.restype = None

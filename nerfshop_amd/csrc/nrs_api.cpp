@@ -57,6 +57,7 @@ struct nrs_ctx {
 	uint8_t counter_parity[kInFlight] = {};   // block the slot's next launch uses; counters_clean: that block is known to be zero
 	bool counters_clean[kInFlight] = {};
 	DeviceEdit* d_edits = nullptr;          // [kInFlight + 1][kMaxEdits]; the last table belongs to the occupancy refresh
+	nrs_sample_view* d_views = nullptr;     // [kInFlight][NRS_SPP_BATCH_MAX]: the view table of a slot's launch (nrs_render_nerf_spp_views)
 	std::atomic<uint32_t> launch_serial{0};
 	std::mutex launch_mutex; // slot acquisition .. launch enqueued: two threads rendering on one ctx must not share a slot's counter block / parity
 	// A slot is reused every kInFlight launches, possibly from ANOTHER stream: the launch that used it last records slot_done, and a
@@ -440,6 +441,7 @@ int nrs_ctx_create(int device, nrs_ctx** out) {
 	if (he == hipSuccess) he = hipMemset(c->d_counters, 0, sizeof(RenderCounters) * nrs_ctx::kInFlight * 2);
 	for (int i = 0; i < nrs_ctx::kInFlight; ++i) c->counters_clean[i] = he == hipSuccess;
 	if (he == hipSuccess) he = hipMalloc((void**)&c->d_edits, sizeof(DeviceEdit) * nrs_ctx::kMaxEdits * (nrs_ctx::kInFlight + 1));
+	if (he == hipSuccess) he = hipMalloc((void**)&c->d_views, sizeof(nrs_sample_view) * NRS_SPP_BATCH_MAX * nrs_ctx::kInFlight);
 	for (int i = 0; i < nrs_ctx::kInFlight && he == hipSuccess; ++i) he = hipEventCreateWithFlags(&c->slot_done[i], hipEventDisableTiming);
 	if (he == hipSuccess) he = hipMalloc((void**)&c->d_mean, 8 + 256 * 8); // mean + partial sums (launch_grid_to_bitfield)
 	if (he == hipSuccess) he = hipMalloc((void**)&c->d_wave_log, 8192 * 4 * 8);
@@ -462,6 +464,7 @@ void nrs_ctx_destroy(nrs_ctx* c) {
 	if (!c) return;
 	(void)hipFree(c->d_counters);
 	(void)hipFree(c->d_edits);
+	(void)hipFree(c->d_views);
 	for (int i = 0; i < nrs_ctx::kInFlight; ++i)
 		if (c->slot_done[i]) (void)hipEventDestroy(c->slot_done[i]);
 	(void)hipFree(c->d_mean);
@@ -1538,6 +1541,11 @@ uint32_t nrs_render_owned_tiles(const nrs_render_params* p) {
 }
 
 // ---- nrs_render_nerf and nrs_render_nerf_spp: spp_count samples of the view into slabs slab_stride pixels apart (a single frame: 1, 0) -----------------
+// the aperture of a view: the params' own, or each record of a views batch
+static int check_lens(float dof, float slice_plane_z, const std::string& who) {
+	if (dof != 0.f && slice_plane_z == 0.f) return fail(NRS_ERR_INVALID_ARG, who + ": dof != 0 needs a focus distance (slice_plane_z = m_slice_plane_z + m_scale != 0)");
+	return NRS_OK;
+}
 static int check_render_args(const nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, const float* d_frame,
                              const float* d_depth, size_t slab_stride) {
 	if (!m || !p || !d_frame || !d_depth) return fail(NRS_ERR_INVALID_ARG, spp_count > 1u ? "nrs_render_nerf_spp: NULL argument (model, params, d_frames, d_depths)" : "nrs_render_nerf: NULL argument");
@@ -1554,7 +1562,7 @@ static int check_render_args(const nrs_model* m, const nrs_render_params* p, nrs
 	if (p->d_distortion_map && (p->distortion_resolution[0] < 1 || p->distortion_resolution[1] < 1)) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: distortion map without a resolution");
 	if (p->render_mode > NRS_RENDER_SLICE && p->render_mode != NRS_RENDER_ENCODING_VIS) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: unknown render mode");
 	if (!std::isfinite(p->dof) || !std::isfinite(p->slice_plane_z) || !std::isfinite(p->depth_scale)) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: dof / slice_plane_z / depth_scale must be finite");
-	if (p->dof != 0.f && p->slice_plane_z == 0.f) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: dof != 0 needs a focus distance (slice_plane_z = m_slice_plane_z + m_scale != 0)");
+	{ const int lc = check_lens(p->dof, p->slice_plane_z, "nrs_render_nerf"); if (lc != NRS_OK) return lc; }
 	if (n_edits < 0 || n_edits > nrs_ctx::kMaxEdits) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: too many edit operators");
 	if (n_edits > 0 && !edits) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf: edits is NULL");
 	if (spp_count > 1u) { // what only a batch can get wrong; everything above is the single frame's check
@@ -1632,7 +1640,7 @@ static int collect_edits(nrs_edit* const* edits, int n_edits, hipStream_t s, Edi
 }
 
 // what plan_route is asked: the model, the operators, the parameters, and the context's state (slot: this launch's, not counted as busy)
-static RouteRequest route_request(const nrs_model* m, const nrs_render_params& p, const EditTable& t, uint32_t spp_count, uint32_t pixels_owned, uint32_t slot, hipStream_t s) {
+static RouteRequest route_request(const nrs_model* m, const nrs_render_params& p, const EditTable& t, uint32_t spp_count, const nrs_sample_view* h_views, uint32_t pixels_owned, uint32_t slot, hipStream_t s) {
 	const nrs_ctx* ctx = m->ctx;
 	RouteRequest q{};
 	q.n_extra_dims = m->n_extra_dims; q.rgb_deep = m->dm.rgb_deep; q.numerics = m->dm.numerics;
@@ -1642,7 +1650,12 @@ static RouteRequest route_request(const nrs_model* m, const nrs_render_params& p
 	q.render_mode = p.render_mode; q.show_accel = p.show_accel; q.dof_on = p.dof != 0.f; q.distortion_mode = p.distortion_mode; q.distortion_map = p.d_distortion_map != nullptr;
 	q.envmap = p.d_envmap != nullptr; q.glow_mode = p.glow_mode;
 	q.cone_angle_constant = p.cone_angle_constant;
-	q.tile_size = p.tile_size; q.height = (uint32_t)p.resolution[1]; q.spp_count = spp_count;
+	q.tile_size = p.tile_size; q.height = (uint32_t)p.resolution[1]; q.spp_count = (uint16_t)spp_count;
+	if (h_views) { // a view per sample: the aperture of ANY of them asks for the thin-lens branch
+		q.views = 1;
+		q.dof_on = 0u;
+		for (uint32_t k = 0; k < spp_count; ++k) q.dof_on |= h_views[k].dof != 0.f ? 1u : 0u;
+	}
 	q.lane_teams = ctx->lane_teams; q.n_cus = ctx->n_cus; q.pixels_owned = pixels_owned;
 	const unsigned long long fb = ctx->h_feedback ? __atomic_load_n(ctx->h_feedback, __ATOMIC_RELAXED) : 0ull;
 	q.hit_share = (fb >> 32) ? (double)(uint32_t)fb / (double)(fb >> 32) : 0.25;
@@ -1664,7 +1677,7 @@ static RouteRequest route_request(const nrs_model* m, const nrs_render_params& p
 // The statistics / queue block of a launch: a slot owns two, and the render kernel's last workgroup zeroes the one it did NOT use, which the slot's next
 // launch takes (launches of a slot are ordered: same stream, or the event wait) -- so a frame costs no memset (two 5-us fill kernels per frame in
 // the round-3 timeline: 2 % of a 1/8 share-frame).  The Slice path and a launch after a failed one still clear their block the plain way.
-static int enqueue(nrs_model* m, const nrs_render_params& p, hipStream_t s, uint32_t slot, const EditTable& t, RenderArgs& a, const RoutePlan* plan, RenderCounters** d_counters) {
+static int enqueue(nrs_model* m, const nrs_render_params& p, hipStream_t s, uint32_t slot, const EditTable& t, const nrs_sample_view* h_views, RenderArgs& a, const RoutePlan* plan, RenderCounters** d_counters) {
 	nrs_ctx* ctx = m->ctx;
 	if (ctx->slot_used[slot] && ctx->slot_stream[slot] != s) HIP_TRY(hipStreamWaitEvent(s, ctx->slot_done[slot], 0));
 	// the operator table of a slot is re-sent only when it changed (a viewer renders many frames per gizmo move)
@@ -1676,6 +1689,14 @@ static int enqueue(nrs_model* m, const nrs_render_params& p, hipStream_t s, uint
 		ctx->shadow_n[slot] = t.n;
 	}
 	a.edits = d_edits_slot;
+	// the view table of a views batch: into the slot's own records, ordered on the stream like the launch that reads them.  The records travel as kernel arguments
+	// (launch_views_upload), which the runtime copies before the call returns: the caller's array is free on return and no pinned staging area is shared between launches.
+	a.views = nullptr;
+	if (h_views && plan && a.n_packets != 0) {
+		nrs_sample_view* d_views_slot = ctx->d_views + (size_t)slot * NRS_SPP_BATCH_MAX;
+		NRS_TRY(launch_views_upload(h_views, a.spp_count, d_views_slot, s));
+		a.views = d_views_slot;
+	}
 	a.counters = *d_counters = ctx->d_counters + 2 * slot + ctx->counter_parity[slot];
 	const bool clean = plan && ctx->counters_clean[slot];
 	ctx->counters_clean[slot] = false; // (until a render launch is known to be enqueued: its last workgroup cleans the other block; slice_kernel cleans nothing)
@@ -1690,7 +1711,7 @@ static int enqueue(nrs_model* m, const nrs_render_params& p, hipStream_t s, uint
 			const unsigned long long dispatches0 = launch_render_dispatches();
 			NRS_TRY(launch_render((RouteId)plan->row, model_for_launch(m, p), a, ctx->n_cus, s));
 			ctx->render_dispatches += launch_render_dispatches() - dispatches0;
-			ctx->last_schedule = a.team | (a.fill_lanes << 8) | (a.all_tail << 16) | ((a.p_big ? 1u : 0u) << 17) | ((a.spp_count > 1u ? 1u : 0u) << 18);
+			ctx->last_schedule = a.team | (a.fill_lanes << 8) | (a.all_tail << 16) | ((a.p_big ? 1u : 0u) << 17) | ((a.spp_count > 1u ? 1u : 0u) << 18) | ((a.views ? 1u : 0u) << 19);
 			ctx->counter_parity[slot] ^= 1u;
 		}
 		ctx->counters_clean[slot] = true;
@@ -1765,8 +1786,9 @@ static int read_stats(nrs_ctx* ctx, hipStream_t s, const RenderCounters* d_count
 	return (dbg & 4u) ? report_wave_log(ctx, c) : NRS_OK;
 }
 
+// h_views: spp_count > 1 records, validated by the caller (nrs_render_nerf_spp_views), or NULL: every sample renders the params' own view
 static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frame, float* d_depth,
-                          uint32_t* d_steps, size_t slab_stride, void* stream, nrs_render_stats* h_stats) {
+                          uint32_t* d_steps, size_t slab_stride, void* stream, nrs_render_stats* h_stats, const nrs_sample_view* h_views = nullptr) {
 	{ const int st = check_render_args(m, p, edits, n_edits, spp_count, d_frame, d_depth, slab_stride); if (st != NRS_OK) return st; }
 	nrs_ctx* ctx = m->ctx;
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -1784,7 +1806,7 @@ static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* co
 	const uint32_t pixels_owned = (uint32_t)std::min<uint64_t>((uint64_t)a.n_packets * 64ull * spp_count, 0xffffffffull); // (a batch: the rays of all its samples decide the schedule)
 	EditTable table;
 	{ const int st = collect_edits(edits, n_edits, s, table); if (st != NRS_OK) return st; }
-	const RouteRequest request = route_request(m, *p, table, spp_count, pixels_owned, slot, s);
+	const RouteRequest request = route_request(m, *p, table, spp_count, h_views, pixels_owned, slot, s);
 	const RoutePlan plan = plan_route(request);
 	if (plan.status != NRS_OK) return fail(plan.status, plan.message);
 	a.n_edits = n_edits;
@@ -1827,7 +1849,7 @@ static int render_samples(nrs_model* m, const nrs_render_params* p, nrs_edit* co
 		a.max_steps = p->max_march_steps ? p->max_march_steps : 10000u; // MARCH_ITER, testbed_nerf.cu:56
 	}
 	RenderCounters* d_counters = nullptr;
-	{ const int st = enqueue(m, *p, s, slot, table, a, slice ? nullptr : &plan, &d_counters); if (st != NRS_OK) return st; }
+	{ const int st = enqueue(m, *p, s, slot, table, plan.views ? h_views : nullptr, a, slice ? nullptr : &plan, &d_counters); if (st != NRS_OK) return st; }
 	launch_lock.unlock();
 	return h_stats ? read_stats(ctx, s, d_counters, !slice, a.dbg, h_stats) : NRS_OK;
 }
@@ -1836,12 +1858,45 @@ int nrs_render_nerf(nrs_model* m, const nrs_render_params* p, nrs_edit* const* e
                     uint32_t* d_steps, void* stream, nrs_render_stats* h_stats) {
 	return render_samples(m, p, edits, n_edits, 1u, d_frame, d_depth, d_steps, 0, stream, h_stats);
 }
-int nrs_render_nerf_spp(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frames, float* d_depths,
-                        uint32_t* d_steps, size_t slab_stride_pixels, void* stream, nrs_render_stats* h_stats) {
+// what both batch entry points refuse before anything else
+static int check_batch_args(uint32_t spp_count, const float* d_frames, const float* d_depths) {
 	if (!d_frames || !d_depths) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: d_frames / d_depths is NULL");
 	if (spp_count == 0u) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count is 0");
 	if (spp_count > NRS_SPP_BATCH_MAX) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp: spp_count above NRS_SPP_BATCH_MAX (64)");
+	return NRS_OK;
+}
+int nrs_render_nerf_spp(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, float* d_frames, float* d_depths,
+                        uint32_t* d_steps, size_t slab_stride_pixels, void* stream, nrs_render_stats* h_stats) {
+	{ const int bc = check_batch_args(spp_count, d_frames, d_depths); if (bc != NRS_OK) return bc; }
 	return render_samples(m, p, edits, n_edits, spp_count, d_frames, d_depths, d_steps, slab_stride_pixels, stream, h_stats);
+}
+int nrs_render_nerf_spp_views(nrs_model* m, const nrs_render_params* p, nrs_edit* const* edits, int n_edits, uint32_t spp_count, const nrs_sample_view* h_views,
+                              float* d_frames, float* d_depths, uint32_t* d_steps, size_t slab_stride_pixels, void* stream, nrs_render_stats* h_stats) {
+	if (!h_views) return nrs_render_nerf_spp(m, p, edits, n_edits, spp_count, d_frames, d_depths, d_steps, slab_stride_pixels, stream, h_stats);
+	{ const int bc = check_batch_args(spp_count, d_frames, d_depths); if (bc != NRS_OK) return bc; }
+	if (!p) return fail(NRS_ERR_INVALID_ARG, "nrs_render_nerf_spp_views: params is NULL");
+	{ const int ac = check_params_abi(p, "nrs_render_nerf_spp_views"); if (ac != NRS_OK) return ac; }
+	for (uint32_t k = 0; k < spp_count; ++k) {
+		const nrs_sample_view& v = h_views[k];
+		const std::string who = "nrs_render_nerf_spp_views: h_views[" + std::to_string(k) + "]";
+		for (int i = 0; i < 12; ++i) {
+			if (!std::isfinite(v.camera_matrix0[i])) return fail(NRS_ERR_INVALID_ARG, who + ".camera_matrix0 is not finite");
+			if (!std::isfinite(v.camera_matrix1[i])) return fail(NRS_ERR_INVALID_ARG, who + ".camera_matrix1 is not finite");
+		}
+		for (int i = 0; i < 2; ++i)
+			if (!std::isfinite(v.focal_length[i]) || !(v.focal_length[i] > 0.f)) return fail(NRS_ERR_INVALID_ARG, who + ".focal_length must be finite and > 0");
+		if (!std::isfinite(v.dof)) return fail(NRS_ERR_INVALID_ARG, who + ".dof is not finite");
+		if (!std::isfinite(v.slice_plane_z)) return fail(NRS_ERR_INVALID_ARG, who + ".slice_plane_z is not finite");
+		{ const int lc = check_lens(v.dof, v.slice_plane_z, who); if (lc != NRS_OK) return lc; }
+	}
+	// the params as the first sample sees them: what the shared checks look at, what a batch of one renders, and (Slice) what the refusal of a batch is decided on
+	nrs_render_params q = *p;
+	memcpy(q.camera_matrix0, h_views[0].camera_matrix0, sizeof(q.camera_matrix0));
+	memcpy(q.camera_matrix1, h_views[0].camera_matrix1, sizeof(q.camera_matrix1));
+	q.focal_length[0] = h_views[0].focal_length[0]; q.focal_length[1] = h_views[0].focal_length[1];
+	q.dof = h_views[0].dof;
+	q.slice_plane_z = h_views[0].slice_plane_z;
+	return render_samples(m, &q, edits, n_edits, spp_count, d_frames, d_depths, d_steps, slab_stride_pixels, stream, h_stats, spp_count > 1u ? h_views : nullptr);
 }
 int nrs_ctx_render_launches(const nrs_ctx* ctx, uint64_t* n_dispatches, uint32_t* last_schedule) {
 	if (!ctx) return fail(NRS_ERR_INVALID_ARG, "nrs_ctx_render_launches: NULL context");
@@ -1863,6 +1918,14 @@ int nrs_route_probe(const RouteRequest* requests, uint32_t request_size, uint32_
 		o.team = plan.team; o.all_tail = plan.all_tail; o.fill_lanes = plan.fill_lanes; o.tail_every = plan.tail_every; o.tail_target = plan.tail_target; o.hybrid = plan.hybrid;
 		o.row_has_batch = kRoutes[plan.row].batch;
 		route_name(o.name, sizeof(o.name), kRoutes[plan.row].t, requests[i].spp_count > 1u);
+	}
+	return NRS_OK;
+}
+int nrs_route_probe_views(const RouteRequest* requests, uint32_t request_size, uint32_t n, uint32_t* views_out) {
+	if (!requests || !views_out || request_size != sizeof(RouteRequest)) return fail(NRS_ERR_INVALID_ARG, "nrs_route_probe_views: NULL argument, or the caller's struct is not this library's");
+	for (uint32_t i = 0; i < n; ++i) {
+		const RoutePlan plan = plan_route(requests[i]);
+		views_out[i] = plan.status == NRS_OK ? plan.views : 0u;
 	}
 	return NRS_OK;
 }

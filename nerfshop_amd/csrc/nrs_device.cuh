@@ -296,12 +296,19 @@ __device__ __forceinline__ float4 read_envmap(const float* __restrict__ data, co
 	                   ((w00 * a.z + w10 * b.z) + w01 * c.z) + w11 * e.z, ((w00 * a.w + w10 * b.w) + w01 * c.w) + w11 * e.w);
 }
 
+#define NRS_GLOBAL __attribute__((address_space(1)))
+#define NRS_CONSTANT __attribute__((address_space(4)))
 // pixel_to_ray (common_device.cuh:245-295): origin and UN-normalised direction of pixel (x, y) through the camera of its ray time
 // (init_rays_with_payload_kernel_nerf, tn:2551-2567).  offset = ld_random_pixel_offset(snap ? 0 : spp), computed once per thread by the caller.
 // LENS compiles in the thin-lens branch (:285-293; m_dof, focus distance focus_z = plane_z): only the instantiations that serve dof != 0 carry it.
 // SPP: the Sobol sample index is the argument `spp`, not p.spp_index (a batch of samples of one view in one launch, nrs_render_nerf_spp: the index differs per packet)
-template <bool LENS = false, bool SPP = false>
-__device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, float focus_z, f3& o, f3& d, bool use_dof = true, uint32_t spp = 0u) {
+//      and, where `vw` is given, the two cameras, the focal length and the aperture are that sample's own (nrs_render_nerf_spp_views): the same arithmetic on the
+//      record's floats as on the params' -- the same bits as a single frame whose params hold them.  The record is read through a pointer with an explicit address
+//      space, never through one that could be merged with a pointer into the params: the kernel arguments would then be copied to scratch for every launch.
+//      UNIFORM: `vw` is the same in every lane (the fill: one packet, one sample) -- the record is constant for the life of the kernel and comes in through scalar loads.
+template <bool LENS = false, bool SPP = false, bool UNIFORM = false>
+__device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, float focus_z, f3& o, f3& d, bool use_dof = true, uint32_t spp = 0u,
+                                              const nrs_sample_view* vw = nullptr) {
 	const float W = (float)p.resolution[0], H = (float)p.resolution[1];
 	const uint32_t idx = x + (uint32_t)p.resolution[0] * y;
 	float u = ((float)x + 0.5f) * (1.f / W);
@@ -309,12 +316,25 @@ __device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32
 	float ray_time = p.rolling_shutter[0] + p.rolling_shutter[1] * u + p.rolling_shutter[2] * v;
 	float rs_rand = (p.rolling_shutter[3] != 0.f) ? ld_random_val(SPP ? spp : p.spp_index, idx * 72239731u) : 0.f; // x * 0 == 0 for finite x
 	ray_time = ray_time + p.rolling_shutter[3] * rs_rand;
-	float cam[12];
-	#pragma unroll
-	for (int i = 0; i < 12; ++i) cam[i] = p.camera_matrix0[i] * ray_time + p.camera_matrix1[i] * (1.f - ray_time);
+	float cam[12], v_focal_x = 0.f, v_focal_y = 0.f, v_dof = 0.f; // (v_*: the view's; without a view every use below reads the params where it always did)
+	const bool viewed = SPP && vw;
+	if (!viewed) {
+		#pragma unroll
+		for (int i = 0; i < 12; ++i) cam[i] = p.camera_matrix0[i] * ray_time + p.camera_matrix1[i] * (1.f - ray_time);
+	} else { // (the focal length and the aperture now; the cameras where they are used, below)
+		if (UNIFORM) {
+			const NRS_CONSTANT float* c = (const NRS_CONSTANT float*)vw;
+			v_focal_x = c[24]; v_focal_y = c[25]; v_dof = c[26];
+			if (use_dof) focus_z = c[27];
+		} else {
+			const NRS_GLOBAL float* c = (const NRS_GLOBAL float*)vw;
+			v_focal_x = c[24]; v_focal_y = c[25]; v_dof = c[26];
+			if (use_dof) focus_z = c[27];
+		}
+	}
 	float uvx = ((float)x + off_x) / W;
 	float uvy = ((float)y + off_y) / H;
-	f3 dir = {(uvx - p.screen_center[0]) * W / p.focal_length[0], (uvy - p.screen_center[1]) * H / p.focal_length[1], 1.0f};
+	f3 dir = {(uvx - p.screen_center[0]) * W / (viewed ? v_focal_x : p.focal_length[0]), (uvy - p.screen_center[1]) * H / (viewed ? v_focal_y : p.focal_length[1]), 1.0f};
 	if (LENS && p.distortion_mode == 2u) { // FTheta, common_device.cuh:231-243, :263-267
 		const float* prm = p.distortion_params;
 		const float xpix = (uvx - p.screen_center[0]) * prm[5], ypix = (uvy - p.screen_center[1]) * prm[6];
@@ -336,31 +356,43 @@ __device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32
 		read_image2(p.d_distortion_map, p.distortion_resolution, uvx, uvy, d0, d1);
 		dir.x += d0; dir.y += d1;
 	}
+	if (viewed) { // the view's cameras, read HERE and not above the lens code: cam[] would live through it in vector registers (the params' are re-read from the kernel arguments)
+		static_assert(offsetof(nrs_sample_view, camera_matrix1) == 48 && offsetof(nrs_sample_view, focal_length) == 96 && offsetof(nrs_sample_view, slice_plane_z) == 108, "record layout");
+		if (UNIFORM) {
+			const NRS_CONSTANT float* c = (const NRS_CONSTANT float*)vw;
+			#pragma unroll
+			for (int i = 0; i < 12; ++i) cam[i] = c[i] * ray_time + c[12 + i] * (1.f - ray_time);
+		} else {
+			const NRS_GLOBAL float* c = (const NRS_GLOBAL float*)vw;
+			#pragma unroll
+			for (int i = 0; i < 12; ++i) cam[i] = c[i] * ray_time + c[12 + i] * (1.f - ray_time);
+		}
+	}
 	d = mat3_mul(cam, dir); // camera_matrix.block<3, 3>(0, 0) * dir, common_device.cuh:282
 	o = {cam[9], cam[10], cam[11]};
-	if (LENS && use_dof && p.dof != 0.0f) {
+	if (LENS && use_dof && (viewed ? v_dof : p.dof) != 0.0f) {
 		const f3 lookat = o + d * focus_z;
 		float r0, r1, bx, by;
 		ld_random_val_2d(SPP ? spp : p.spp_index, x * 19349663u + y * 96925573u, r0, r1);
 		square2disk_shirley(r0 * 2.0f - 1.0f, r1 * 2.0f - 1.0f, bx, by);
-		bx = p.dof * bx; by = p.dof * by;
+		bx = (viewed ? v_dof : p.dof) * bx; by = (viewed ? v_dof : p.dof) * by;
 		o = {o.x + (cam[0] * bx + cam[3] * by), o.y + (cam[1] * bx + cam[4] * by), o.z + (cam[2] * bx + cam[5] * by)};
 		const f3 diff = lookat - o;
 		d = {diff.x / focus_z, diff.y / focus_z, diff.z / focus_z};
 	}
 }
 // origin and normalised direction (tn:2588)
-template <bool LENS = false, bool SPP = false>
-__device__ __forceinline__ void ray_origin_dir(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, f3& o, f3& d, uint32_t spp = 0u) {
-	pixel_ray_raw<LENS, SPP>(p, x, y, off_x, off_y, p.slice_plane_z, o, d, true, spp);
+template <bool LENS = false, bool SPP = false, bool UNIFORM = false>
+__device__ __forceinline__ void ray_origin_dir(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, f3& o, f3& d, uint32_t spp = 0u, const nrs_sample_view* vw = nullptr) {
+	pixel_ray_raw<LENS, SPP, UNIFORM>(p, x, y, off_x, off_y, p.slice_plane_z, o, d, true, spp, vw); // (a view brings its own focus distance)
 	float n = sqrtf(dot3(d, d));
 	d = {d.x / n, d.y / n, d.z / n};
 }
 
 template <bool LENS = false, bool SPP = false>
-__device__ __forceinline__ Ray init_ray(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, uint32_t spp = 0u) {
+__device__ __forceinline__ Ray init_ray(const nrs_render_params& p, uint32_t x, uint32_t y, float off_x, float off_y, uint32_t spp = 0u, const nrs_sample_view* vw = nullptr) {
 	Ray r;
-	ray_origin_dir<LENS, SPP>(p, x, y, off_x, off_y, r.o, r.d, spp);
+	ray_origin_dir<LENS, SPP, SPP>(p, x, y, off_x, off_y, r.o, r.d, spp, vw); // (the fill: the packet's sample is wave-uniform)
 	float tmin;
 	ray_intersect(p.render_aabb_min, p.render_aabb_max, r.o, r.d, tmin);
 	r.t = fmaxf(tmin, NRS_NEAR_DISTANCE) + 1e-6f;
@@ -698,7 +730,6 @@ __device__ __forceinline__ void bary_tet(f3 a, f3 b, f3 c, f3 d, f3 p, float out
 // The operator tables are reached through pointers that sit in a device-memory struct (DeviceEdit): left alone, the compiler cannot tell their address
 // space and emits FLAT loads (an aperture check per access, both wait counters) with one 64-bit address computation per dword.  They are global memory:
 // gp() casts them so (global_load), and a vertex / matrix column is one 12-byte load.
-#define NRS_GLOBAL __attribute__((address_space(1)))
 template <typename T>
 __device__ __forceinline__ const NRS_GLOBAL T* gp(const T* p) { return (const NRS_GLOBAL T*)p; }
 __device__ __forceinline__ f3 ld3(const float* __restrict__ a, uint32_t i) {

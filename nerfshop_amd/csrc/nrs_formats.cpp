@@ -669,4 +669,47 @@ int nrs_edits_cage(const nrs_edits* e, uint32_t i, nrs_tet_mesh* mesh_out, const
 	return NRS_OK;
 }
 
+// ---- camera paths: CameraPath::load (src/camera_path.cu:114-136) of the file CameraPath::save writes (:105-112), load_relative_to_first = false ----
+} // extern "C"
+struct nrs_camera_path { std::vector<nrs_camera_keyframe> keys; };
+extern "C" {
+int nrs_camera_path_open(const char* path, nrs_camera_path** out) {
+	if (!path || !out) return fmt_fail(NRS_ERR_INVALID_ARG, "nrs_camera_path_open: NULL argument");
+	try {
+		const std::string raw = read_file(path);
+		JsonReader rd{raw.data(), raw.data() + raw.size()};
+		const Value root = rd.read();
+		std::unique_ptr<nrs_camera_path> cp(new nrs_camera_path());
+		const Value* list = root.find("path"); // (`if (j.contains("path"))`; an empty vector is written as null: json_binding's writers)
+		if (list && list->kind != Value::Null) {
+			if (list->kind != Value::Arr) throw std::runtime_error("path is not an array");
+			for (const Value& el : list->a) {
+				nrs_camera_keyframe k;
+				const Value &r = el.at("R"), &t = el.at("T");
+				if (r.kind != Value::Arr || r.a.size() != 4) throw std::runtime_error("R: expected [x, y, z, w]");
+				if (t.kind != Value::Arr || t.a.size() != 3) throw std::runtime_error("T: expected [x, y, z]");
+				for (int i = 0; i < 4; ++i) k.R[i] = (float)r.a[i].number();
+				for (int i = 0; i < 3; ++i) k.T[i] = (float)t.a[i].number();
+				k.slice = (float)el.at("slice").number();
+				k.scale = (float)el.at("scale").number();
+				k.fov = (float)el.at("fov").number();
+				k.dof = (float)el.at("dof").number();
+				cp->keys.push_back(k);
+			}
+		}
+		*out = cp.release();
+		return NRS_OK;
+	} catch (const std::exception& ex) {
+		return fmt_fail(NRS_ERR_INVALID_ARG, std::string("nrs_camera_path_open('") + path + "'): " + ex.what());
+	}
+}
+void nrs_camera_path_close(nrs_camera_path* p) { delete p; }
+uint32_t nrs_camera_path_count(const nrs_camera_path* p) { return p ? (uint32_t)p->keys.size() : 0u; }
+int nrs_camera_path_keyframes(const nrs_camera_path* p, nrs_camera_keyframe* out, uint32_t capacity) {
+	if (!p || (!out && !p->keys.empty())) return fmt_fail(NRS_ERR_INVALID_ARG, "nrs_camera_path_keyframes: NULL argument");
+	if (capacity < p->keys.size()) return fmt_fail(NRS_ERR_INVALID_ARG, "nrs_camera_path_keyframes: capacity is smaller than nrs_camera_path_count");
+	if (!p->keys.empty()) memcpy(out, p->keys.data(), p->keys.size() * sizeof(nrs_camera_keyframe));
+	return NRS_OK;
+}
+
 } // extern "C"

@@ -191,11 +191,14 @@ struct RenderArgs {
 	RenderCounters* counters;
 	RenderCounters* counters_next; // the block the slot's NEXT launch will use: zeroed by this launch's last workgroup (nullable)
 	unsigned long long* wave_log; // NRS_DEBUG & 4: 4 words per wave (see nrs_render_nerf)
+	const nrs_sample_view* views; // nrs_render_nerf_spp_views: spp_count records in the launch slot's device table, sample s renders with record s (null: every sample with p's camera)
 };
 
 // kernel launchers (nrs_render.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip).  stream is a hipStream_t.
 // launches row `row` of kRoutes (nrs_route.h; the caller planned it: plan_route), or its batch twin when a.spp_count > 1
 int launch_render(RouteId row, const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
+// n records of a views batch into the launch slot's table, ordered on the stream; h_views is free when the call returns (the records travel as kernel arguments)
+int launch_views_upload(const nrs_sample_view* h_views, uint32_t n, nrs_sample_view* d_views, void* stream);
 unsigned long long launch_render_dispatches(); // render-kernel dispatches of this process so far (nrs_ctx_render_launches counts with it)
 // render mode Slice (Testbed::render_nerf's branch, testbed_nerf.cu:3111-3175): one network evaluation per owned pixel on the slice plane
 int launch_slice(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
@@ -292,3 +295,6 @@ void set_last_error(const char* msg);
 
 // plans n requests; request_size / probe_size are the caller's sizeof of the two structs (a mirror that has drifted is refused: NRS_ERR_INVALID_ARG)
 extern "C" int nrs_route_probe(const nrs::RouteRequest* requests, uint32_t request_size, uint32_t n, nrs::RouteProbe* out, uint32_t probe_size);
+// RoutePlan::views of each request (0 for a refused one): what nrs_route_probe's answer has no field for
+// (a second test-only export that plans every request again for one field: RouteProbe gets a `views` member, and this goes, when RouteProbe's mirrors next change)
+extern "C" int nrs_route_probe_views(const nrs::RouteRequest* requests, uint32_t request_size, uint32_t n, uint32_t* views_out);

@@ -213,6 +213,10 @@ __device__ __forceinline__ bool packet_pixel_tail(const RenderArgs& a, uint32_t 
 //      one packet to the whole wave): the fill forms the pixel offsets and the Sobol draws of sample spp_index + s and writes to slab s of the buffers (+ s * slab_stride
 //      pixels); a ring entry carries s (6 bits beside 13-bit pixel coordinates: nrs_render_nerf_spp refuses what does not fit).  From its first hit on a ray is an ordinary
 //      ray.  The instantiations without it are what they were before the flag existed: a single frame pays nothing for it.
+//      RenderArgs::views (nrs_render_nerf_spp_views; a wave-uniform branch of the same twins -- VIEWS: all but the lean EXTRA row's, see route_carries_views): sample s has its own cameras, focal length and aperture, record s of a
+//      device table.  The fill reads the packet's record (wave-uniform), the refill the record of each pending ray's sample, and the round re-reads the six floats of
+//      camera_matrix1 that the depth of a sample is measured against (cam_fwd / cam_o) for the lane's sample -- which is out_idx / slab_stride (a slab is at least as long as
+//      the pixels a call owns), so a ray carries no word more through re-teaming and the hand-over than it did.
 constexpr uint32_t kBatchXYBits = 13u, kBatchXYMask = (1u << kBatchXYBits) - 1u;
 static_assert((NRS_SPP_BATCH_MAX - 1u) >> (32u - 2u * kBatchXYBits) == 0u, "a ring entry holds the sample index beside the pixel");
 template <int WAVES, int OCC, bool PROF, bool POISSON, bool AFFINE, int TEAM, int NUM = 0, int XTRA = 0, bool BATCH = false>
@@ -223,6 +227,7 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 	// (plain frames and cage edits on the automatic schedule); 8 = the catch-all of such a network: EXTRA + INTRO, the third hidden layer where the network has one
 	// (DeviceModel::rgb_deep, a wave-uniform run-time branch here), every numerics, AffineDuplication -- whatever 7 does not serve.
 	constexpr bool LIGHT = kX.light;
+	constexpr bool VIEWS = route_carries_views(POISSON, AFFINE, XTRA, BATCH); // (nrs_route.h: every BATCH twin but the lean EXTRA row's, which has XTRA 9 for it)
 	// four levels per round trip in the gathers (encode_to_lds QUADS): the automatic schedule's instantiations with the default or the fully tiny-cuda-nn roundings -- since
 	// round 6 the membrane instantiation too (both of its gathers: 9.68 -> 10.06 Gsamples/s, same registers; profiles/r06/ab_poisson_quads.txt)
 	constexpr bool kQuads = TEAM == 0 && !EXTRA && NUM >= 0;
@@ -436,7 +441,7 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 			const bool first_of_team = TEAM == 0 ? (!small || (lane & (int)(a1.fill_lanes - 1u)) == 0) : tk == 0;
 			if (BATCH) oi += bs * a1.slab_stride;
 			if (inside) {
-				Ray r = BATCH ? init_ray<EXTRA, true>(p1, x, y, fo_x, fo_y, spp) : init_ray<EXTRA>(p1, x, y, off_x, off_y);
+				Ray r = BATCH ? init_ray<EXTRA, true>(p1, x, y, fo_x, fo_y, spp, (VIEWS && a1.views) ? a1.views + bs : nullptr) : init_ray<EXTRA>(p1, x, y, off_x, off_y);
 				if (first_of_team) {
 					a1.depth[oi] = 1e10f; // tn:2586
 					if (a1.steps) a1.steps[oi] = 0;
@@ -501,7 +506,7 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 					const uint32_t es = e.x >> (2u * kBatchXYBits), espp = p1.spp_index + es;
 					float eo_x, eo_y;
 					ld_random_pixel_offset(p1.snap_to_pixel_centers ? 0u : espp, eo_x, eo_y);
-					ray_origin_dir<EXTRA, true>(p1, x, y, eo_x, eo_y, o, d, espp);
+					ray_origin_dir<EXTRA, true>(p1, x, y, eo_x, eo_y, o, d, espp, (VIEWS && a1.views) ? a1.views + es : nullptr);
 					out_idx = pixel_out_idx(a1, x, y) + es * a1.slab_stride;
 				} else {
 				ray_origin_dir<EXTRA>(p1, x, y, off_x, off_y, o, d); // same arithmetic as at enqueue time -> same bits
@@ -839,8 +844,13 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 		const nrs_render_params& p3 = a3.p;
 		NRS_PHASE(5); // composite + march + shade
 		// (read here, not in front of the frame loop: six scalar registers that would otherwise live through every phase)
-		const f3 cam_fwd = mk3(p3.camera_matrix1[6], p3.camera_matrix1[7], p3.camera_matrix1[8]);
-		const f3 cam_o = mk3(p3.camera_matrix1[9], p3.camera_matrix1[10], p3.camera_matrix1[11]);
+		f3 cam_fwd = mk3(p3.camera_matrix1[6], p3.camera_matrix1[7], p3.camera_matrix1[8]);
+		f3 cam_o = mk3(p3.camera_matrix1[9], p3.camera_matrix1[10], p3.camera_matrix1[11]);
+		if (VIEWS && a3.views) { // the lane's sample has its own camera: re-read here, where it is used, not kept through the round (out_idx < spp_count * slab_stride)
+			const NRS_GLOBAL float* c1 = (const NRS_GLOBAL float*)(a3.views + (have ? out_idx / a3.slab_stride : 0u)) + 12; // camera_matrix1
+			cam_fwd = mk3(c1[6], c1[7], c1[8]);
+			cam_o = mk3(c1[9], c1[10], c1[11]);
+		}
 		// ---- composite_kernel_nerf body (tn:750-955, Shade mode) + next-sample march ----
 		uint32_t it_march = 0;
 		if (PROF) { pf_walk[4] += (lane == 0) ? 1u : 0u; pf_walk[5] += have ? 1u : 0u; }

@@ -57,7 +57,7 @@ int launch_row(const DeviceModel& m, const RenderArgs& a, int n_cus, hipStream_t
 	return NRS_OK;
 }
 
-// This shard's rows: the single-frame launcher of each and, where the row has one, its batch twin.  Naming them in a class that is instantiated explicitly is what
+// This shard's rows: of each, the single-frame launcher and the batch twin that the row has.  Naming them in a class that is instantiated explicitly is what
 // instantiates them here (a __launch_bounds__(512, 4) twin is instantiated from inside its row's launch_row: the same shard).
 template <int SHARD, typename Rows>
 struct RowShard;
@@ -65,7 +65,7 @@ template <int SHARD, int... ROW>
 struct RowShard<SHARD, std::integer_sequence<int, ROW...>> {
 	template <int R>
 	static constexpr RouteLauncher single() {
-		if constexpr (R % NRS_ROW_SHARDS == SHARD) return &launch_row<R, false>;
+		if constexpr (R % NRS_ROW_SHARDS == SHARD && kRoutes[R].single) return &launch_row<R, false>;
 		else return nullptr;
 	}
 	template <int R>

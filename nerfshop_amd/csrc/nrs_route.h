@@ -3,6 +3,7 @@
 //   plan_route   a request (model, operators, parameters, context, development knobs) -> a refusal, or a row plus the schedule fields of RenderArgs
 // Host-only, plain C++17, no HIP types, no getenv, no statics: the planner is a pure function (tests/test_route_plan_host.py sweeps it without a GPU).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/nrs.h"
@@ -19,6 +20,7 @@ constexpr int kXtraDeep = 5;       // that layer and nothing else of EXTRA: the 
 constexpr int kXtraGate = 6;       // the plain kernel with the L2 phase gate on the four finest hashed levels (cone-stepping scenes)
 constexpr int kXtraLight = 7;      // a network trained with light directions: the light term and nothing else (the twin of the default kernel)
 constexpr int kXtraLightAll = 8;   // the catch-all of such a network: EXTRA + INTRO, the third hidden layer where the network has one (a run-time branch)
+constexpr int kXtraExtraViews = 9; // 1 on the lean row (no POISSON, no AFFINE) with the view table of nrs_render_nerf_spp_views compiled in: that row's BATCH twin of 1 carries none
 struct XtraTraits { bool extra, intro, deep, light, gate; };
 constexpr XtraTraits xtra_traits(int xtra) {
 	switch (xtra) {
@@ -30,9 +32,17 @@ constexpr XtraTraits xtra_traits(int xtra) {
 	case kXtraGate:      return {false, false, false, false, true};
 	case kXtraLight:     return {false, false, false, true, false};
 	case kXtraLightAll:  return {true, true, true, true, false};
+	case kXtraExtraViews: return {true, false, false, false, false};
 	default:             return {false, false, false, false, false};
 	}
 }
+// Does this instantiation read RenderArgs::views?  Every BATCH twin does, behind a wave-uniform branch, but the lean EXTRA row's (XTRA 1 without POISSON and AFFINE): the
+// table's reads take it from 123 to 133 VGPRs, from 4 to 3 waves per SIMD, so its still batch keeps the twin it had and its views batch has one of its own (XTRA 9).
+// The kernel (render_body) and the launch's last guard (check_route) both ask here.
+constexpr bool route_carries_views(bool poisson, bool affine, int xtra, bool batch) { return batch && !(xtra == kXtraExtra && !poisson && !affine); }
+constexpr bool same_traits(XtraTraits a, XtraTraits b) { return a.extra == b.extra && a.intro == b.intro && a.deep == b.deep && a.light == b.light && a.gate == b.gate; }
+static_assert(same_traits(xtra_traits(kXtraExtraViews), xtra_traits(kXtraExtra)), "XTRA 9 is XTRA 1 with the view table: the same body otherwise");
+static_assert(route_carries_views(false, false, kXtraExtraViews, true) && !route_carries_views(false, false, kXtraExtra, true), "of the two lean EXTRA twins, XTRA 9 reads the view table");
 constexpr int kNumRuntime = -1; // NUM: tiny-cuda-nn's other roundings chosen at run time from DeviceModel::numerics (nrs_mlp.cuh encode_num)
 
 // ---- one instantiation ----------------------------------------------------------------------------------------------------------------------------------
@@ -57,10 +67,12 @@ enum RouteId : int {
 	kRtExtra, kRtExtraNumRt, kRtIntro, kRtIntroNumRt, kRtDeepExtra, kRtDeepExtraNumRt, kRtDeepIntro, kRtDeepIntroNumRt,
 	kRtLightAuto, kRtLightAll,
 	kRtProfAuto, kRtProf1, kRtCfg84Auto, kRtCfg84_1, kRtCfg84_2, kRtCfg84_4, kRtCfg84AffineAuto, kRtCfg42, kRtCfg124,
+	kRtExtraLeanViews,
 	kRouteCount
 };
 // batch: the row has a BATCH twin, the instantiation that serves a queue of several samples (nrs_render_nerf_spp).  The measurement rows have none.
-struct RouteRow { RouteId id; RouteTraits t; bool batch; };
+// single: the row has a single-frame instantiation.  Every row but the one that exists for views batches alone.
+struct RouteRow { RouteId id; RouteTraits t; bool batch; bool single = true; };
 
 // TEAM 0 = the wave decides (automatic schedule: all-tail or hybrid queues); 1 / 2 / 4 = fixed lanes per ray.  A row's TEAM is what sizes the launch's packets.
 constexpr RouteRow kRoutes[kRouteCount] = {
@@ -107,6 +119,7 @@ constexpr RouteRow kRoutes[kRouteCount] = {
 	// a lean instantiation without the membrane and AffineDuplication code: 123 VGPRs on the 128-register entry point, 8-wave workgroups, 4 waves per SIMD instead of
 	// the catch-all's 145 at 3)
 	{kRtExtraLean,   {kEntryC128, 8, 3, false, false, false, 1, 0, kXtraExtra}, true},
+	// (its views batches run kRtExtraLeanViews, the last row)
 	// the EXTRA catch-alls: every operator kind, membrane correction, one lane per ray.  Normals / EncodingVis: the INTRO instantiation (145 / 165 VGPRs, no scratch:
 	// 12-wave workgroups at 3 waves per SIMD like the other modes); the DEEP twins of both for a network with a third rgb hidden layer, every mode
 	{kRtExtra,           {kEntryCfg, 12, 3, false, true, true, 1, 0, kXtraExtra}, true},
@@ -136,6 +149,10 @@ constexpr RouteRow kRoutes[kRouteCount] = {
 	// two selection fragments in the LDS image, ten waves no longer fit the LDS budget of two workgroups per CU either)
 	{kRtCfg42,       {kEntryCfg, 4, 2, false, false, false, 1, 0, kXtraNone}, false},
 	{kRtCfg124,      {kEntryCfg, 12, 3, false, true, false, 0, 0, kXtraNone}, false}, // (A/B: one 12-wave workgroup per CU at 3 waves per SIMD, 136 VGPRs, no scratch)
+	// ---- a production row again, last so that every row above keeps its number and with it its shard of nrs_render_rows.hip ----
+	// the views batches (nrs_render_nerf_spp_views) of kRtExtraLean: the same body with the view table's reads, 133 VGPRs, 3 waves per SIMD.  A BATCH twin only: the still
+	// batch and the single frame of kRtExtraLean compile as they did without it (123 VGPRs, 4 waves per SIMD)
+	{kRtExtraLeanViews, {kEntryC128, 8, 3, false, false, false, 1, 0, kXtraExtraViews}, true, false},
 };
 constexpr bool routes_in_order() {
 	for (int i = 0; i < kRouteCount; ++i)
@@ -167,7 +184,10 @@ struct RouteRequest {
 	// parameters
 	uint32_t render_mode, show_accel, dof_on, distortion_mode, distortion_map, envmap, glow_mode;
 	float    cone_angle_constant;
-	uint32_t tile_size, height, spp_count;
+	uint32_t tile_size, height;
+	uint16_t spp_count;        // samples in the launch's queue (<= NRS_SPP_BATCH_MAX)
+	uint16_t views;            // the samples have a view each (nrs_render_nerf_spp_views).  The two halves of what was one 32-bit spp_count: a mirror that writes the count
+	                           // as one little-endian word still says "no views"
 	// context
 	int32_t  lane_teams, n_cus;
 	uint32_t busy;             // OTHER streams of the context with an unfinished launch
@@ -175,6 +195,8 @@ struct RouteRequest {
 	double   hit_share;        // share of the pixels that became rays in the last finished launch
 	RouteKnobs knobs;
 };
+static_assert(offsetof(RouteRequest, spp_count) == 68 && offsetof(RouteRequest, views) == 70 && offsetof(RouteRequest, lane_teams) == 72,
+              "spp_count and views are the low and the high half of the word that was a 32-bit spp_count (a little-endian host: gfx950's are)");
 struct RoutePlan {
 	int      status;           // NRS_OK, or the refusal (then `message` says why and `row` is -1)
 	char     message[256];
@@ -188,6 +210,7 @@ struct RoutePlan {
 	int32_t  forced;
 	uint32_t fill_lanes_auto;
 	double   rays_per_lane;
+	uint32_t views;            // the launch carries a view table (a views request of more than one sample): the schedule word's bit 19
 	// lanes on a pixel of the packets tile_geometry cuts: 64 / packet_lanes pixels per packet
 	uint32_t packet_lanes() const { return all_tail ? fill_lanes : (team ? team : 1u); }
 };
@@ -301,8 +324,12 @@ inline RoutePlan plan_route(const RouteRequest& q) {
 	} else {
 		row = want == 0 ? kRtDefaultAuto : (want == 2 ? kRtDefault2 : (want == 4 ? kRtDefault4 : kRtDefault1));
 	}
+	// A view per sample (q.views): every BATCH twin carries the view table behind a wave-uniform branch, so the row of the still batch serves it -- but the lean EXTRA row,
+	// whose views batches have a row of their own (route_carries_views).  A views request of one sample is a single frame of that view.
+	r.views = (batch && q.views) ? 1u : 0u;
+	if (r.views && row == kRtExtraLean) row = kRtExtraLeanViews;
 	const RouteRow& rr = kRoutes[row];
-	if (batch && !rr.batch) { // (cannot happen: the measurement rows are reached through the knobs refused above)
+	if ((batch && !rr.batch) || (!batch && !rr.single)) { // (cannot happen: the measurement rows are reached through the knobs refused above, the views row by a batch alone)
 		snprintf(r.message, sizeof(r.message), "launch_render: route refused: no instantiation for a batch of samples (spp_count %u) on this route", q.spp_count);
 		return refuse(NRS_ERR_STATE);
 	}

@@ -534,6 +534,11 @@ class Testbed:
         mn, mx = list(desc.aabb_min), list(desc.aabb_max)
         self.render_aabb = (mn, mx)       # m_render_aabb
         self.last_stats = None
+        self.m_camera = None              # m_camera: 3x4 column-major [12]; set by set_camera_from_time / render_to_cpu
+        self.m_smoothed_camera = None     # m_smoothed_camera: the camera the last frame ended on
+        self.camera_smoothing = False     # m_camera_smoothing
+        self.fov, self.fov_axis = 50.625, 1   # fov() in degrees (set_camera_from_time sets it), m_fov_axis
+        self.camera_path = []             # m_camera_path.m_keyframes: a list of _abi.CameraKeyframe
 
     def add_edit_operator(self, op):
         self.edit_operators.append(op)
@@ -610,16 +615,104 @@ class Testbed:
         self.last_stats = stats
         return stats
 
+    def render_spp_with_views(self, network, p, views, frames, depths, steps=None, slab_stride_pixels=None, stream=None, want_stats=False, spp_count=None):
+        """nrs_render_nerf_spp_views: slab k receives sample p.spp_index + k rendered with views[k] (a ctypes array of _abi.SampleView, or a list of them) in place of
+        p's cameras, focal length, dof and slice_plane_z.  One launch for the whole batch.  views = None is nrs_render_nerf_spp of `spp_count` samples; spp_count
+        defaults to len(views)."""
+        _require_cuda(frames, torch.float32, "frames")
+        _require_cuda(depths, torch.float32, "depths")
+        if views is not None and not isinstance(views, C.Array):
+            views = (_abi.SampleView * max(len(views), 1))(*views)
+        if spp_count is None:
+            spp_count = len(views)
+        if slab_stride_pixels is None:
+            slab_stride_pixels = frames[0].numel() // 4 if frames.dim() > 1 and frames.shape[0] else 0
+        n = len(self.edit_operators)
+        arr = (C.c_void_p * max(n, 1))(*[op.h for op in self.edit_operators])
+        stats = RenderStats() if want_stats else None
+        check(self.lib.nrs_render_nerf_spp_views(network.h, C.byref(p), arr, n, int(spp_count), C.cast(views, C.c_void_p) if views is not None else None, frames.data_ptr(), depths.data_ptr(),
+                                                 steps.data_ptr() if steps is not None else None, int(slab_stride_pixels), _stream_handle(stream),
+                                                 C.byref(stats) if stats is not None else None))
+        self.last_stats = stats
+        return stats
+
+    # ---- the camera path (CameraPath, Testbed::set_camera_from_time / apply_camera_smoothing) ----
+    def load_camera_path(self, path):
+        """Testbed::load_camera_path -> CameraPath::load (src/camera_path.cu:114-136): the keyframes of a file CameraPath::save wrote; returns their number"""
+        h = C.c_void_p()
+        check(self.lib.nrs_camera_path_open(os.fsencode(path), C.byref(h)))
+        try:
+            n = self.lib.nrs_camera_path_count(h)
+            keys = (_abi.CameraKeyframe * max(n, 1))()
+            check(self.lib.nrs_camera_path_keyframes(h, C.cast(keys, C.c_void_p), n))
+        finally:
+            self.lib.nrs_camera_path_close(h)
+        self.camera_path = [keys[i] for i in range(n)]
+        return n
+
+    def _path_array(self):
+        n = len(self.camera_path)
+        return (_abi.CameraKeyframe * max(n, 1))(*self.camera_path), n
+
+    def set_camera_from_time(self, t):
+        """Testbed::set_camera_from_time (src/testbed.cu:2099-2111): m_camera, slice / scale, fov and dof from the path's keyframe at t; nothing without a path"""
+        keys, n = self._path_array()
+        if n == 0:
+            return
+        k = _abi.CameraKeyframe()
+        check(self.lib.nrs_camera_path_eval(C.cast(keys, C.c_void_p), n, float(t), C.byref(k)))
+        m = (C.c_float * 12)()
+        check(self.lib.nrs_camera_keyframe_matrix(C.byref(k), C.byref(m)))
+        self.m_camera = list(m)
+        self.slice_plane_z, self.scale, self.fov, self.dof = k.slice, k.scale, k.fov, k.dof
+
+    def log_space_lerp(self, begin, end, t):
+        a, b, out = (C.c_float * 12)(*[float(v) for v in begin]), (C.c_float * 12)(*[float(v) for v in end]), (C.c_float * 12)()
+        check(self.lib.nrs_log_space_lerp(C.byref(a), C.byref(b), float(t), C.byref(out)))
+        return list(out)
+
+    def apply_camera_smoothing(self, elapsed_ms):
+        """Testbed::apply_camera_smoothing (src/testbed.cu:2086-2093)"""
+        if self.camera_smoothing and self.m_smoothed_camera is not None:
+            decay = float(np.float32(0.02) ** np.float32(elapsed_ms / 1000.0))
+            self.m_smoothed_camera = self.log_space_lerp(self.m_smoothed_camera, self.m_camera, float(np.float32(1.0) - np.float32(decay)))
+        else:
+            self.m_smoothed_camera = list(self.m_camera)
+
+    def motion_views(self, start, end, shutter_fraction, spp_count, first_sample, spp_total, resolution, start_time, end_time, base_view):
+        """nrs_motion_views over this testbed's camera path -> a ctypes array of spp_count _abi.SampleView"""
+        keys, n = self._path_array()
+        a, b = (C.c_float * 12)(*[float(v) for v in start]), (C.c_float * 12)(*[float(v) for v in end])
+        res = (C.c_int32 * 2)(int(resolution[0]), int(resolution[1]))
+        out = (_abi.SampleView * int(spp_count))()
+        check(self.lib.nrs_motion_views(C.byref(a), C.byref(b), float(shutter_fraction), int(spp_count), int(first_sample), int(spp_total), C.byref(res), int(self.fov_axis),
+                                        C.cast(keys, C.c_void_p) if n else None, n, float(start_time), float(end_time), C.byref(base_view), C.cast(out, C.c_void_p)))
+        return out
+
     def render_to_cpu(self, network, width, height, spp, linear, focal_length, camera_matrix0, camera_matrix1=None, rolling_shutter=(0.0, 0.0, 0.0, 0.0),
                       screen_center=(0.5, 0.5), exposure=0.0, background=(0.0, 0.0, 0.0, 0.0), fmt="rgba32f", tonemap_curve=0, color_space=0, apply_operators=True,
-                      stream=None):
-        """Testbed::render_to_cpu(width, height, spp, linear, ...) (src/python_api.cu:129-175) for a still camera (its camera-path smoothing is out of scope): the
-        accumulation is reset, `spp` samples of the view are rendered in batches of at most NRS_SPP_BATCH_MAX (one launch each) and folded into the running mean, and
-        the last fold is fused with the display step (tonemap: `background`, `exposure`, `tonemap_curve`; sRGB output unless `linear`).  Returns a host array [H, W, 4]:
-        float32 for fmt "rgba32f", uint8 for "rgba8".  The accumulate buffer stays readable as render_to_cpu_buffer().accumulate_buffer()."""
+                      stream=None, start_time=-1.0, end_time=-1.0, fps=30.0, shutter_fraction=1.0, motion_blur=None):
+        """Testbed::render_to_cpu(width, height, spp, linear, start_time, end_time, fps, shutter_fraction) (src/python_api.cu:129-175): the accumulation is reset, `spp`
+        samples are rendered in batches of at most NRS_SPP_BATCH_MAX (one launch each) and folded into the running mean, and the last fold is fused with the display
+        step (tonemap: `background`, `exposure`, `tonemap_curve`; sRGB output unless `linear`).  Returns a host array [H, W, 4]: float32 for fmt "rgba32f", uint8 for
+        "rgba8".  The accumulate buffer stays readable as render_to_cpu_buffer().accumulate_buffer().
+
+        A moving camera: with start_time >= 0 (the reference's own condition, python_api.cu:139) the frame runs from m_smoothed_camera to the (smoothed) camera of
+        end_time -- the path's keyframe there, or without keyframes camera_matrix1 (camera_matrix0 when that is None) -- and over a path every sample takes fov, dof and
+        focus plane from it at its own time.  Sample i renders between log_space_lerp(start, end, i / spp * shutter_fraction) and (i + 1) / spp * shutter_fraction
+        (nrs_motion_views), a view per sample in one launch per batch, and m_smoothed_camera is left at the end camera.
+
+        WHAT camera_matrix1 MEANS with start_time < 0 is decided by `motion_blur`.  False: the still call -- camera_matrix0 / camera_matrix1 go to every sample as they
+        are (the two cameras of a rolling shutter) and shutter_fraction is not looked at.  True: camera_matrix1 is the end-of-shutter camera of a frame that starts at
+        camera_matrix0, for every shutter_fraction, 1.0 included.  None (the default) is True exactly when shutter_fraction != 1.0: the reference's default shutter
+        keeps the call what it was before these arguments existed, bit for bit -- so a full-shutter blur between two cameras has to be asked for with motion_blur=True."""
         spp = int(spp)
         if spp < 1:
             raise ValueError("spp must be at least 1")
+        on_path = start_time >= 0.0
+        if on_path or (float(shutter_fraction) != 1.0 if motion_blur is None else bool(motion_blur)):
+            return self._render_to_cpu_moving(network, width, height, spp, linear, focal_length, camera_matrix0, camera_matrix1, rolling_shutter, screen_center, exposure,
+                                              background, fmt, tonemap_curve, color_space, apply_operators, stream, start_time, end_time, fps, shutter_fraction, on_path)
         buf = getattr(self, "_windowless", None)
         if buf is None or buf.in_resolution() != (int(width), int(height)):
             buf = self._windowless = RenderBuffer(width, height, device=f"cuda:{self.ctx.device}")   # m_windowless_render_surface.resize
@@ -636,6 +729,55 @@ class Testbed:
             else:
                 out = buf.accumulate_spp_tonemap(self.ctx, frames, exposure, background, 0 if linear else 1, fmt, stream)
             done += k
+        if stream is not None:
+            (stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream))).synchronize()
+        return out.cpu().numpy()
+
+    def _render_to_cpu_moving(self, network, width, height, spp, linear, focal_length, camera_matrix0, camera_matrix1, rolling_shutter, screen_center, exposure,
+                              background, fmt, tonemap_curve, color_space, apply_operators, stream, start_time, end_time, fps, shutter_fraction, on_path):
+        buf = getattr(self, "_windowless", None)
+        if buf is None or buf.in_resolution() != (int(width), int(height)):
+            buf = self._windowless = RenderBuffer(width, height, device=f"cuda:{self.ctx.device}")
+        buf.set_spp(0)
+        buf.set_color_space(color_space)
+        buf.set_tonemap_curve(tonemap_curve)
+        cam0 = [float(v) for v in np.asarray(camera_matrix0, np.float32).reshape(-1)]
+        if on_path:                                                    # python_api.cu:133-146
+            if end_time < 0.0:
+                end_time = start_time
+            start_cam = list(self.m_smoothed_camera) if self.m_smoothed_camera is not None else cam0
+            if self.m_smoothed_camera is None:
+                self.m_smoothed_camera = list(start_cam)
+            if not self.camera_path:   # set_camera_from_time leaves m_camera alone without keyframes: the caller's camera is the current one
+                self.m_camera = cam0 if camera_matrix1 is None else [float(v) for v in np.asarray(camera_matrix1, np.float32).reshape(-1)]
+            self.set_camera_from_time(end_time)
+            self.apply_camera_smoothing(1000.0 / fps)
+            end_cam = list(self.m_smoothed_camera)
+        else:
+            start_cam = cam0
+            end_cam = cam0 if camera_matrix1 is None else [float(v) for v in np.asarray(camera_matrix1, np.float32).reshape(-1)]
+            self.m_camera = list(end_cam)
+            start_time = -1.0
+        base = _abi.SampleView()
+        base.focal_length[:] = list(focal_length)
+        base.dof, base.slice_plane_z = self.dof, self.slice_plane_z + self.scale
+        done, out = 0, None
+        while done < spp:
+            k = min(spp - done, _abi.SPP_BATCH_MAX)
+            views = self.motion_views(start_cam, end_cam, shutter_fraction, k, done, spp, (width, height), start_time, end_time, base)
+            p = self.make_params(buf, focal_length, views[0].camera_matrix0, views[0].camera_matrix1, rolling_shutter, screen_center, apply_operators and self.enable_edits)
+            frames, depths, steps = buf.spp_slabs(k)
+            self.render_spp_with_views(network, p, views, frames, depths, steps, None, stream)
+            if done + k < spp:
+                buf.accumulate_spp(self.ctx, frames, stream, color_space)
+            else:
+                out = buf.accumulate_spp_tonemap(self.ctx, frames, exposure, background, 0 if linear else 1, fmt, stream)
+            done += k
+        if on_path:   # the loop's last set_camera_from_time: the testbed is left on the last sample's keyframe
+            a0 = np.float32(spp - 1) / np.float32(spp) * np.float32(shutter_fraction)
+            a1 = (np.float32(spp - 1) + np.float32(1.0)) / np.float32(spp) * np.float32(shutter_fraction)
+            self.set_camera_from_time(float(np.float32(start_time) + (np.float32(end_time) - np.float32(start_time)) * (a0 + a1) / np.float32(2.0)))
+        self.m_smoothed_camera = list(end_cam)                         # python_api.cu:167-168
         if stream is not None:
             (stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream))).synchronize()
         return out.cpu().numpy()
