@@ -1,4 +1,4 @@
-// nrs_internal.h -- PODs shared between the C++ host code (nrs_api.cpp) and the HIP kernels (nrs_render*.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip, nrs_cage.hip).
+// nrs_internal.h -- PODs shared between the C++ host code (nrs_api.cpp, nrs_api_*.cpp; their own header: nrs_host.h) and the HIP kernels (nrs_render*.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip, nrs_cage.hip).
 // Nothing here is part of the public ABI (that is include/nrs.h).
 #pragma once
 #include <stdint.h>
@@ -29,7 +29,7 @@ constexpr uint32_t kDensityW = 64 * 32 + 16 * 64;           // density MLP param
 constexpr uint32_t kRgbW = 64 * 32 + 64 * 64 + 16 * 64;     // rgb MLP params (base.json:52-58)
 // The kernels evaluate ONE network shape: base.json's (density 32 -> 64 -> 16, rgb 32 -> 64 -> 64 -> 16), plus an optional third rgb hidden layer.  The
 // other members of configs/nerf/'s family -- rgb network with 0 / 1 / 3 hidden layers, no rgb network at all -- are LOWERED onto it when their parameters
-// arrive (lower_weights, nrs_api.cpp): matrices of 0 / +-1 that reproduce the smaller network's values exactly.  The canonical blob the MFMA fragments are
+// arrive (lower_weights, nrs_api_lowering.cpp): matrices of 0 / +-1 that reproduce the smaller network's values exactly.  The canonical blob the MFMA fragments are
 // cut from: [Wd1 64x32 | Wd2 16x64 | Wr1 64x32 | Wr2 64x64 | Wr3 16x64 | Wr2b 64x64 (third hidden layer, base_3layer.json)].
 // A network trained with light directions (n_extra_dims = 3) appends Wr1x [64 x 16]: columns 32..47 of its [64 x 48] first rgb matrix (the warped light
 // direction and the Identity encoding's padding ones); zeros for every other network.
@@ -94,7 +94,7 @@ struct DeviceModel {
 	Box3            aabb;      // train aabb (m_aabb)
 	float           inv_diag[3]; // 1 / (aabb.max - aabb.min), exact when diag_pow2
 	uint32_t        diag_pow2; // every aabb extent is a power of two (always so for NGP scene boxes): x / d == x * (1/d) bit for bit
-	OccAccel        occ;       // marching shortcuts (filled per launch, see model_for_launch in nrs_api.cpp)
+	OccAccel        occ;       // marching shortcuts (filled per launch, see model_for_launch in nrs_api_model.cpp)
 	uint32_t        rgb_activation;
 	uint32_t        density_activation;
 	uint32_t        numerics;  // bit 0: nrs_grid_acc NETWORK, bit 1: nrs_mlp_acc FP16 (nrs_model_set_numerics); 0 = the default roundings
@@ -246,7 +246,7 @@ int launch_grid_update(const DeviceModel& m, const DeviceEdit* d_edits, int n_ed
                        float* d_grid, uint32_t* d_grid_tmp, int n_cus, void* stream);
 int launch_accumulate(uint32_t n_pixels, const float* d_frame, float* d_accum, uint32_t sample_count, int color_space, void* stream);
 int launch_accumulate_spp(uint32_t n_pixels, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count, float* d_accum, uint32_t sample_count, int color_space, void* stream);
-// the display step (tonemap_kernel) and the last fold of a view fused with it; p has been validated by the caller (nrs_api.cpp: check_tonemap_params)
+// the display step (tonemap_kernel) and the last fold of a view fused with it; p has been validated by the caller (nrs_api_display.cpp: check_tonemap_params)
 int launch_tonemap(uint32_t n_pixels, const float* d_accum, const nrs_tonemap_params& p, void* d_out, void* stream);
 int launch_accumulate_spp_tonemap(uint32_t n_pixels, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count, float* d_accum, uint32_t sample_count,
                                   const nrs_tonemap_params& p, void* d_out, void* stream);

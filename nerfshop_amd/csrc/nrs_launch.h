@@ -1,5 +1,5 @@
-// nrs_launch.h -- the launch-error plumbing of the device translation units: ONE thread-local message (nrs_launch.cpp), which nrs_api.cpp reads
-// through launch_last_error() after a launcher has returned anything but NRS_OK.
+// nrs_launch.h -- the launch-error plumbing of the device translation units: ONE thread-local message (nrs_launch.cpp), which the host units read
+// through launch_last_error() (NRS_LAUNCH, nrs_host.h) after a launcher has returned anything but NRS_OK.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>

@@ -12,7 +12,7 @@
 // v_mfma_f32_32x32x16_f16: A = a 32x16 weight tile (LDS, pre-arranged on the host), B = 16 x 32 samples.  The D tile of
 // one layer (lane = sample column, 16 rows per lane) is, after ReLU + fp16 rounding, directly the B operand of the next
 // layer: the k index of an MFMA is free as long as A and B agree, so the host arranges the weight tiles in the order the
-// D registers come out (make_weight_fragments in nrs_api.cpp).  No cross-lane shuffles between layers, no global
+// D registers come out (make_weight_fragments in nrs_api_lowering.cpp).  No cross-lane shuffles between layers, no global
 // intermediates.  The gathered features pass through a 4 KiB per-wave LDS slab only because the level loop is kept
 // rolled (small code, few live registers, which buys occupancy for the gather latency).
 //
@@ -732,7 +732,7 @@ __device__ __forceinline__ void hidden_layer_64(const half8* lds_w, const half8*
 }
 // RGB MLP [density out 16 | SH 16] -> 64 -> 64 -> 16 (3 used) for one block.  Same output row map.
 // DEEP instantiations take `deep_w` (wave-uniform; DeviceModel::wfrag when DeviceModel::rgb_deep, else null): a third hidden layer between the second and the
-// output layer, its fragments read from HBM (base_3layer.json; the other members of the family are lowered onto the two-layer shape, nrs_api.cpp lower_weights).
+// output layer, its fragments read from HBM (base_3layer.json; the other members of the family are lowered onto the two-layer shape, nrs_api_lowering.cpp lower_weights).
 // LIGHT instantiations take `light_w` (wave-uniform; DeviceModel::wfrag when DeviceModel::n_extra_dims, else null) and `lb`: a network trained with light
 // directions has a 48-wide input -- [density out 16 | SH 16 | Identity(light 3) padded with ones to 16] -- i.e. one more k step in layer 0 (25 MFMA issues per
 // block instead of 24), k order density, SH, light; its two A fragments R1L are read from HBM like the DEEP ones.  The instantiations without the flag are what

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void weight_fragments_kernel(const uint16_t* _
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= n) return;
 	const uint32_t k = src[i];
-	// (kFragOne / kFragMinusOne: the constants of the selection fragments and of lowered networks; bit 15: a negated weight -- lower_weights, nrs_api.cpp)
+	// (kFragOne / kFragMinusOne: the constants of the selection fragments and of lowered networks; bit 15: a negated weight -- lower_weights, nrs_api_lowering.cpp)
 	const uint32_t idx = k & (uint32_t)(kFragNegate - 1u);
 	frag[i] = k == kFragOne ? (uint16_t)0x3C00 : (k == kFragMinusOne ? (uint16_t)0xBC00 : (idx ? (uint16_t)(params[idx - 1u] ^ (k & kFragNegate)) : (uint16_t)0));
 }

@@ -28,6 +28,10 @@ def _rebuilt_if_touched(name):
     return objects, re.search(r" -o libnrs\.so\b", out) is not None
 
 
+# the units behind the C-ABI of include/nrs.h: what includes nrs_host.h
+API_OBJECTS = {"nrs_api", "nrs_api_lowering", "nrs_api_model", "nrs_api_network", "nrs_api_edit", "nrs_api_render", "nrs_api_display"}
+
+
 def _shards(objects):
     return {o for o in objects if o.startswith("nrs_render_rows_")}
 
@@ -53,5 +57,11 @@ def test_the_display_source_rebuilds_its_object_alone():
 def test_the_render_kernel_header_rebuilds_every_shard_and_no_streaming_object():
     objects, link = _rebuilt_if_touched("nrs_render.cuh")
     assert _shards(objects) == _all_shards(), objects
-    assert not objects & {"nrs_display", "nrs_tables", "nrs_occupancy", "nrs_cage", "nrs_render", "nrs_api"}, objects
+    assert not objects & ({"nrs_display", "nrs_tables", "nrs_occupancy", "nrs_cage", "nrs_render"} | API_OBJECTS), objects
+    assert link
+
+
+def test_the_host_header_rebuilds_the_host_units_and_no_device_object():
+    objects, link = _rebuilt_if_touched("nrs_host.h")
+    assert objects == API_OBJECTS, objects  # (and so no device object, no render shard, none of the host units that stand alone)
     assert link

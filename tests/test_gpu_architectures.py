@@ -2,7 +2,7 @@
 (base_{1,3}layer.json), no rgb network at all (base_nodir.json -> NerfNetworkNoDir, testbed.cu:2314-2353) and the smaller / larger hash tables (base_14 /
 small / big.json) -- through the C-ABI on an MI355X against the oracle, which evaluates every one of them natively (oracle/nrs_oracle.cpp rgb_mlp_one,
 network_inference_one).  The library LOWERS the 0- / 1-layer and the no-direction networks onto the kernels' one shape with 0 / +-1 matrices
-(nrs_api.cpp lower_weights): these tests are the proof that the lowered network computes the network it stands for.
+(nrs_api_lowering.cpp lower_weights): these tests are the proof that the lowered network computes the network it stands for.
 
 Tolerances: the network bar of tests/test_gpu_parity.py (<= 4 fp16 ulps or 2e-3 abs, > 90 % of the outputs bit-identical), frames the Shade bar
 (6e-3 max, 2e-4 mean).  What the lowering adds is exact (a sum with one non-zero term), so the bars do not widen; NerfNetworkNoDir's colour IS a density-network

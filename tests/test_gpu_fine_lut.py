@@ -61,7 +61,7 @@ probe("created", edit.vertices)
 pose = synth.deform_cage(edit.cage_vertices, tuple(t * scale for t in (0.07, 0.03, -0.02)), 33.0)
 op.update_cage(None, pose)
 torch.cuda.synchronize()
-# a move drops the fine table; the second frame rendered after it builds the new one (nrs_api.cpp: nrs_edit::fine_stale)
+# a move drops the fine table; the second frame rendered after it builds the new one (nrs_host.h: nrs_edit::fine_stale)
 tb = runtime.Testbed(ctx, desc, aabb_scale)
 tb.nerf_network.set_cell_cache(0)
 tb.nerf_network.set_params(synth.make_params(desc, sigma_raw=synth.default_sigma_raw(aabb_scale)))
