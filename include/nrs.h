@@ -32,6 +32,7 @@
  *   nrs_accumulate           <- CudaRenderBuffer::accumulate / accumulate_kernel                                   src/render_buffer.cu:540 / :217
  *   nrs_tonemap              <- CudaRenderBuffer::tonemap / tonemap_kernel                                         src/render_buffer.cu:562 / :471
  *   nrs_detile               <- (new) inverse of the multi-GPU tile packing, no reference counterpart
+ *   nrs_mesh_extract / nrs_mesh_from_density / nrs_mesh_write <- Testbed::marching_cubes src/testbed_nerf.cu:4614, marching_cubes_gpu / save_mesh src/marching_cubes.cu:730 / :760
  *
  * Conventions: every function returns NRS_OK (0) or a negative nrs_status; nrs_last_error() returns a
  * thread-local message.  All buffers named d_* are DEVICE pointers owned by the caller; h_* are HOST
@@ -700,6 +701,56 @@ int nrs_tonemap(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, con
 int nrs_accumulate_spp_tonemap(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_frames, size_t slab_stride_pixels, uint32_t spp_count,
                                float* d_accumulate, uint32_t sample_count, const nrs_tonemap_params* params, void* d_out);
 size_t nrs_tonemap_output_bytes(uint32_t width, uint32_t height, uint32_t output_format);
+
+/* ---- mesh extraction: marching cubes on the density field ------------------------------------------------------------------------------------ */
+/* Testbed::compute_marching_cubes_mesh / compute_and_save_marching_cubes_mesh (src/python_api.cu:105-127, src/testbed.cu:337-343) = Testbed::marching_cubes
+ * (src/testbed_nerf.cu:4614-4649) = get_density_on_grid + marching_cubes_gpu + compute_mesh_1ring + compute_mesh_vertex_colors (src/marching_cubes.cu:730-758, :656-662;
+ * src/testbed_nerf.cu:4515-4536), then save_mesh (src/marching_cubes.cu:760-896).  Callers detect these entry points by symbol (dlsym); NRS_ABI_VERSION is unchanged
+ * because no existing layout changes.  Not here: the Adam state of the vertices, trainable_verts, optimise_mesh_step, the UV unwrap.
+ *
+ * The case table is the library's own, generated at first use from a rule: the reference's numbering of corners, edges and mask bits; on a cube face
+ * with four crossed edges every SET corner is cut off on its own (the choice depends on the face's corners alone, so both cells of a face agree: no holes); loops over the
+ * crossed edges in order of their lowest edge, each fanned from the first edge, walking from the lowest, whose fan has no diagonal inside a cube face; winding such that
+ * (pb - pa) x (pa - pc) of a triangle (a, b, c) points out of the dense side, as accumulate_1ring and save_mesh expect.  Vertices are the reference's; which diagonals
+ * split a loop, and the pairing on ambiguous faces, are not.
+ *
+ * Host-only (no context, no GPU):
+ * nrs_marching_cubes_res <- get_marching_cubes_res (src/marching_cubes.cu:48-55): float arithmetic in the reference's order, each axis rounded up to a multiple of 16.
+ * nrs_marching_cubes_table: *row_len = length of a row (the longest row and its terminator: found by the generator); out (may be NULL) receives [256][*row_len] edge
+ *   numbers, three per triangle, terminated by -1.
+ * nrs_mesh_write <- save_mesh without its unwrap branch: the extension "ply" selects the ASCII PLY, anything else the OBJ (v with colours, vn, f a//a b//b c//c).  Positions
+ *   are written as (v - offset) / scale, normals normalised here (a zero normal stays zero), colour bytes (unsigned char)clamp(c * 255, 0, 255), faces in reversed index
+ *   order, the reference's printf formats.  A file that cannot be opened is NRS_ERR_INVALID_ARG with the path in the message.
+ *
+ * nrs_mesh_from_density <- marching_cubes_gpu + compute_mesh_1ring on the caller's lattice d_density[x + y * rx + z * rx * ry] (what nrs_density_on_grid writes), any res3d
+ *   with every axis >= 2.  A vertex sits on a lattice edge whose ends lie on different sides of thresh (f > thresh; a NaN counts as not above), at
+ *   (x + dt, y, z) * scale + aabb_min with dt = (thresh - f0) / (f1 - f0) and scale = (aabb_max - aabb_min) / res3d, product and sum separate.  The numbering is
+ *   DETERMINISTIC: vertices by ascending (point index, axis), triangles by ascending cell index and table order inside a cell -- one of the numberings the reference's atomic
+ *   counters can produce, and the same one every run.  n_verts_padded = (n_verts + 127) & ~127; padding rows are zero.  verts_smoothed (f32x4) and vert_normals (f32x3, not
+ *   normalised) are the sums of accumulate_1ring added per vertex in ascending triangle order: bit-reproducible, equal to the sequential sum.  An empty surface is 0 vertices,
+ *   0 triangles and a valid handle.  NRS_ERR_INVALID_ARG before any launch, with the argument named: a NULL pointer, an axis < 2, 3 * rx * ry * rz >= 2^31, a non-finite thresh
+ *   or box, aabb_max <= aabb_min on an axis.  The call SYNCHRONISES `stream`: once when the counts come back to size the arrays (the reference reads its counters back the
+ *   same way) and again before it returns, when its temporaries (4 bytes per lattice point, 4 per vertex) are released.
+ * nrs_mesh_extract <- Testbed::marching_cubes: res3d rounded up to multiples of 16 per axis, the lattice evaluated by nrs_density_on_grid's kernel (mask_with_density_grid as
+ *   there), the step above, then vertex colours for all n_verts_padded rows: dir = normalize(v - 0.5); network input (warp_position(v, model aabb), warp_dt(MIN_CONE_STEPSIZE),
+ *   warp_direction(dir)); the full network with the model's numerics and light direction; network_to_rgb with the model's rgb activation, linear_to_srgb when linear_colors.
+ *   nrs_mesh_color_inputs (test hook) writes those [n_verts_padded x 7] inputs of a mesh to d_coords_out.
+ * nrs_mesh_counts / _device / _download / _destroy: any out pointer may be NULL; d_colors is NULL for a mesh made by nrs_mesh_from_density (asking _download for its colours
+ *   is NRS_ERR_STATE); _download copies the padded rows and n_tris x 3 indices, synchronously. */
+typedef struct nrs_mesh nrs_mesh;
+int  nrs_marching_cubes_res(uint32_t res_1d, const float aabb_min[3], const float aabb_max[3], uint32_t res3d_out[3]);
+int  nrs_marching_cubes_table(int8_t* out, uint32_t* row_len);
+int  nrs_mesh_write(const char* path, uint32_t n_verts, const float* h_verts, const float* h_normals, const float* h_colors, uint32_t n_tris, const uint32_t* h_indices,
+                    float scale, const float offset[3]);
+int  nrs_mesh_from_density(nrs_ctx* ctx, void* stream, const uint32_t res3d[3], const float aabb_min[3], const float aabb_max[3], float thresh, const float* d_density,
+                           nrs_mesh** mesh_out);
+int  nrs_mesh_extract(nrs_model* model, void* stream, const uint32_t res3d[3], const float aabb_min[3], const float aabb_max[3], float thresh, int mask_with_density_grid,
+                      int linear_colors, nrs_mesh** mesh_out);
+int  nrs_mesh_color_inputs(nrs_model* model, void* stream, const nrs_mesh* mesh, float* d_coords_out);
+int  nrs_mesh_counts(const nrs_mesh* mesh, uint32_t* n_verts, uint32_t* n_verts_padded, uint32_t* n_tris);
+int  nrs_mesh_device(const nrs_mesh* mesh, const float** d_verts, const float** d_normals, const float** d_colors, const float** d_smoothed, const uint32_t** d_indices);
+int  nrs_mesh_download(const nrs_mesh* mesh, float* h_verts, float* h_normals, float* h_colors, float* h_smoothed, uint32_t* h_indices);
+void nrs_mesh_destroy(nrs_mesh* mesh);
 
 #ifdef __cplusplus
 }

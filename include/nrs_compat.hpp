@@ -7,6 +7,7 @@
 //   ngp::Testbed::render_nerf  src/testbed_nerf.cu:3066                                    -> nrs::compat::Testbed::render_nerf
 //   ngp::Testbed::render_to_cpu src/python_api.cu:129-175                                  -> nrs::compat::Testbed::render_to_cpu (+ load_camera_path,
 //                                                                                             set_camera_from_time, apply_camera_smoothing)
+//   ngp::Testbed::marching_cubes src/testbed_nerf.cu:4614 (+ compute_and_save_marching_cubes_mesh, get_marching_cubes_res) -> nrs::compat::Testbed::marching_cubes
 //
 // No Eigen / tiny-cuda-nn types: matrices are column-major float arrays (what Eigen::Matrix<float,3,4>::data() yields),
 // streams are passed as void* (hipStream_t), errors become std::runtime_error (the reference throws from CUDA_CHECK_THROW).
@@ -300,6 +301,51 @@ public:
 		check(nrs_render_nerf(network.get(), &p, edits.data(), (int)edits.size(), render_buffer.frame_buffer, render_buffer.depth_buffer, nullptr, stream,
 		                      stats),
 		      "nrs_render_nerf");
+	}
+
+	// ---- mesh extraction (src/testbed_nerf.cu:4614-4649, src/testbed.cu:337-343, src/marching_cubes.cu:48-55) ----
+	// m_mesh: the device-resident mesh of the last marching_cubes call (verts, vert_normals, vert_colors, verts_smoothed, indices behind nrs_mesh_device)
+	struct Mesh {
+		float thresh = 2.5f;           // m_mesh.thresh
+		nrs_mesh* handle = nullptr;
+		Mesh() = default;
+		Mesh(const Mesh&) = delete;
+		Mesh& operator=(const Mesh&) = delete;
+		~Mesh() { nrs_mesh_destroy(handle); }
+	} m_mesh;
+	float m_dataset_offset[3] = {0.f, 0.f, 0.f};      // m_nerf.training.dataset.offset (save_mesh writes (v - offset) / scale)
+	// Vector3i get_marching_cubes_res(uint32_t res_1d, const BoundingBox& aabb)
+	static void get_marching_cubes_res(uint32_t res_1d, const float aabb_min[3], const float aabb_max[3], int res3d_out[3]) {
+		uint32_t r[3];
+		check(nrs_marching_cubes_res(res_1d, aabb_min, aabb_max, r), "nrs_marching_cubes_res");
+		for (int i = 0; i < 3; ++i) res3d_out[i] = (int)r[i];
+	}
+	// int Testbed::marching_cubes(Vector3i res3d, const BoundingBox& aabb, float thresh): thresh == FLT_MAX means m_mesh.thresh; returns the number of triangles
+	int marching_cubes(NerfNetwork& network, const int res3d[3], const float aabb_min[3], const float aabb_max[3], float thresh, void* stream = nullptr) {
+		if (res3d[0] < 0 || res3d[1] < 0 || res3d[2] < 0) throw std::runtime_error("Testbed::marching_cubes: negative resolution");
+		if (thresh == 3.402823466e+38f) thresh = m_mesh.thresh;
+		const uint32_t r[3] = {(uint32_t)res3d[0], (uint32_t)res3d[1], (uint32_t)res3d[2]};
+		check(nrs_model_set_light_dir(network.get(), m_nerf.light_dir), "nrs_model_set_light_dir");
+		nrs_mesh* mesh = nullptr;
+		check(nrs_mesh_extract(network.get(), stream, r, aabb_min, aabb_max, thresh, 1, m_nerf.training_linear_colors ? 1 : 0, &mesh), "nrs_mesh_extract");
+		nrs_mesh_destroy(m_mesh.handle);
+		m_mesh.handle = mesh;
+		uint32_t n_tris = 0;
+		check(nrs_mesh_counts(mesh, nullptr, nullptr, &n_tris), "nrs_mesh_counts");
+		return (int)n_tris;
+	}
+	// void Testbed::compute_and_save_marching_cubes_mesh(const char* filename, Vector3i res3d, BoundingBox aabb, float thresh, bool unwrap_it): an empty box (NULL) is the render box
+	void compute_and_save_marching_cubes_mesh(NerfNetwork& network, const char* filename, const int res3d[3], const float* aabb_min = nullptr, const float* aabb_max = nullptr,
+	                                          float thresh = 2.5f, bool unwrap_it = false) {
+		if (unwrap_it) throw std::runtime_error("Testbed::compute_and_save_marching_cubes_mesh: unwrap_it (the UV unwrap and its texture) is not built");
+		const bool empty = !aabb_min || !aabb_max;
+		marching_cubes(network, res3d, empty ? m_render_aabb_min : aabb_min, empty ? m_render_aabb_max : aabb_max, thresh);
+		uint32_t n_padded = 0, n_tris = 0;
+		check(nrs_mesh_counts(m_mesh.handle, nullptr, &n_padded, &n_tris), "nrs_mesh_counts");
+		std::vector<float> verts((size_t)n_padded * 3), normals((size_t)n_padded * 3), colors((size_t)n_padded * 3);
+		std::vector<uint32_t> indices((size_t)n_tris * 3);
+		check(nrs_mesh_download(m_mesh.handle, verts.data(), normals.data(), colors.data(), nullptr, indices.data()), "nrs_mesh_download");
+		check(nrs_mesh_write(filename, n_padded, verts.data(), normals.data(), colors.data(), n_tris, indices.data(), m_dataset_scale, m_dataset_offset), "nrs_mesh_write");
 	}
 
 	// ---- Testbed::render_to_cpu and the camera state it moves (src/python_api.cu:129-175, src/testbed.cu:2086-2111) ----

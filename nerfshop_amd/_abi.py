@@ -189,12 +189,15 @@ EXPORTS = [
     "nrs_tonemap", "nrs_accumulate_spp_tonemap", "nrs_tonemap_output_bytes",
     "nrs_render_nerf_spp_views", "nrs_log_space_lerp", "nrs_camera_keyframe_matrix", "nrs_camera_keyframe_from_matrix", "nrs_camera_path_eval",
     "nrs_camera_path_open", "nrs_camera_path_count", "nrs_camera_path_keyframes", "nrs_camera_path_close", "nrs_motion_views",
+    "nrs_marching_cubes_res", "nrs_marching_cubes_table", "nrs_mesh_write", "nrs_mesh_from_density", "nrs_mesh_extract", "nrs_mesh_color_inputs",
+    "nrs_mesh_counts", "nrs_mesh_device", "nrs_mesh_download", "nrs_mesh_destroy",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
 COLOR_LINEAR, COLOR_SRGB, COLOR_VISPOSNEG = 0, 1, 2  # nrs_color_space
 TONEMAP_IDENTITY, TONEMAP_ACES, TONEMAP_HABLE, TONEMAP_REINHARD = 0, 1, 2, 3  # nrs_tonemap_curve
 TONEMAP_RGBA32F, TONEMAP_RGBA8 = 0, 1  # NRS_TONEMAP_RGBA32F / _RGBA8
+MESH_THRESH_DEFAULT = 2.5  # m_mesh.thresh as the reference's Python interface passes it (testbed.h:387)
 
 _lib = None
 
@@ -330,6 +333,20 @@ def load():
         lib.nrs_camera_path_close.argtypes = [P]
         lib.nrs_camera_path_close.restype = None
         lib.nrs_motion_views.argtypes = [F12, F12, C.c_float, U32, U32, U32, C.POINTER(C.c_int32 * 2), I, P, U32, C.c_float, C.c_float, C.POINTER(SampleView), P]
+    # mesh extraction (appended exports, detected by symbol like the spp batch)
+    if hasattr(lib, "nrs_mesh_from_density"):
+        F3, U3 = C.POINTER(C.c_float * 3), C.POINTER(U32 * 3)
+        lib.nrs_marching_cubes_res.argtypes = [U32, F3, F3, U3]
+        lib.nrs_marching_cubes_table.argtypes = [P, C.POINTER(U32)]
+        lib.nrs_mesh_write.argtypes = [C.c_char_p, U32, P, P, P, U32, P, C.c_float, F3]
+        lib.nrs_mesh_from_density.argtypes = [P, P, U3, F3, F3, C.c_float, P, C.POINTER(P)]
+        lib.nrs_mesh_extract.argtypes = [P, P, U3, F3, F3, C.c_float, I, I, C.POINTER(P)]
+        lib.nrs_mesh_color_inputs.argtypes = [P, P, P, P]
+        lib.nrs_mesh_counts.argtypes = [P, C.POINTER(U32), C.POINTER(U32), C.POINTER(U32)]
+        lib.nrs_mesh_device.argtypes = [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]
+        lib.nrs_mesh_download.argtypes = [P, P, P, P, P, P]
+        lib.nrs_mesh_destroy.argtypes = [P]
+        lib.nrs_mesh_destroy.restype = None
     lib.nrs_snapshot_open.argtypes = [C.c_char_p, C.POINTER(P)]
     lib.nrs_snapshot_close.argtypes = [P]
     lib.nrs_snapshot_close.restype = None

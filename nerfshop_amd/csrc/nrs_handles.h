@@ -1,0 +1,185 @@
+// nrs_handles.h -- the three opaque structs of include/nrs.h, the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
+// work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp) includes
+// this header alone.  Host-only C++17: no .hip / .cuh includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "nrs_internal.h"
+
+namespace nrs {
+
+// The thread-local message behind nrs_last_error() (nrs_api.cpp): both set it and return the status.
+int fail(int code, const std::string& msg);
+int fail_hip(hipError_t e, const char* what); // "<what>: <HIP's error string>", NRS_ERR_HIP
+
+// a HIP runtime call: the message quotes the failing expression
+#define HIP_TRY(call)                                           \
+	do {                                                        \
+		hipError_t e_ = (call);                                 \
+		if (e_ != hipSuccess) return nrs::fail_hip(e_, #call);  \
+	} while (0)
+// a host function that has set the message itself (fail / fail_hip / one of these macros): hand its status on
+#define NRS_TRY(call)                   \
+	do {                                \
+		int s_ = (call);                \
+		if (s_ != NRS_OK) return s_;    \
+	} while (0)
+// a launch_* function of the device units: they report through launch_last_error() (nrs_launch.cpp)
+#define NRS_LAUNCH(call)                                                  \
+	do {                                                                  \
+		int s_ = (call);                                                  \
+		if (s_ != NRS_OK) return nrs::fail(s_, nrs::launch_last_error()); \
+	} while (0)
+
+// The one owner of a device allocation: `count` elements of T from hipMalloc, freed when the owner goes.  Move-only.
+template <typename T>
+class DeviceBuffer {
+public:
+	DeviceBuffer() = default;
+	DeviceBuffer(DeviceBuffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+	DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+		if (this != &o) {
+			reset();
+			p_ = std::exchange(o.p_, nullptr);
+			n_ = std::exchange(o.n_, 0);
+		}
+		return *this;
+	}
+	DeviceBuffer(const DeviceBuffer&) = delete;
+	DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+	~DeviceBuffer() { reset(); }
+	// frees what it holds, then allocates (never less than 16 bytes: an empty array still has an address); holds nothing after a failure
+	hipError_t alloc(size_t count) {
+		reset();
+		const hipError_t e = hipMalloc((void**)&p_, std::max<size_t>(count * sizeof(T), 16));
+		if (e != hipSuccess) p_ = nullptr;
+		else n_ = count;
+		return e;
+	}
+	void reset() {
+		if (p_) (void)hipFree(p_);
+		p_ = nullptr;
+		n_ = 0;
+	}
+	T* get() const { return p_; }
+	size_t count() const { return n_; }
+
+private:
+	T* p_ = nullptr;
+	size_t n_ = 0;
+};
+
+} // namespace nrs
+
+struct nrs_ctx {
+	int lane_teams = 0; // nrs_ctx_set_lane_teams: 0 = automatic, 1 / 2 / 4 = lanes per ray for every render launch
+	int handover = -1;  // nrs_ctx_set_ray_handover: -1 = default (on; NRS_STEAL=0 turns it off), 0 / 1
+	unsigned long long last_handover = 0; // rays | hand-overs << 32 of the last launch that returned statistics
+	unsigned long long render_dispatches = 0; // render-kernel dispatches enqueued through this context, and the schedule of the last one (nrs_ctx_render_launches; under launch_mutex)
+	uint32_t last_schedule = 0;
+	int device = 0;
+	int n_cus = 0;
+	size_t hbm_bytes = 0;
+	char name[256] = {0};
+	// per-launch scratch comes from small rings so that render calls issued back to back on DIFFERENT streams (double-buffered
+	// frames) do not share a packet counter or an operator table: slot = launch number % kInFlight
+	static constexpr int kInFlight = 8;
+	nrs::DeviceBuffer<nrs::RenderCounters> d_counters;   // [kInFlight][2]: the render kernel of a slot zeroes the OTHER block for the slot's next launch (no memset between frames)
+	uint8_t counter_parity[kInFlight] = {};   // block the slot's next launch uses; counters_clean: that block is known to be zero
+	bool counters_clean[kInFlight] = {};
+	nrs::DeviceBuffer<nrs::DeviceEdit> d_edits;          // [kInFlight + 1][kMaxEdits]; the last table belongs to the occupancy refresh
+	nrs::DeviceBuffer<nrs_sample_view> d_views;     // [kInFlight][NRS_SPP_BATCH_MAX]: the view table of a slot's launch (nrs_render_nerf_spp_views)
+	std::atomic<uint32_t> launch_serial{0};
+	std::mutex launch_mutex; // slot acquisition .. launch enqueued: two threads rendering on one ctx must not share a slot's counter block / parity
+	// A slot is reused every kInFlight launches, possibly from ANOTHER stream: the launch that used it last records slot_done, and a
+	// launch on a different stream makes its stream wait on that event before it clears the counters / re-sends the operator table
+	// (same-stream reuse is ordered by the stream itself).
+	hipEvent_t slot_done[kInFlight] = {};
+	hipStream_t slot_stream[kInFlight] = {};
+	bool slot_used[kInFlight] = {};
+	nrs::DeviceBuffer<float> d_mean;
+	nrs::DeviceBuffer<unsigned long long> d_wave_log; // profiling only (NRS_DEBUG & 4)
+	unsigned long long* h_feedback = nullptr; // pinned, device-visible: written by the last workgroup of a render launch
+	unsigned long long* d_feedback = nullptr; // its device address
+	std::vector<nrs::DeviceEdit> edits_shadow = std::vector<nrs::DeviceEdit>((size_t)kInFlight * 32); // what each slot of d_edits holds
+	int shadow_n[kInFlight] = {-1, -1, -1, -1, -1, -1, -1, -1};
+	static constexpr int kMaxEdits = 32;
+};
+
+// (the cell-record cache's measured optimum on 1080p lego is 10 GiB = levels 0..11 of base.json's table, 9.2 GB: 12 levels 8.80, 14 levels (64 GB) 8.64, 10 levels 8.52,
+// none 8.05 Gsamples/s -- the budget a caller who opts in would pass: include/nrs.h MEMORY NOTE)
+
+struct nrs_model {
+	nrs_ctx* ctx = nullptr;
+	nrs_model_desc desc{};
+	uint32_t n_extra_dims = 0;      // 0, or 3: trained with light directions (nrs_model_create_ex)
+	float light_dir[3] = {0.5f, 0.5f, 0.5f}; // m_nerf.light_dir as the caller set it (testbed.h:639); normalised at use -> dm.light01
+	nrs::DeviceModel dm{};
+	uint32_t total_entries = 0;
+	nrs::DeviceBuffer<uint32_t> d_grid;
+	nrs::DeviceBuffer<uint16_t> d_wfrag;
+	nrs::DeviceBuffer<uint16_t> d_wfrag_src;     // make_weight_fragments as a permutation (source index + 1, 0 = padding), for nrs_model_set_params_device
+	nrs::DeviceBuffer<uint8_t> d_bitfield;
+	nrs::DeviceBuffer<uint32_t> d_accel_masks;   // 2 x kCoarseWords: accel_any.mask | accel_exact.mask
+	nrs::OccAccel accel_any{}, accel_exact{}; // marching shortcuts for general step parameters / for cone_angle == 0 && min_mip == 0
+	nrs::DeviceBuffer<float> d_density_grid;   // m_nerf.density_grid [5*128^3], kept for the occupancy refresh
+	nrs::DeviceBuffer<uint32_t> d_density_tmp; // density_grid_tmp (float bits), allocated on first refresh
+	bool have_params = false, have_bitfield = false;
+	// cell records of the first `cached_levels` levels (nrs_model_set_cell_cache)
+	nrs::DeviceBuffer<uint4> d_records;
+	size_t records_bytes = 0, cell_cache_budget = 0;
+	uint32_t cached_levels = 0;
+	// sparse brick records of the levels after them (nrs_model_set_sparse_cell_cache)
+	nrs::DeviceBuffer<uint32_t> d_bricks;   // brick tables of the sparse levels, concatenated
+	nrs::DeviceBuffer<uint32_t> d_slots;    // brick number of every allocated brick, per level (slot_first[l] .. +slot_count[l])
+	nrs::DeviceBuffer<uint4> d_records2;
+	size_t sparse_bytes = 0;        // tables + slots + records
+	uint32_t sparse_first = 0, sparse_levels = 0;
+	uint32_t slot_first[nrs::kLevels] = {}, slot_count[nrs::kLevels] = {};
+};
+
+struct nrs_edit {
+	nrs_ctx* ctx = nullptr;
+	nrs::DeviceEdit de{};
+	uint32_t n_vertices = 0, n_tets = 0;
+	// what a cage move does not rewrite
+	nrs::DeviceBuffer<float> d_orig;           // == de.orig
+	nrs::DeviceBuffer<uint32_t> d_tets;        // == de.tets
+	nrs::DeviceBuffer<uint8_t> d_orig_bitfield; // == de.orig_bitfield
+	nrs::DeviceBuffer<float> d_shs, d_out_density, d_res_density; // == de.shs / out_density / res_density once the operator holds membrane terms
+	// device-side authoring state (nrs_cage.hip): everything a cage move rewrites
+	nrs::DeviceBuffer<float> d_verts;          // == de.verts
+	nrs::DeviceBuffer<uint32_t> d_lut_off;     // == de.lut_off, [5*128^3 + 1]
+	nrs::DeviceBuffer<uint32_t> d_lut_idx;     // == de.lut_idx
+	size_t lut_idx_cap = 0;            // entries allocated
+	nrs::DeviceBuffer<float> d_rot;            // == de.rot when rotations are on
+	nrs::DeviceBuffer<float> d_planes;         // == de.planes, [T x 32] one 128-byte record per tet (tet_planes_kernel), follows the deformed vertices
+	nrs::DeviceBuffer<uint32_t> d_counts;      // [5*128^3], all zero between builds
+	nrs::DeviceBuffer<uint32_t> d_tile_sums;
+	nrs::DeviceBuffer<unsigned long long> d_hit_masks; // per (tet, cascade): the count pass's first 128 cell / tet tests (two words per item), reused by the fill pass (nrs_cage.hip tet_mark_kernel)
+	nrs::DeviceBuffer<uint32_t> d_scratch;     // [0..5] bbox (float bits), [6] total entries, [7] max tets per cell, [8] long-list counter
+	nrs::DeviceBuffer<uint32_t> d_big_cells;   // worklist of cells with long tet lists (sized with d_lut_idx)
+	nrs::DeviceBuffer<float> d_mvc;            // [V x n_cv] weights
+	nrs::DeviceBuffer<float> d_cage;           // [n_cv x 3]
+	uint32_t n_cv = 0;
+	uint32_t lut_n_idx = 0, lut_max_per_cell = 0;
+	// fine look-up table under the LUT (DeviceEdit::fine_*, nrs_cage.hip): rebuilt with the LUT
+	nrs::DeviceBuffer<uint32_t> d_fine_off;    // [fine_cells_cap + 1]
+	nrs::DeviceBuffer<uint32_t> d_fine_counts; // [fine_cells_cap]
+	nrs::DeviceBuffer<uint32_t> d_fine_idx;
+	nrs::DeviceBuffer<uint32_t> d_fine_tiles;  // [kFineScanTiles]
+	nrs::DeviceBuffer<int32_t> d_fine_win;     // [kCascades * 6] window + [30] total entries
+	size_t fine_cells_cap = 0, fine_idx_cap = 0;
+	uint32_t fine_n_idx = 0;
+	// A cage MOVE does not rebuild the fine table (0.3 ms of a 1.0 ms move at 6 k tets): it drops it -- the kernels scan the LUT's own lists, as before round 6 -- and
+	// the second nrs_render_nerf after the last move builds it (a gizmo drag renders one frame per move and never pays; a cage at rest renders 2-3 % faster)
+	bool fine_stale = false;
+	uint32_t renders_since_move = 0;
+};

@@ -493,6 +493,57 @@ class RenderBuffer:
         self._depth.zero_()
 
 
+class Mesh:
+    """nrs_mesh: a triangle mesh on the device (m_mesh's verts, vert_normals, vert_colors, verts_smoothed, indices)"""
+
+    def __init__(self, lib, handle):
+        self.lib, self.h = lib, handle
+        nv, npad, nt = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib.nrs_mesh_counts(handle, C.byref(nv), C.byref(npad), C.byref(nt)))
+        self.n_verts, self.n_verts_padded, self.n_tris = nv.value, npad.value, nt.value
+        ptrs = [C.c_void_p() for _ in range(5)]
+        check(lib.nrs_mesh_device(handle, *[C.byref(p) for p in ptrs]))
+        self.d_verts, self.d_normals, self.d_colors, self.d_smoothed, self.d_indices = [p.value for p in ptrs]
+
+    def download(self):
+        """-> (V [n_padded, 3], N [n_padded, 3] not normalised, C [n_padded, 3] or None, S [n_padded, 4], F uint32 [n_tris, 3]) numpy arrays"""
+        n, t = self.n_verts_padded, self.n_tris
+        V, N, S, F = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32), np.zeros((t, 3), np.uint32)
+        Cc = np.zeros((n, 3), np.float32) if self.d_colors else None
+        check(self.lib.nrs_mesh_download(self.h, V.ctypes.data, N.ctypes.data, Cc.ctypes.data if Cc is not None else None, S.ctypes.data, F.ctypes.data))
+        return V, N, Cc, S, F
+
+    def save(self, filename, scale=1.0, offset=(0.0, 0.0, 0.0)):
+        V, N, Cc, _, F = self.download()
+        if Cc is None:
+            Cc = np.zeros_like(V)
+        check(self.lib.nrs_mesh_write(os.fsencode(filename), V.shape[0], V.ctypes.data, N.ctypes.data, Cc.ctypes.data, F.shape[0], F.ctypes.data, float(scale),
+                                      C.byref((C.c_float * 3)(*offset))))
+
+    def close(self):
+        if self.h:
+            self.lib.nrs_mesh_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mesh_from_density(ctx, density, aabb_min, aabb_max, thresh, stream=None):
+    """marching_cubes_gpu + compute_mesh_1ring on a caller's field: a float32 CUDA tensor [rz, ry, rx] (what Testbed.get_density_on_grid returns) -> Mesh"""
+    _require_cuda(density, torch.float32, "density")
+    if density.dim() != 3 or not density.is_contiguous():
+        raise NrsError("mesh_from_density: density must be a contiguous [rz, ry, rx] tensor")
+    rz, ry, rx = density.shape
+    h = C.c_void_p()
+    check(ctx.lib.nrs_mesh_from_density(ctx.h, _stream_handle(stream), C.byref((C.c_uint32 * 3)(rx, ry, rz)), C.byref((C.c_float * 3)(*aabb_min)),
+                                        C.byref((C.c_float * 3)(*aabb_max)), float(thresh), density.data_ptr(), C.byref(h)))
+    return Mesh(ctx.lib, h)
+
+
 def set_camera_extras(p, render_distortion=None, distortion_map=None, envmap=None):
     """Camera model and background of an nrs_render_params (init_rays_from_camera's arguments, testbed_nerf.cu:3078-3100): lens distortion (mode, 7 params),
     the distortion map [H, W, 2] and the environment map [H, W, 4] as float32 CUDA tensors (the struct keeps raw device pointers: keep the tensors alive)."""
@@ -794,6 +845,48 @@ class Testbed:
         check(self.lib.nrs_density_on_grid(self.nerf_network.h, _stream_handle(stream), C.byref(res), C.byref(mn), C.byref(mx),
                                            1 if mask_with_density_grid else 0, out.data_ptr()))
         return out
+
+    # ---- mesh extraction (Testbed::marching_cubes and its Python callers) ----
+    @staticmethod
+    def get_marching_cubes_res(res_1d, aabb_min, aabb_max):
+        """get_marching_cubes_res(res_1d, aabb) (marching_cubes.cu:48) -> (rx, ry, rz), each a multiple of 16; host-only"""
+        out = (C.c_uint32 * 3)()
+        check(_abi.load().nrs_marching_cubes_res(int(res_1d), C.byref((C.c_float * 3)(*aabb_min)), C.byref((C.c_float * 3)(*aabb_max)), C.byref(out)))
+        return tuple(out)
+
+    def _mesh_aabb(self, aabb):
+        if aabb is None or len(aabb) == 0:   # aabb.is_empty(): the render box (python_api.cu:106-108)
+            return self.render_aabb
+        return aabb
+
+    def marching_cubes(self, res3d, aabb=None, thresh=_abi.MESH_THRESH_DEFAULT, mask_with_density_grid=True, stream=None):
+        """Testbed::marching_cubes(res3d, aabb, thresh) (testbed_nerf.cu:4614): the mesh stays on the testbed (self.mesh, m_mesh); returns the number of triangles."""
+        if np.isscalar(res3d):
+            res3d = (res3d,) * 3
+        mn, mx = self._mesh_aabb(aabb)
+        h = C.c_void_p()
+        check(self.lib.nrs_mesh_extract(self.nerf_network.h, _stream_handle(stream), C.byref((C.c_uint32 * 3)(*[int(v) for v in res3d])), C.byref((C.c_float * 3)(*mn)),
+                                        C.byref((C.c_float * 3)(*mx)), float(thresh), 1 if mask_with_density_grid else 0, 1 if self.linear_colors else 0, C.byref(h)))
+        if getattr(self, "mesh", None) is not None:
+            self.mesh.close()
+        self.mesh = Mesh(self.lib, h)
+        return self.mesh.n_tris
+
+    def compute_marching_cubes_mesh(self, res3d=128, aabb=None, thresh=_abi.MESH_THRESH_DEFAULT):
+        """Testbed::compute_marching_cubes_mesh (python_api.cu:105-127) -> {"V", "N", "C": float32 [n_verts_padded, 3], "F": int32 [n_tris, 3]}; N normalised on the host"""
+        self.marching_cubes(res3d, aabb, thresh)
+        V, N, Cc, _, F = self.mesh.download()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sq = (N * N).sum(axis=1, dtype=np.float32)
+            N = np.where(sq[:, None] > 0, N / np.sqrt(sq, dtype=np.float32)[:, None], N).astype(np.float32)   # Eigen's normalize(): a zero vector stays
+        return {"V": V, "N": N, "C": Cc, "F": F.view(np.int32)}
+
+    def compute_and_save_marching_cubes_mesh(self, filename, res3d=128, aabb=None, thresh=_abi.MESH_THRESH_DEFAULT, unwrap_it=False, dataset_offset=(0.0, 0.0, 0.0)):
+        """Testbed::compute_and_save_marching_cubes_mesh (testbed.cu:337-343): positions go out as (v - dataset offset) / dataset scale; .ply is a PLY, anything else an OBJ"""
+        if unwrap_it:
+            raise NrsError("compute_and_save_marching_cubes_mesh: unwrap_it (the UV unwrap and its texture) is not built")
+        self.marching_cubes(res3d, aabb, thresh)
+        self.mesh.save(filename, self.dataset_scale, dataset_offset)
 
     def project_selection_pixels(self, params, pixels_xy, transmittance_threshold=0.1, automatic_max_level=True, growing_level=0, stream=None):
         """GrowingSelection::project_selection_pixels (growing_selection.cu:1832): scribbled pixels -> surface points and the
