@@ -752,6 +752,68 @@ int  nrs_mesh_device(const nrs_mesh* mesh, const float** d_verts, const float** 
 int  nrs_mesh_download(const nrs_mesh* mesh, float* h_verts, float* h_normals, float* h_colors, float* h_smoothed, uint32_t* h_indices);
 void nrs_mesh_destroy(nrs_mesh* mesh);
 
+/* ---- selection tool: region growing, morphology, the fine mesh -------------------------------------------------------------------------------- */
+/* What lies between nrs_project_selection_pixels / nrs_selection_cells (the seed cells) and the cage: RegionGrowing (src/editing/tools/region_growing.cu),
+ * CorrectMMOperations (src/editing/tools/correct_mm_operations.cu) and GrowingSelection::dilate / erode / extract_fine_mesh (src/editing/tools/growing_selection.cu:2083-2162).
+ * Callers detect these entry points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  Not here: the Automatic growing mode (not
+ * implemented in the reference either), the proxy cage (progressive hulls), fTetWild, MeshFix.
+ *
+ * A selection handle holds m_density_grid_host, m_max_cascade, the selection bitfield S (density-bitfield layout: bit morton3D(x, y, z) of level l at byte
+ * (l * 128^3 + idx) / 8), the ordered cell list L = m_selection_cell_idx WITH its duplicates, the FIFO queue Q, the growing level g, m_performed_closing and the two
+ * structuring elements (dilation Cube 2, erosion Sphere 2: correct_mm_operations.h:70).  Growing is host-only (no context, no GPU): its result depends on pop order.
+ *
+ * nrs_selection_create: copies h_density_grid; n_floats != 5 * 128^3 or max_cascade > 4 is NRS_ERR_INVALID_ARG.  nrs_selection_destroy releases it.
+ * nrs_selection_reset <- reset_growing (region_growing.cu:10-55): S, Q, L cleared; every seed whose level is <= growing_level enters Q and L in input order, lifted
+ *   with nrs_upper_cell_idx; higher seeds are dropped; seeds enter L but NOT S; performed_closing cleared.  g := growing_level here already (the reference leaves
+ *   m_growing_level to the grow_region that follows, whose caller passes the same value), so the accessors describe the seeds at their level before any growth.  A seed >= 5 * 128^3 or growing_level > 4: NRS_ERR_INVALID_ARG.
+ * nrs_selection_grow <- grow_region, Manual mode (:93-141): nothing happens on an empty queue; g := growing_level; at most growing_steps entries are popped (*n_popped,
+ *   may be NULL); a popped cell is accepted iff its bit is clear and grid[cell] >= density_threshold and its level is g; an accepted cell on the grid's shell (is_boundary,
+ *   selection_utils.cu:8) first upscales the selection (below) and is lifted with it, accepted without a second test; acceptance pushes the up to six neighbours in the order
+ *   -x, -y, -z, +x, +y, +z (add_neighbours, :15-34), appends the cell to L and sets its bit.  performed_closing is cleared.  A non-finite density_threshold or
+ *   growing_level > 4: NRS_ERR_INVALID_ARG.
+ * nrs_selection_upscale <- upscale_selection (:57-91): nothing at g == max_cascade (and at g == 4, the last level there is); else g + 1, S rebuilt from L lifted one
+ *   level (L keeps its length and duplicates), every entry of Q lifted.
+ * nrs_selection_state: any out pointer may be NULL.  nrs_selection_get_cells: L as cells [n_cells] and / or as points [n_cells x 3] = get_cell_pos (selection_utils.cu:65)
+ *   of each cell at its own level, in the reference's float operation order.  nrs_selection_get_bitfield: S [NRS_BITFIELD_BYTES].
+ * nrs_selection_set_structuring_elements: type NRS_SE_CUBE (|i|, |j|, |k| <= r) or NRS_SE_SPHERE (i^2 + j^2 + k^2 <= r^2), radius 1..10, for each of the two operations;
+ *   anything else is NRS_ERR_INVALID_ARG.
+ *
+ * nrs_bitfield_morph <- CorrectMMOperations::dilate / erode (correct_mm_operations.cu:117-187) on the device.  op NRS_MORPH_DILATE: a cell of `level` is set iff any
+ *   IN-GRID tap of the element is set (hit); NRS_MORPH_ERODE: iff no in-grid tap is clear (fit).  Taps outside the grid are ignored: dilation never wraps, erosion treats the
+ *   outside as set, a full grid erodes to a full grid.  d_in and d_out are whole bitfields (NRS_BITFIELD_BYTES, 16-byte aligned, not overlapping); only `level` of d_in is
+ *   read; in d_out every other level is ZERO when the call completes, as in the reference.  SCRATCH CONTRACT: the call allocates nothing and is asynchronous on
+ *   `stream`; until it completes there, two of d_out's OTHER levels hold its intermediate rows, so no level of d_out may be read or written by other work (another
+ *   stream, the host) while the call is in flight -- not even the levels the call only zeroes.  The kernels work on packed words: the level is re-packed to x-major rows, the x extent of each (dy, dz) row of the element is done with
+ *   word shifts and carries, rows are combined with OR (on the complement for erosion), and the result is packed back.  NRS_ERR_INVALID_ARG before any launch, with the
+ *   argument named: a NULL or misaligned pointer, overlapping bitfields, level > 4, radius outside 1..10, an unknown op or element.
+ * nrs_bitfield_morph_host: the same contract on host pointers, as the reference's loops on one thread (a loop over the taps of every cell that ends at the first hit /
+ *   miss; a tap is a load from an unpacked copy of the level, not a Morton encode, the taps of one (i, j) column are a run clipped to the grid, and a column of the
+ *   grid that holds no set -- for erosion no clear -- cell is passed over): the CPU twin for tests and the baseline of tools/selection_mesh_probe.py.
+ * nrs_selection_dilate / _erode <- GrowingSelection::dilate / erode (growing_selection.cu:2083-2093): S := op(S) at level g on the device with the handle's element,
+ *   then L is rebuilt from S in the reference's loop order (x outer, y, z inner).  Synchronous.  performed_closing is not touched.
+ * nrs_selection_fine_mesh <- extract_fine_mesh (:2096-2162): if use_morphological and not performed_closing: dilate, erode, set the flag.  Then a 128^3 float lattice is
+ *   built on the device (x + 128 y + 128^2 z; 1.0 at every cell of L whose level is g and which is not on the grid's shell -- L, not S: without morphology the seeds that
+ *   failed the density test are in it, as in the reference) and nrs_mesh_from_density's code runs on it with the box 0.5 +- 0.5 * 2^g, res3d 128, thresh 0.5.  The closed
+ *   bitfield does not travel through the host between the closing and the lattice (L and S are still refreshed on the host for the accessors).  The result is an ordinary
+ *   nrs_mesh without colours.  Synchronous.  A handle is used with one device: a context on another is NRS_ERR_INVALID_ARG. */
+typedef struct nrs_selection nrs_selection;
+enum { NRS_SE_CUBE = 0, NRS_SE_SPHERE = 1 };        /* ESEType */
+enum { NRS_MORPH_DILATE = 0, NRS_MORPH_ERODE = 1 };
+int  nrs_selection_create(const float* h_density_grid, size_t n_floats, uint32_t max_cascade, nrs_selection** sel_out);
+void nrs_selection_destroy(nrs_selection* sel);
+int  nrs_selection_reset(nrs_selection* sel, const uint32_t* h_cells, uint32_t n, uint32_t growing_level);
+int  nrs_selection_grow(nrs_selection* sel, float density_threshold, uint32_t growing_level, uint32_t growing_steps, uint32_t* n_popped);
+int  nrs_selection_upscale(nrs_selection* sel);
+int  nrs_selection_state(const nrs_selection* sel, uint32_t* growing_level, uint32_t* n_cells, uint32_t* n_queue, int* performed_closing);
+int  nrs_selection_get_cells(const nrs_selection* sel, uint32_t* h_cells_out, float* h_points_out);
+int  nrs_selection_get_bitfield(const nrs_selection* sel, uint8_t* h_bitfield_out);
+int  nrs_selection_set_structuring_elements(nrs_selection* sel, int dilation_type, int dilation_radius, int erosion_type, int erosion_radius);
+int  nrs_bitfield_morph(nrs_ctx* ctx, void* stream, const uint8_t* d_in, uint32_t level, int op, int se_type, int radius, uint8_t* d_out);
+int  nrs_bitfield_morph_host(const uint8_t* h_in, uint32_t level, int op, int se_type, int radius, uint8_t* h_out);
+int  nrs_selection_dilate(nrs_ctx* ctx, void* stream, nrs_selection* sel);
+int  nrs_selection_erode(nrs_ctx* ctx, void* stream, nrs_selection* sel);
+int  nrs_selection_fine_mesh(nrs_ctx* ctx, void* stream, nrs_selection* sel, int use_morphological, nrs_mesh** mesh_out);
+
 #ifdef __cplusplus
 }
 #endif

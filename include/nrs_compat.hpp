@@ -8,6 +8,7 @@
 //   ngp::Testbed::render_to_cpu src/python_api.cu:129-175                                  -> nrs::compat::Testbed::render_to_cpu (+ load_camera_path,
 //                                                                                             set_camera_from_time, apply_camera_smoothing)
 //   ngp::Testbed::marching_cubes src/testbed_nerf.cu:4614 (+ compute_and_save_marching_cubes_mesh, get_marching_cubes_res) -> nrs::compat::Testbed::marching_cubes
+//   ngp::GrowingSelection (RegionGrowing, CorrectMMOperations) src/editing/tools/growing_selection.cu:2083-2162, region_growing.cu -> nrs::compat::GrowingSelection
 //
 // No Eigen / tiny-cuda-nn types: matrices are column-major float arrays (what Eigen::Matrix<float,3,4>::data() yields),
 // streams are passed as void* (hipStream_t), errors become std::runtime_error (the reference throws from CUDA_CHECK_THROW).
@@ -478,6 +479,74 @@ public:
 		}
 		for (int i = 0; i < 12; ++i) m_smoothed_camera[i] = end_cam[i]; // :167-168
 	}
+};
+
+// GrowingSelection's growing and fine-mesh members (editing/tools/growing_selection.h; RegionGrowing, region_growing.h): thin forwards to the nrs_selection_* calls.
+// The context is needed by dilate, erode and extract_fine_mesh only (NULL: a host-only selection).
+class GrowingSelection {
+public:
+	GrowingSelection(nrs_ctx* ctx, const std::vector<float>& density_grid, uint32_t max_cascade) : m_ctx(ctx) {
+		check(nrs_selection_create(density_grid.data(), density_grid.size(), max_cascade, &m_sel), "nrs_selection_create");
+	}
+	~GrowingSelection() {
+		nrs_mesh_destroy(m_selection_mesh);
+		nrs_selection_destroy(m_sel);
+	}
+	GrowingSelection(const GrowingSelection&) = delete;
+	GrowingSelection& operator=(const GrowingSelection&) = delete;
+	nrs_selection* get() const { return m_sel; }
+
+	bool m_use_morphological = true;
+	float m_density_threshold = 0.01f;
+	int m_growing_steps = 10000;
+	nrs_mesh* m_selection_mesh = nullptr; // selection_mesh of the last extract_fine_mesh, on the device
+
+	void reset_growing(const std::vector<uint32_t>& selected_cells, int growing_level) {
+		check(nrs_selection_reset(m_sel, selected_cells.data(), (uint32_t)selected_cells.size(), (uint32_t)growing_level), "nrs_selection_reset");
+	}
+	// grow_region(density_threshold, ERegionGrowingMode::Manual, growing_level, growing_steps); returns the entries popped
+	uint32_t grow_region(float density_threshold, int growing_level, int growing_steps) {
+		uint32_t popped = 0;
+		check(nrs_selection_grow(m_sel, density_threshold, (uint32_t)growing_level, growing_steps < 0 ? 0u : (uint32_t)growing_steps, &popped), "nrs_selection_grow");
+		return popped;
+	}
+	void upscale_growing() { check(nrs_selection_upscale(m_sel), "nrs_selection_upscale"); }
+	void dilate(void* stream = nullptr) { check(nrs_selection_dilate(m_ctx, stream, m_sel), "nrs_selection_dilate"); }
+	void erode(void* stream = nullptr) { check(nrs_selection_erode(m_ctx, stream, m_sel), "nrs_selection_erode"); }
+	void extract_fine_mesh(void* stream = nullptr) {
+		nrs_mesh* mesh = nullptr;
+		check(nrs_selection_fine_mesh(m_ctx, stream, m_sel, m_use_morphological ? 1 : 0, &mesh), "nrs_selection_fine_mesh");
+		nrs_mesh_destroy(m_selection_mesh);
+		m_selection_mesh = mesh;
+	}
+	int growing_level() const {
+		uint32_t level = 0;
+		check(nrs_selection_state(m_sel, &level, nullptr, nullptr, nullptr), "nrs_selection_state");
+		return (int)level;
+	}
+	std::vector<uint32_t> selection_cell_idx() const {
+		uint32_t n = 0;
+		check(nrs_selection_state(m_sel, nullptr, &n, nullptr, nullptr), "nrs_selection_state");
+		std::vector<uint32_t> cells(n);
+		check(nrs_selection_get_cells(m_sel, cells.data(), nullptr), "nrs_selection_get_cells");
+		return cells;
+	}
+	std::vector<float> selection_points() const { // x, y, z per cell
+		uint32_t n = 0;
+		check(nrs_selection_state(m_sel, nullptr, &n, nullptr, nullptr), "nrs_selection_state");
+		std::vector<float> points((size_t)n * 3);
+		check(nrs_selection_get_cells(m_sel, nullptr, points.data()), "nrs_selection_get_cells");
+		return points;
+	}
+	std::vector<uint8_t> selection_grid_bitfield() const {
+		std::vector<uint8_t> bits(NRS_BITFIELD_BYTES);
+		check(nrs_selection_get_bitfield(m_sel, bits.data()), "nrs_selection_get_bitfield");
+		return bits;
+	}
+
+private:
+	nrs_ctx* m_ctx = nullptr;
+	nrs_selection* m_sel = nullptr;
 };
 
 } // namespace compat

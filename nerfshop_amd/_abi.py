@@ -191,12 +191,17 @@ EXPORTS = [
     "nrs_camera_path_open", "nrs_camera_path_count", "nrs_camera_path_keyframes", "nrs_camera_path_close", "nrs_motion_views",
     "nrs_marching_cubes_res", "nrs_marching_cubes_table", "nrs_mesh_write", "nrs_mesh_from_density", "nrs_mesh_extract", "nrs_mesh_color_inputs",
     "nrs_mesh_counts", "nrs_mesh_device", "nrs_mesh_download", "nrs_mesh_destroy",
+    "nrs_selection_create", "nrs_selection_destroy", "nrs_selection_reset", "nrs_selection_grow", "nrs_selection_upscale", "nrs_selection_state",
+    "nrs_selection_get_cells", "nrs_selection_get_bitfield", "nrs_selection_set_structuring_elements", "nrs_bitfield_morph", "nrs_bitfield_morph_host",
+    "nrs_selection_dilate", "nrs_selection_erode", "nrs_selection_fine_mesh",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
 COLOR_LINEAR, COLOR_SRGB, COLOR_VISPOSNEG = 0, 1, 2  # nrs_color_space
 TONEMAP_IDENTITY, TONEMAP_ACES, TONEMAP_HABLE, TONEMAP_REINHARD = 0, 1, 2, 3  # nrs_tonemap_curve
 TONEMAP_RGBA32F, TONEMAP_RGBA8 = 0, 1  # NRS_TONEMAP_RGBA32F / _RGBA8
+SE_CUBE, SE_SPHERE = 0, 1  # NRS_SE_CUBE / _SPHERE (ESEType)
+MORPH_DILATE, MORPH_ERODE = 0, 1  # NRS_MORPH_DILATE / _ERODE
 MESH_THRESH_DEFAULT = 2.5  # m_mesh.thresh as the reference's Python interface passes it (testbed.h:387)
 
 _lib = None
@@ -347,6 +352,24 @@ def load():
         lib.nrs_mesh_download.argtypes = [P, P, P, P, P, P]
         lib.nrs_mesh_destroy.argtypes = [P]
         lib.nrs_mesh_destroy.restype = None
+    # selection tool (appended exports, detected by symbol)
+    if hasattr(lib, "nrs_selection_create"):
+        PU32 = C.POINTER(U32)
+        lib.nrs_selection_create.argtypes = [P, C.c_size_t, U32, C.POINTER(P)]
+        lib.nrs_selection_destroy.argtypes = [P]
+        lib.nrs_selection_destroy.restype = None
+        lib.nrs_selection_reset.argtypes = [P, P, U32, U32]
+        lib.nrs_selection_grow.argtypes = [P, C.c_float, U32, U32, PU32]
+        lib.nrs_selection_upscale.argtypes = [P]
+        lib.nrs_selection_state.argtypes = [P, PU32, PU32, PU32, C.POINTER(I)]
+        lib.nrs_selection_get_cells.argtypes = [P, P, P]
+        lib.nrs_selection_get_bitfield.argtypes = [P, P]
+        lib.nrs_selection_set_structuring_elements.argtypes = [P, I, I, I, I]
+        lib.nrs_bitfield_morph.argtypes = [P, P, P, U32, I, I, I, P]
+        lib.nrs_bitfield_morph_host.argtypes = [P, U32, I, I, I, P]
+        lib.nrs_selection_dilate.argtypes = [P, P, P]
+        lib.nrs_selection_erode.argtypes = [P, P, P]
+        lib.nrs_selection_fine_mesh.argtypes = [P, P, P, I, C.POINTER(P)]
     lib.nrs_snapshot_open.argtypes = [C.c_char_p, C.POINTER(P)]
     lib.nrs_snapshot_close.argtypes = [P]
     lib.nrs_snapshot_close.restype = None

@@ -195,6 +195,14 @@ void normalized(const float* v, float out[3]) { // Eigen's normalized(): a vecto
 
 } // namespace
 
+int nrs::mesh_from_lattice(int device, void* stream, const uint32_t res3d[3], const float aabb_min[3], const float aabb_max[3], float thresh, const float* d_density,
+                           nrs_mesh** mesh_out, const char* fn) {
+	std::unique_ptr<nrs_mesh> mesh;
+	NRS_TRY(build_mesh(device, stream, res3d, aabb_min, aabb_max, thresh, d_density, mesh, fn));
+	*mesh_out = mesh.release();
+	return NRS_OK;
+}
+
 extern "C" {
 
 // get_marching_cubes_res, marching_cubes.cu:48-55

@@ -1,11 +1,12 @@
-// nrs_handles.h -- the three opaque structs of include/nrs.h, the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
-// work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp) includes
+// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
+// work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp, nrs_api_selection.cpp) includes
 // this header alone.  Host-only C++17: no .hip / .cuh includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <deque>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -75,6 +76,10 @@ private:
 	T* p_ = nullptr;
 	size_t n_ = 0;
 };
+
+// marching_cubes_gpu + compute_mesh_1ring on a lattice that is already on the device (nrs_api_mesh.cpp; the arguments have been checked); `fn` names the caller in messages
+int mesh_from_lattice(int device, void* stream, const uint32_t res3d[3], const float aabb_min[3], const float aabb_max[3], float thresh, const float* d_density,
+                      nrs_mesh** mesh_out, const char* fn);
 
 } // namespace nrs
 
@@ -182,4 +187,19 @@ struct nrs_edit {
 	// the second nrs_render_nerf after the last move builds it (a gizmo drag renders one frame per move and never pays; a cage at rest renders 2-3 % faster)
 	bool fine_stale = false;
 	uint32_t renders_since_move = 0;
+};
+
+// RegionGrowing + GrowingSelection's morphology state (region_growing.h, growing_selection.h): host-only until a device call names a context
+struct nrs_selection {
+	std::vector<float> grid;            // m_density_grid_host [5 * 128^3]
+	uint32_t max_cascade = 0;
+	std::vector<uint8_t> bits;          // m_selection_grid_bitfield [NRS_BITFIELD_BYTES]
+	std::vector<uint32_t> cells;        // m_selection_cell_idx, in order, duplicates kept (m_selection_points follows from it)
+	std::deque<uint32_t> queue;         // m_growing_queue
+	uint32_t level = 0;                 // m_growing_level
+	bool performed_closing = false;
+	int dilation_type = NRS_SE_CUBE, dilation_radius = 2, erosion_type = NRS_SE_SPHERE, erosion_radius = 2; // correct_mm_operations.h:70
+	int device = -1;                    // of the buffers below, once a device call has allocated them
+	nrs::DeviceBuffer<uint32_t> d_work; // [3][kMorphLevelWords]: the growing level in Morton order | two levels of rows
+	nrs::DeviceBuffer<float> d_lattice; // [128^3]
 };

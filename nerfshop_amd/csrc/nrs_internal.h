@@ -1,4 +1,4 @@
-// nrs_internal.h -- PODs shared between the C++ host code (nrs_api.cpp, nrs_api_*.cpp; their own header: nrs_host.h) and the HIP kernels (nrs_render*.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip, nrs_cage.hip, nrs_mesh.hip).
+// nrs_internal.h -- PODs shared between the C++ host code (nrs_api.cpp, nrs_api_*.cpp; their own header: nrs_host.h) and the HIP kernels (nrs_render*.hip, nrs_network.hip, nrs_display.hip, nrs_tables.hip, nrs_occupancy.hip, nrs_cage.hip, nrs_mesh.hip, nrs_selection.hip).
 // Nothing here is part of the public ABI (that is include/nrs.h).
 #pragma once
 #include <stdint.h>
@@ -301,6 +301,21 @@ int launch_mc_1ring(const McGrid& g, const float* d_density, const int8_t* d_tab
 // generate_nerf_network_inputs_from_positions (tn:608): [n x 7] network inputs of n vertices; extract_srgb_with_activation (tn:338) on interleaved fp16 network outputs
 int launch_mesh_color_inputs(uint32_t n, const float* d_verts, const Box3& aabb, float* d_coords7, void* stream);
 int launch_mesh_colors(uint32_t n, const void* d_net_fp16, uint32_t rgb_activation, int linear_colors, float* d_colors, void* stream);
+
+// selection tool (nrs_selection.hip).  Morphology works on one level of a bitfield re-packed to x-major rows: word (z * 128 + y) * 4 + x / 32, bit x % 32.
+constexpr uint32_t kMorphLevelWords = kGridVol / 32;
+constexpr int32_t kMorphMaxRadius = 10;          // the reference's slider, correct_mm_operations.cu:16
+constexpr uint32_t kMorphMaxTaps = (2 * kMorphMaxRadius + 1) * (2 * kMorphMaxRadius + 1);
+// a structuring element as rows: tap i covers x - half[i] .. x + half[i] of row (y + dy[i], z + dz[i]); sorted by descending half.  invert: erosion (the walk runs on the complement)
+struct MorphPlan {
+	uint32_t n_taps, invert;
+	int8_t dy[kMorphMaxTaps], dz[kMorphMaxTaps], half[kMorphMaxTaps];
+};
+int launch_morph_pack(const uint32_t* d_morton_level, uint32_t* d_rows, void* stream);
+int launch_morph_unpack(const uint32_t* d_rows, uint32_t* d_morton_level, void* stream);
+int launch_morph_rows(const MorphPlan& plan, const uint32_t* d_rows_in, uint32_t* d_rows_out, void* stream); // in != out
+// [128^3] floats, x + 128 y + 128^2 z: 1.0 where the row bit is set and the cell is not on the grid's shell, else 0.0
+int launch_selection_lattice(const uint32_t* d_rows, float* d_lattice, void* stream);
 
 // The planner behind one C symbol (exported from libnrs.so, declared here only: not part of include/nrs.h): tests sweep it without a GPU.
 struct RouteProbe {
