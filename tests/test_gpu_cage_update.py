@@ -84,10 +84,15 @@ def test_cage_moves_rebuild_on_device(rig, via):
 def test_large_meshes_take_the_other_launch_shapes(rig, lattice):
     """The LUT passes choose their lane teams by mesh size and tet size (nrs_cage.hip launch_tet_mark: a wave per item at cascade 0 for the bench's 6 000-tet cage,
     eight lanes / one lane per item for a 35 000-tet one), cells with more than 24 tets are sorted by a wave in LDS and cells with more than 128 (the coarse
-    cascades of the large mesh) by a workgroup's bitmap pass: the tables are the oracle's builder's whatever the shape, after creation and after a move."""
+    cascades of the large mesh) by a workgroup's bitmap pass: the tables are the oracle's builder's whatever the shape, after creation and after a move.
+    What regular lattices cannot reach -- a small mesh with 8-lane teams, boxes beyond the 128-cell hit mask under 8 and 1 lanes, lists of exactly 24, 25, 128 and
+    129 tets, the bitonic networks of meshes beyond 491 520 tets -- is in tests/test_gpu_cage_lut_shapes.py."""
     scene = rig.scene
     synth, orc = scene.synth, scene.orc
     e = synth.make_cage_edit(lattice_n=lattice)
+    n_tets = e.tets.shape[0]
+    assert (n_tets <= 16384) == (lattice == 10)   # launch_tet_mark's `small`: 6 000 tets against 34 992
+    assert n_tets <= 15360 * 32                   # lists of more than 128 tets take the bitmap pass
     op = rig.rt.CageDeformation(rig.ctx, scene.desc, e, device_authoring=True)
     op.set_mvc(e.mvc_weights)
     try:
@@ -97,6 +102,11 @@ def test_large_meshes_take_the_other_launch_shapes(rig, lattice):
             got = op.download(rotations=False)
             off, idx, _, mx = orc.tet_lut_build(verts, e.tets)
             assert np.array_equal(got["lut_offsets"], off) and np.array_equal(got["lut_idx"], idx) and op.lut_size() == (idx.size, mx)
+            lengths = np.diff(off.astype(np.int64))
+            assert ((lengths > 24) & (lengths <= 128)).any() and (lengths > 128).any() and ((lengths > 1) & (lengths <= 24)).any()   # a wave's, a workgroup's and a thread's sort all ran
+            if lattice == 10:   # a wave per item at cascade 0: build_lut_on_device's estimate, from the box of the pose before the build (this pose's or the first's), is >= 32
+                ext = (verts.max(0) - verts.min(0)).astype(np.float64)
+                assert (np.cbrt(ext.prod() / (n_tets / 6.0)) * 128 + 1.0) ** 3 >= 32.0
             if lattice == 18:
                 assert mx > 1024   # the bitmap pass ran (lists longer than a wave's share of LDS)
             if verts is e.vertices:
