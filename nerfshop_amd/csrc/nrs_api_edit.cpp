@@ -79,12 +79,17 @@ static int build_lut_on_device(nrs_edit* e, const float* d_verts, uint8_t* d_bit
 }
 // The fine look-up table of e's CURRENT LUT and plane records (both on the device, written on stream s): DeviceEdit::fine_*.  Leaves the operator without one (the kernels
 // then scan the LUT's own lists) when the mesh reaches no cell, when even one fine cell per LUT cell would exceed kFineMaxCells, or when NRS_NO_FINE_LUT is set (A/B).
+// The table comes with a head word per fine cell (DeviceEdit::fine_head) unless a tet number would not fit its 25 bits or NRS_NO_FINE_HEAD is set (A/B, and the test
+// of that fallback); a fine list is a filtered LUT list of a cascade that passed kFineMaxList, so its length always fits the head's 7 bits.
 // Two small read-backs (the window, the entry count), like the LUT's own build.
 int nrs::build_fine_lut(nrs_edit* e, hipStream_t s) {
 	static const bool off = dev_knob("NRS_NO_FINE_LUT") != nullptr;
+	static const bool no_head = dev_knob("NRS_NO_FINE_HEAD") != nullptr;
+	const bool want_head = !no_head && e->n_tets < (1u << kFineHeadTetBits);
 	DeviceEdit& de = e->de;
 	de.fine_off = nullptr;
 	de.fine_idx = nullptr;
+	de.fine_head = nullptr;
 	memset(de.fine_win, 0, sizeof(de.fine_win));
 	e->fine_n_idx = 0;
 	if (off) return NRS_OK;
@@ -119,12 +124,13 @@ int nrs::build_fine_lut(nrs_edit* e, hipStream_t s) {
 	}
 	if (!any) { memset(de.fine_win, 0, sizeof(de.fine_win)); return NRS_OK; }
 	const uint32_t n_cells = base, n_padded = (n_cells + 4095u) / 4096u * 4096u;
-	if (n_padded > e->fine_cells_cap) {
-		e->d_fine_off.reset(); e->d_fine_counts.reset();
+	if (n_padded > e->fine_cells_cap || (want_head && !e->d_fine_head.get())) {
+		e->d_fine_off.reset(); e->d_fine_counts.reset(); e->d_fine_head.reset();
 		e->fine_cells_cap = 0;
 		const size_t cap = std::min<size_t>(kFineMaxCells, (size_t)n_padded + n_padded / 4 + 4095) / 4096 * 4096;
 		HIP_TRY(e->d_fine_off.alloc(cap + 1));
 		HIP_TRY(e->d_fine_counts.alloc(cap));
+		if (want_head) HIP_TRY(e->d_fine_head.alloc(cap)); // (a refusal: no fine table at all, like a refusal of the offsets -- de.fine_* are null already)
 		e->fine_cells_cap = cap;
 	}
 	NRS_LAUNCH(launch_fine_count_scan(de, n_cells, e->d_fine_counts.get(), e->d_fine_tiles.get(), e->d_fine_off.get(), (uint32_t*)e->d_fine_win.get() + kCascades * 8, s));
@@ -138,13 +144,14 @@ int nrs::build_fine_lut(nrs_edit* e, hipStream_t s) {
 		HIP_TRY(e->d_fine_idx.alloc(cap));
 		e->fine_idx_cap = cap;
 	}
-	NRS_LAUNCH(launch_fine_fill(de, n_cells, e->d_fine_off.get(), e->d_fine_idx.get(), s));
+	NRS_LAUNCH(launch_fine_fill(de, n_cells, e->d_fine_off.get(), e->d_fine_idx.get(), want_head ? e->d_fine_head.get() : nullptr, s));
 	e->fine_n_idx = n_idx;
 	de.fine_off = e->d_fine_off.get();
 	de.fine_idx = e->d_fine_idx.get();
+	de.fine_head = want_head ? e->d_fine_head.get() : nullptr;
 	static const bool log_fine = dev_knob("NRS_FINE_LOG") != nullptr;
-	if (log_fine) fprintf(stderr, "[nrs fine lut] %u fine cells, %u entries (the LUT holds %u), subdivision per cascade %d %d %d %d %d\n", n_cells, n_idx, e->lut_n_idx, de.fine_win[0][7],
-	                      de.fine_win[1][7], de.fine_win[2][7], de.fine_win[3][7], de.fine_win[4][7]);
+	if (log_fine) fprintf(stderr, "[nrs fine lut] %u fine cells, %u entries (the LUT holds %u), subdivision per cascade %d %d %d %d %d, head words %s\n", n_cells, n_idx, e->lut_n_idx, de.fine_win[0][7],
+	                      de.fine_win[1][7], de.fine_win[2][7], de.fine_win[3][7], de.fine_win[4][7], de.fine_head ? "yes" : "no");
 	return NRS_OK;
 }
 // everything that follows new deformed vertices in e->d_verts: bbox, LUT, rotations.  Synchronous.
@@ -152,12 +159,14 @@ static int rebuild_after_vertices(nrs_edit* e, hipStream_t s, bool build_fine_no
 	NRS_TRY(ensure_build_scratch(e));
 	NRS_LAUNCH(launch_bbox(e->n_vertices, e->d_verts.get(), (float*)e->d_scratch.get(), s));
 	NRS_TRY(build_lut_on_device(e, e->d_verts.get(), nullptr, s));
-	if (e->d_rot.get()) NRS_LAUNCH(launch_local_rotations(e->n_tets, e->d_verts.get(), e->de.orig, e->de.tets, e->d_rot.get(), s));
+	// (the rotation of a tet's map-back record and its plane record: both of the new pose, on this stream, before the next reader)
+	if (e->d_rot.get()) NRS_LAUNCH(launch_local_rotations(e->n_tets, e->d_verts.get(), e->de.orig, e->de.tets, e->d_rot.get(), e->d_mapback.get(), s));
 	NRS_LAUNCH(launch_tet_planes(e->n_tets, e->d_verts.get(), e->de.tets, e->d_planes.get(), s));
 	if (build_fine_now) NRS_TRY(build_fine_lut(e, s));
 	else { // (see nrs_edit::fine_stale)
 		e->de.fine_off = nullptr;
 		e->de.fine_idx = nullptr;
+		e->de.fine_head = nullptr;
 		memset(e->de.fine_win, 0, sizeof(e->de.fine_win));
 		e->fine_stale = true;
 		e->renders_since_move = 0;
@@ -218,6 +227,8 @@ int nrs_edit_create(nrs_ctx* ctx, const nrs_model_desc* desc, const nrs_tet_mesh
 	if (hipMemcpy(e->d_verts.get(), mesh->h_vertices, 12 * (size_t)mesh->n_vertices, hipMemcpyHostToDevice) != hipSuccess)
 		return fail(NRS_ERR_HIP, "nrs_edit_create: vertex upload failed");
 	NRS_TRY(dev_alloc(e->d_planes, 32 * (size_t)mesh->n_tets));
+	NRS_TRY(dev_alloc(e->d_mapback, 24 * (size_t)mesh->n_tets));
+	de.mapback = e->d_mapback.get();
 	de.verts = e->d_verts.get();
 	de.lut_off = e->d_lut_off.get();
 	de.planes = e->d_planes.get();
@@ -262,7 +273,7 @@ int nrs_edit_create(nrs_ctx* ctx, const nrs_model_desc* desc, const nrs_tet_mesh
 			he = hipMemcpy(e->d_rot.get(), mesh->h_local_rotations, 36 * (size_t)mesh->n_tets, hipMemcpyHostToDevice);
 			if (he != hipSuccess) return fail_hip(he, "nrs_edit_create: rotation upload");
 		} else if (want_rot) {
-			NRS_LAUNCH(launch_local_rotations(e->n_tets, e->d_verts.get(), de.orig, de.tets, e->d_rot.get(), nullptr));
+			NRS_LAUNCH(launch_local_rotations(e->n_tets, e->d_verts.get(), de.orig, de.tets, e->d_rot.get(), nullptr, nullptr));
 			if (hipDeviceSynchronize() != hipSuccess) return fail(NRS_ERR_HIP, "nrs_edit_create: rotation kernel failed");
 		}
 	} else {
@@ -270,6 +281,9 @@ int nrs_edit_create(nrs_ctx* ctx, const nrs_model_desc* desc, const nrs_tet_mesh
 		if (mesh->h_local_rotations && hipMemcpy(e->d_rot.get(), mesh->h_local_rotations, 36 * (size_t)mesh->n_tets, hipMemcpyHostToDevice) != hipSuccess)
 			return fail(NRS_ERR_HIP, "nrs_edit_create: rotation upload failed");
 	}
+	// the map-back records, whole: the canonical vertices and the rotations as they stand now, wherever they came from (a move rewrites the rotation part)
+	NRS_LAUNCH(launch_tet_mapback(e->n_tets, de.orig, de.tets, e->d_rot.get(), e->d_mapback.get(), nullptr));
+	if (hipDeviceSynchronize() != hipSuccess) return fail(NRS_ERR_HIP, "nrs_edit_create: tet_mapback_kernel failed");
 	*out = owner.release();
 	return NRS_OK;
 }

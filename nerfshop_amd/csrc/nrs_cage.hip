@@ -503,8 +503,9 @@ __global__ __launch_bounds__(1024) void lut_sort_big_kernel(const uint32_t* __re
 }
 
 // ---- TetMesh::update_local_rotations (tet_mesh.cu:37-74): R = U V^T from the reference's approximate SVD (nrs_svd3.h) -------------
+// mapback (nullable): the tet's map-back record (DeviceEdit::mapback) gets the same nine floats behind its twelve canonical ones
 __global__ void local_rotations_kernel(uint32_t n_tets, const float* __restrict__ def, const float* __restrict__ org,
-                                       const uint32_t* __restrict__ tets, float* __restrict__ out) {
+                                       const uint32_t* __restrict__ tets, float* __restrict__ out, float* __restrict__ mapback) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n_tets) return;
 	const uint4 tv = reinterpret_cast<const uint4*>(tets)[i];
@@ -515,6 +516,22 @@ __global__ void local_rotations_kernel(uint32_t n_tets, const float* __restrict_
 	float R[9];
 	svd3::tet_rotation(o, d, R);
 	for (int k = 0; k < 9; ++k) out[9 * (size_t)i + k] = R[k];
+	if (mapback)
+		for (int k = 0; k < 9; ++k) mapback[24 * (size_t)i + 12 + k] = R[k];
+}
+// ---- per-tet map-back records (DeviceEdit::mapback), the whole record: the canonical vertices of the tet's corners, never rewritten, and the rotation as `rot` holds it
+// now (null: zeros) -- at creation, where the rotations may have come from the host; a move rewrites the rotation part only (local_rotations_kernel) ----
+__global__ void tet_mapback_kernel(uint32_t n_tets, const float* __restrict__ org, const uint32_t* __restrict__ tets, const float* __restrict__ rot, float* __restrict__ mapback) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_tets) return;
+	const uint4 tv = reinterpret_cast<const uint4*>(tets)[i];
+	const f3 v[4] = {ld3(org, tv.x), ld3(org, tv.y), ld3(org, tv.z), ld3(org, tv.w)};
+	float out[24];
+	for (int f = 0; f < 4; ++f) { out[3 * f] = v[f].x; out[3 * f + 1] = v[f].y; out[3 * f + 2] = v[f].z; }
+	for (int k = 0; k < 9; ++k) out[12 + k] = rot ? rot[9 * (size_t)i + k] : 0.f;
+	for (int k = 21; k < 24; ++k) out[k] = 0.f;
+	float4* dst = reinterpret_cast<float4*>(mapback) + 6 * (size_t)i;
+	for (int q = 0; q < 6; ++q) dst[q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
 }
 
 // ---- per-tet face planes for point_in_tet_planes (nrs_device.cuh): the tet-only half of same_side_tet, selection_utils.h:33-39 ----
@@ -614,7 +631,7 @@ __device__ __forceinline__ bool tet_may_contain_box(const float* __restrict__ r,
 // tets serially with a dependent load per step: 20 ms per cage move at 48 k tets.)
 template <bool FILL>
 __global__ __launch_bounds__(256) void fine_lists_kernel(const DeviceEdit e, uint32_t* __restrict__ counts, const uint32_t* __restrict__ fine_off,
-                                                         uint32_t* __restrict__ fine_idx) {
+                                                         uint32_t* __restrict__ fine_idx, uint2* __restrict__ fine_head) {
 	uint32_t w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); // one launch for every cascade: the few long lists of the coarse ones run beside the many short ones
 	const uint32_t lane = threadIdx.x & 63u;
 	uint32_t level = kCascades;
@@ -636,7 +653,11 @@ __global__ __launch_bounds__(256) void fine_lists_kernel(const DeviceEdit e, uin
 	const uint32_t sx = lane & (sub - 1u), sy = (lane >> S) & (sub - 1u), sz = lane >> (2u * S);
 	const uint32_t rx = (cx << S) + sx, ry = (cy << S) + sy, rz = (cz << S) + sz; // fine cell inside the window
 	const uint32_t cell = (uint32_t)e.fine_win[level][3] + (rz * ey + ry) * ex + rx;
-	if (j0 == j1) { if (!FILL && owner) counts[cell] = 0u; return; }
+	if (j0 == j1) {
+		if (!FILL && owner) counts[cell] = 0u;
+		if (FILL && owner && fine_head) fine_head[cell] = make_uint2(0u, 0u);
+		return;
+	}
 	// the positions u whose fine coordinate is f: q = ((u - 0.5) * 2^-level + 0.5), floor(q * res) = f  =>  u in 0.5 + ((f .. f + 1) / res - 0.5) * 2^level, widened by
 	// what the three float operations can round; the outermost fine cells take everything beyond (the index clamps)
 	const uint32_t res = kGrid << S;
@@ -652,6 +673,8 @@ __global__ __launch_bounds__(256) void fine_lists_kernel(const DeviceEdit e, uin
 		border = border || f[i] == 0 || f[i] >= res - 1;
 	}
 	uint32_t n = 0, wpos = (FILL && owner) ? fine_off[cell] : 0u;
+	const uint32_t wpos0 = wpos;
+	uint32_t first = 0u; // (FILL: the list's first tet, for the head word)
 	for (uint32_t b = j0; b < j1; b += 64u) {
 		const uint32_t mine = b + lane < j1 ? e.lut_idx[b + lane] : 0u; // 64 candidates, one per lane
 		const uint32_t nb = min(64u, j1 - b);
@@ -672,7 +695,7 @@ __global__ __launch_bounds__(256) void fine_lists_kernel(const DeviceEdit e, uin
 			}
 			const float* r = reinterpret_cast<const float*>(cur);
 			if ((border || tet_may_contain_box(r, c, h)) && owner) {
-				if (FILL) fine_idx[wpos++] = t;
+				if (FILL) { fine_idx[wpos++] = t; if (n == 0) first = t; }
 				++n;
 			}
 			#pragma unroll
@@ -680,6 +703,8 @@ __global__ __launch_bounds__(256) void fine_lists_kernel(const DeviceEdit e, uin
 		}
 	}
 	if (!FILL && owner) counts[cell] = n;
+	// the head word (DeviceEdit::fine_head; null: this edit keeps none).  n <= kFineMaxList < 128 and first < 2^kFineHeadTetBits: build_fine_lut's conditions
+	if (FILL && owner && fine_head) fine_head[cell] = make_uint2(wpos0, first | (n << kFineHeadTetBits));
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
@@ -729,9 +754,14 @@ int launch_tet_planes(uint32_t n_tets, const float* d_verts, const uint32_t* d_t
 	NRS_LAUNCH_CHECK("tet_planes_kernel launch");
 	return NRS_OK;
 }
-int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, void* stream) {
-	hipLaunchKernelGGL(local_rotations_kernel, dim3((n_tets + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_tets, d_verts, d_orig, d_tets, d_out);
+int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, float* d_mapback, void* stream) {
+	hipLaunchKernelGGL(local_rotations_kernel, dim3((n_tets + 63) / 64), dim3(64), 0, (hipStream_t)stream, n_tets, d_verts, d_orig, d_tets, d_out, d_mapback);
 	NRS_LAUNCH_CHECK("local_rotations_kernel launch");
+	return NRS_OK;
+}
+int launch_tet_mapback(uint32_t n_tets, const float* d_orig, const uint32_t* d_tets, const float* d_rot, float* d_mapback, void* stream) {
+	hipLaunchKernelGGL(tet_mapback_kernel, dim3((n_tets + 127) / 128), dim3(128), 0, (hipStream_t)stream, n_tets, d_orig, d_tets, d_rot, d_mapback);
+	NRS_LAUNCH_CHECK("tet_mapback_kernel launch");
 	return NRS_OK;
 }
 
@@ -745,30 +775,30 @@ int launch_fine_window(const uint32_t* d_lut_off, int32_t* d_window_out, void* s
 	return NRS_OK;
 }
 template <bool FILL>
-static void launch_fine_lists(const DeviceEdit& de, uint32_t* d_counts, const uint32_t* d_fine_off, uint32_t* d_fine_idx, hipStream_t s) {
+static void launch_fine_lists(const DeviceEdit& de, uint32_t* d_counts, const uint32_t* d_fine_off, uint32_t* d_fine_idx, uint2* d_fine_head, hipStream_t s) {
 	uint32_t n_parents = 0;
 	for (uint32_t c = 0; c < kCascades; ++c) {
 		const int32_t* f = de.fine_win[c];
 		if (f[4] == 0 || (uint32_t)f[7] > 2u) continue;
 		n_parents += ((uint32_t)f[4] >> f[7]) * ((uint32_t)f[5] >> f[7]) * ((uint32_t)f[6] >> f[7]);
 	}
-	if (n_parents) hipLaunchKernelGGL(fine_lists_kernel<FILL>, dim3((n_parents + 3) / 4), dim3(256), 0, s, de, d_counts, d_fine_off, d_fine_idx);
+	if (n_parents) hipLaunchKernelGGL(fine_lists_kernel<FILL>, dim3((n_parents + 3) / 4), dim3(256), 0, s, de, d_counts, d_fine_off, d_fine_idx, d_fine_head);
 }
 int launch_fine_count_scan(const DeviceEdit& de, uint32_t n_fine_cells, uint32_t* d_counts, uint32_t* d_tile_sums, uint32_t* d_fine_off, uint32_t* d_total, void* stream) {
 	hipStream_t s = (hipStream_t)stream;
 	const uint32_t n_tiles = (n_fine_cells + kScanTile - 1) / kScanTile, n_padded = n_tiles * kScanTile;
 	if (n_tiles == 0 || n_tiles > kMaxScanTiles) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: %u fine cells", n_fine_cells); return NRS_ERR_INVALID_ARG; }
 	if (n_padded != n_fine_cells && hipMemsetAsync(d_counts + n_fine_cells, 0, (size_t)(n_padded - n_fine_cells) * 4, s) != hipSuccess) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: memset failed"); return NRS_ERR_HIP; }
-	launch_fine_lists<false>(de, d_counts, nullptr, nullptr, s);
+	launch_fine_lists<false>(de, d_counts, nullptr, nullptr, nullptr, s);
 	hipLaunchKernelGGL(scan_tile_sum_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums);
 	hipLaunchKernelGGL(scan_tile_prefix_kernel, dim3(1), dim3(1024), 0, s, d_tile_sums, d_fine_off + n_padded, d_total, n_tiles);
 	hipLaunchKernelGGL(scan_write_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums, d_fine_off);
 	NRS_LAUNCH_CHECK("fine look-up table count/scan launch");
 	return NRS_OK;
 }
-int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t* d_fine_off, uint32_t* d_fine_idx, void* stream) {
+int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t* d_fine_off, uint32_t* d_fine_idx, uint2* d_fine_head, void* stream) {
 	(void)n_fine_cells;
-	launch_fine_lists<true>(de, nullptr, d_fine_off, d_fine_idx, (hipStream_t)stream);
+	launch_fine_lists<true>(de, nullptr, d_fine_off, d_fine_idx, d_fine_head, (hipStream_t)stream);
 	NRS_LAUNCH_CHECK("fine_lists_kernel launch");
 	return NRS_OK;
 }

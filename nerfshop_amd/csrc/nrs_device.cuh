@@ -754,35 +754,62 @@ __device__ __forceinline__ bool point_in_tet_rec(const float* __restrict__ recs,
 	const uint32_t got = (__float_as_uint(d0) >> 31) | ((__float_as_uint(d1) >> 31) << 1) | ((__float_as_uint(d2) >> 31) << 2) | ((__float_as_uint(d3) >> 31) << 3);
 	return got == __float_as_uint(sg.x);
 }
-// first tet of the cell's list that contains p (0xffffffff: none); the next candidate's id is fetched while the current one is tested
+// first tet of the list idx[j0 .. j1) that contains p (0xffffffff: none), t = idx[j0] already in hand; the next candidate's id is fetched while the current one is tested
+__device__ __forceinline__ uint32_t scan_entries_for_tet(const DeviceEdit& e, const NRS_GLOBAL uint32_t* lut_idx, uint32_t j0, uint32_t j1, uint32_t t, f3 p, uint32_t* n_tested) {
+	uint32_t found = 0xffffffffu;
+	#pragma unroll 1
+	for (uint32_t j = j0; j < j1; ++j) {
+		const uint32_t t_next = lut_idx[min(j + 1, j1 - 1)];
+		if (n_tested) ++*n_tested; // (profiling instantiation only)
+		if (point_in_tet_rec(e.planes, t, p)) { found = t; break; }
+		t = t_next;
+	}
+	return found;
+}
+// first tet of the cell's list that contains p (0xffffffff: none)
 __device__ __forceinline__ uint32_t scan_list_for_tet(const DeviceEdit& e, const uint32_t* __restrict__ off, const uint32_t* __restrict__ idx, uint32_t cell, f3 p, uint32_t* n_tested = nullptr) {
 	const NRS_GLOBAL uint32_t* lut_off = gp(off);
 	const NRS_GLOBAL uint32_t* lut_idx = gp(idx);
 	const uint32_t j0 = lut_off[cell], j1 = lut_off[cell + 1];
-	uint32_t found = 0xffffffffu;
-	if (j0 < j1) {
-		uint32_t t = lut_idx[j0];
-		#pragma unroll 1
-		for (uint32_t j = j0; j < j1; ++j) {
-			const uint32_t t_next = lut_idx[min(j + 1, j1 - 1)];
-			if (n_tested) ++*n_tested; // (profiling instantiation only)
-			if (point_in_tet_rec(e.planes, t, p)) { found = t; break; }
-			t = t_next;
-		}
-	}
-	return found;
+	if (j0 >= j1) return 0xffffffffu;
+	return scan_entries_for_tet(e, lut_idx, j0, j1, lut_idx[j0], p, n_tested);
 }
 __device__ __forceinline__ uint32_t scan_cell_for_tet(const DeviceEdit& e, uint32_t cell, f3 p, uint32_t* n_tested = nullptr) { return scan_list_for_tet(e, e.lut_off, e.lut_idx, cell, p, n_tested); }
+// the same scan of a fine cell through its head word (DeviceEdit::fine_head): one 8-byte load brings the list's start, its length and its first tet -- the two offsets and
+// fine_idx[j0] of the scan above, two dependent trips -- so the first candidate's record and the second candidate's id are requested together.  The same candidates in
+// the same order: the same tet.
+__device__ __forceinline__ uint32_t scan_fine_cell_for_tet(const DeviceEdit& e, uint32_t cell, f3 p, uint32_t* n_tested = nullptr) {
+	typedef uint32_t u2n __attribute__((ext_vector_type(2))); // (a native vector, as in point_in_tet_rec: one 8-byte load)
+	const u2n head = *reinterpret_cast<const NRS_GLOBAL u2n*>(gp(e.fine_head) + cell);
+	const uint32_t n = head.y >> kFineHeadTetBits;
+	return scan_entries_for_tet(e, gp(e.fine_idx), head.x, head.x + n, head.y & ((1u << kFineHeadTetBits) - 1u), p, n_tested); // (n == 0: no iteration, nothing is read)
+}
 // The tet of e's deformed mesh that contains position u (un-warped), as the reference's scan of u's LUT cell finds it (0xffffffff: none).  With a fine look-up table
 // (DeviceEdit::fine_off) the candidates are the fine cell's -- the same first hit by construction (nrs_cage.hip: fine_lists_kernel), after fewer tests: on the bench's cage
 // the scan of a wave drops from 7 dependent trips per round to 2-3.  The fine coordinates are the LUT cell's arithmetic with a finer multiplier (cn:117-141), so fine >> shift
 // IS the LUT cell; a position outside the window stands in a LUT cell whose list is empty.
+// SHORT = false: the window per lane and the list through its CSR offsets, as before the head words -- for the gated kernel of the cone-stepping scenes, whose frame
+// measured 0.4 % slower with the shorter chain (profiles/warp_chain.md: garden_cage; waves of several cascades, a tenth of the samples in the box)
+template <bool SHORT = true>
 __device__ __forceinline__ uint32_t find_tet(const DeviceEdit& e, f3 u, const uint32_t* __restrict__ march_lds, uint32_t* n_tested = nullptr) {
 	const int level = mip_from_pos(u);
 	if (e.fine_off) {
 		typedef int32_t i4n __attribute__((ext_vector_type(4)));
-		const NRS_GLOBAL i4n* win = gp(reinterpret_cast<const i4n*>(&e.fine_win[0][0])) + 2 * level;
-		const i4n lo = win[0], ext = win[1];
+		// The cascade's window.  Where every lane of the wave stands in the same cascade (always so in a scene box of scale 1, mostly so in larger ones) the eight ints
+		// come in through scalar loads -- no trip of the vector memory path in front of the scan; the operator's struct does not change while a kernel runs.  (A pointer
+		// with an explicit address space, like the views table's: one that could be merged with a pointer into the kernel arguments has them copied to scratch.  Where
+		// `e` is a by-value kernel argument (map_rays_kernel; the render kernel and the occupancy refresh read their operators from a table in device memory) both casts below hold only because the compiler
+		// leaves the struct in the kernel-argument segment, which is global and constant memory, and makes no private copy of it: the per-lane cast relied on that
+		// before this one did; tests/test_gpu_parity.py::test_map_rays_bit_exact and tests/test_gpu_warp_chain.py run that kernel.)
+		i4n lo, ext;
+		const int level_u = __builtin_amdgcn_readfirstlane(level);
+		if (SHORT && __all(level == level_u)) {
+			const NRS_CONSTANT i4n* win = (const NRS_CONSTANT i4n*)reinterpret_cast<const i4n*>(&e.fine_win[0][0]) + 2 * level_u;
+			lo = win[0]; ext = win[1];
+		} else {
+			const NRS_GLOBAL i4n* win = gp(reinterpret_cast<const i4n*>(&e.fine_win[0][0])) + 2 * level;
+			lo = win[0]; ext = win[1];
+		}
 		const float mip_scale = ldexpf(1.0f, -level);
 		f3 q = u - mk3(0.5f, 0.5f, 0.5f);
 		q = q * mip_scale;
@@ -794,6 +821,7 @@ __device__ __forceinline__ uint32_t find_tet(const DeviceEdit& e, f3 u, const ui
 			const int fx = clampi_((int)(q.x * fres), 0, hi) - lo.x, fy = clampi_((int)(q.y * fres), 0, hi) - lo.y, fz = clampi_((int)(q.z * fres), 0, hi) - lo.z;
 			if ((uint32_t)fx >= (uint32_t)ext.x || (uint32_t)fy >= (uint32_t)ext.y || (uint32_t)fz >= (uint32_t)ext.z) return 0xffffffffu;
 			const uint32_t cell = (uint32_t)lo.w + ((uint32_t)fz * (uint32_t)ext.y + (uint32_t)fy) * (uint32_t)ext.x + (uint32_t)fx;
+			if (SHORT && e.fine_head) return scan_fine_cell_for_tet(e, cell, u, n_tested);
 			return scan_list_for_tet(e, e.fine_off, e.fine_idx, cell, u, n_tested);
 		}
 	}
@@ -804,12 +832,15 @@ __device__ __forceinline__ uint32_t find_tet(const DeviceEdit& e, f3 u, const ui
 // interpolate_tet (with_dir, honours copy) / interpolate_tet_pos (!with_dir, ignores copy).  pos/dir are the warped
 // [0,1] values of the NerfCoordinate; returns true if the sample must be treated as empty space.
 // Two phases on purpose: the LUT scan only decides WHICH tet contains the sample; the barycentric map-back reloads that
-// tet's vertices afterwards.  Fusing them keeps ~48 more VGPRs live across the scan and costs the kernel a wave of occupancy.
+// tet's vertices afterwards (from its plane record).  Fusing them keeps ~48 more VGPRs live across the scan and costs the kernel a wave of occupancy.
 // march_lds (optional): the kernel's LDS copy of the Morton spread table (stage_march_lds) -- the cell index then costs three LDS reads instead of 28 VALU
 // instructions (the same index: occupancy_bit_index is cascaded_grid_idx_at through the table)
 // scan_out (optional): what the tet search found (a tet number or 0xffffffff), kTetNotSearched when the sample is outside the deformed mesh's box -- the membrane
 // correction of the same operator looks for the same tet at the same position (poisson_residual_find) and takes it from here.
+// RECORD = false: the map-back through tets -> verts -> orig -> rot, four dependent trips, as before the map-back records -- for the instantiation that has no
+// register to spare for the record's wider trip (the membrane kernel: 128 VGPRs and scratch already); the same values, the same arithmetic.
 constexpr uint32_t kTetNotSearched = 0xfffffffeu;
+template <bool RECORD = true, bool SHORT = true> // (SHORT: find_tet's)
 __device__ __forceinline__ bool tet_warp(const DeviceEdit& e, bool with_dir, f3& wpos, f3& wdir, const uint32_t* __restrict__ march_lds = nullptr, uint32_t* scan_out = nullptr,
                                          uint32_t* n_tested = nullptr) {
 	bool in_deformed = false;
@@ -817,31 +848,63 @@ __device__ __forceinline__ bool tet_warp(const DeviceEdit& e, bool with_dir, f3&
 	if (box_contains(e.warped_bbox, wpos)) {
 		const f3 u = unwarp_position(wpos, e.aabb);
 		if (n_tested) *n_tested |= 0x10000u; // (profiling: the sample stands inside the deformed mesh's box; low half = candidates tested)
-		const uint32_t found = find_tet(e, u, march_lds, n_tested);
+		const uint32_t found = find_tet<SHORT>(e, u, march_lds, n_tested);
 		if (n_tested && found != 0xffffffffu) *n_tested |= 0x20000u;
 		if (scan_out) *scan_out = found;
 		__builtin_amdgcn_sched_barrier(0);
 		if (found != 0xffffffffu) {
-			typedef uint32_t u4n __attribute__((ext_vector_type(4)));
-			const u4n tv = gp(reinterpret_cast<const u4n*>(e.tets))[found];
-			float bc[4];
-			{
-				const f3 a = ld3(e.verts, tv.x), b = ld3(e.verts, tv.y), c = ld3(e.verts, tv.z), d = ld3(e.verts, tv.w);
-				bary_tet(a, b, c, d, u, bc);
-			}
-			__builtin_amdgcn_sched_barrier(0);
-			f3 canon = bc[0] * ld3(e.orig, tv.x) + bc[1] * ld3(e.orig, tv.y);
-			canon = canon + bc[2] * ld3(e.orig, tv.z);
-			canon = canon + bc[3] * ld3(e.orig, tv.w);
-			wpos = e.diag_pow2 ? mk3((canon.x - e.aabb.mn[0]) * e.inv_diag[0], (canon.y - e.aabb.mn[1]) * e.inv_diag[1], (canon.z - e.aabb.mn[2]) * e.inv_diag[2])
-			                   : warp_position(canon, e.aabb);
-			__builtin_amdgcn_sched_barrier(0);
-			if (with_dir && e.rot) {
-				const f3 ud = unwarp_direction(wdir);
-				const f3 c0 = ld3(e.rot, 3u * found), c1 = ld3(e.rot, 3u * found + 1u), c2 = ld3(e.rot, 3u * found + 2u); // the three columns
-				const float R[9] = {c0.x, c0.y, c0.z, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z};
-				const f3 rd = mat3_mul(R, ud);
-				wdir = warp_direction(rd);
+			// Everything the map-back reads of the tet hangs on `found` alone: its deformed vertices are the first 12 floats of its plane record (tet_planes_kernel copies
+			// them there: the floats ld3(e.verts, tets[found].*) returns, in the line the scan has just read), its canonical vertices and its rotation are its map-back
+			// record (DeviceEdit::mapback).  Vertices of both kinds in one trip, the rotation in a second -- where tets[found] -> verts -> orig -> rot were four
+			// dependent trips.  The arithmetic is what it was, value for value.
+			if constexpr (!RECORD) {
+				typedef uint32_t u4n __attribute__((ext_vector_type(4)));
+				const u4n tv = gp(reinterpret_cast<const u4n*>(e.tets))[found];
+				float bc[4];
+				{
+					const f3 a = ld3(e.verts, tv.x), b = ld3(e.verts, tv.y), c = ld3(e.verts, tv.z), d = ld3(e.verts, tv.w);
+					bary_tet(a, b, c, d, u, bc);
+				}
+				__builtin_amdgcn_sched_barrier(0);
+				f3 canon = bc[0] * ld3(e.orig, tv.x) + bc[1] * ld3(e.orig, tv.y);
+				canon = canon + bc[2] * ld3(e.orig, tv.z);
+				canon = canon + bc[3] * ld3(e.orig, tv.w);
+				wpos = e.diag_pow2 ? mk3((canon.x - e.aabb.mn[0]) * e.inv_diag[0], (canon.y - e.aabb.mn[1]) * e.inv_diag[1], (canon.z - e.aabb.mn[2]) * e.inv_diag[2])
+				                   : warp_position(canon, e.aabb);
+				__builtin_amdgcn_sched_barrier(0);
+				if (with_dir && e.rot) {
+					const f3 ud = unwarp_direction(wdir);
+					const f3 c0 = ld3(e.rot, 3u * found), c1 = ld3(e.rot, 3u * found + 1u), c2 = ld3(e.rot, 3u * found + 2u); // the three columns
+					const float R[9] = {c0.x, c0.y, c0.z, c1.x, c1.y, c1.z, c2.x, c2.y, c2.z};
+					const f3 rd = mat3_mul(R, ud);
+					wdir = warp_direction(rd);
+				}
+			} else {
+				typedef float f4n __attribute__((ext_vector_type(4)));
+				const NRS_GLOBAL f4n* pq = gp(reinterpret_cast<const f4n*>(e.planes)) + 8 * (size_t)found;
+				const NRS_GLOBAL f4n* mq = gp(reinterpret_cast<const f4n*>(e.mapback)) + 6 * (size_t)found;
+				const bool rotate = with_dir && e.rot;
+				const f4n v0 = pq[0], v1 = pq[1], v2 = pq[2];
+				const f4n o0 = mq[0], o1 = mq[1], o2 = mq[2];
+				float bc[4];
+				bary_tet(mk3(v0.x, v0.y, v0.z), mk3(v0.w, v1.x, v1.y), mk3(v1.z, v1.w, v2.x), mk3(v2.y, v2.z, v2.w), u, bc);
+				// (the rotation behind bary_tet, where the twelve vertex registers are free again: with all nine words requested at once the default instantiation needs
+				// 129 VGPRs and loses its fourth wave per SIMD -- so a second trip, whose data arrives under the canonical sum)
+				__builtin_amdgcn_sched_barrier(0);
+				f4n r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f};
+				float r2 = 0.f;
+				if (rotate) { r0 = mq[3]; r1 = mq[4]; r2 = reinterpret_cast<const NRS_GLOBAL float*>(mq)[20]; }
+				f3 canon = bc[0] * mk3(o0.x, o0.y, o0.z) + bc[1] * mk3(o0.w, o1.x, o1.y);
+				canon = canon + bc[2] * mk3(o1.z, o1.w, o2.x);
+				canon = canon + bc[3] * mk3(o2.y, o2.z, o2.w);
+				wpos = e.diag_pow2 ? mk3((canon.x - e.aabb.mn[0]) * e.inv_diag[0], (canon.y - e.aabb.mn[1]) * e.inv_diag[1], (canon.z - e.aabb.mn[2]) * e.inv_diag[2])
+				                   : warp_position(canon, e.aabb);
+				if (rotate) {
+					const f3 ud = unwarp_direction(wdir);
+					const float R[9] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2}; // the three columns
+					const f3 rd = mat3_mul(R, ud);
+					wdir = warp_direction(rd);
+				}
 			}
 			in_deformed = true;
 		}
@@ -882,9 +945,10 @@ __device__ __forceinline__ bool affine_warp(const DeviceEdit& e, bool with_dir, 
 	return e.a_hide_original && affine_contains(e.a_sel, wpos);
 }
 // EditOperator::map_rays / map_positions dispatch
+template <bool RECORD = true> // (tet_warp's)
 __device__ __forceinline__ bool edit_warp(const DeviceEdit& e, bool with_dir, f3& wpos, f3& wdir) {
 	if (e.kind == kEditAffine) return affine_warp(e, with_dir, wpos, wdir);
-	return tet_warp(e, with_dir, wpos, wdir);
+	return tet_warp<RECORD>(e, with_dir, wpos, wdir);
 }
 
 // Membrane ("Poisson") correction inputs of one sample: compute_residual_poisson_kernel's body (cage_deformation.cu:467-507)

@@ -166,6 +166,7 @@ struct nrs_edit {
 	size_t lut_idx_cap = 0;            // entries allocated
 	nrs::DeviceBuffer<float> d_rot;            // == de.rot when rotations are on
 	nrs::DeviceBuffer<float> d_planes;         // == de.planes, [T x 32] one 128-byte record per tet (tet_planes_kernel), follows the deformed vertices
+	nrs::DeviceBuffer<float> d_mapback;        // == de.mapback, [T x 24] one 96-byte record per tet: canonical vertices (written once), rotation (follows the deformed vertices with d_rot)
 	nrs::DeviceBuffer<uint32_t> d_counts;      // [5*128^3], all zero between builds
 	nrs::DeviceBuffer<uint32_t> d_tile_sums;
 	nrs::DeviceBuffer<unsigned long long> d_hit_masks; // per (tet, cascade): the count pass's first 128 cell / tet tests (two words per item), reused by the fill pass (nrs_cage.hip tet_mark_kernel)
@@ -179,6 +180,7 @@ struct nrs_edit {
 	nrs::DeviceBuffer<uint32_t> d_fine_off;    // [fine_cells_cap + 1]
 	nrs::DeviceBuffer<uint32_t> d_fine_counts; // [fine_cells_cap]
 	nrs::DeviceBuffer<uint32_t> d_fine_idx;
+	nrs::DeviceBuffer<uint2> d_fine_head;      // == de.fine_head when the table has head words, [fine_cells_cap]; dropped and rebuilt with d_fine_idx
 	nrs::DeviceBuffer<uint32_t> d_fine_tiles;  // [kFineScanTiles]
 	nrs::DeviceBuffer<int32_t> d_fine_win;     // [kCascades * 6] window + [30] total entries
 	size_t fine_cells_cap = 0, fine_idx_cap = 0;

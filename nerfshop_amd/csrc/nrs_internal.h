@@ -7,6 +7,7 @@
 #include "nrs_route.h"
 
 #include <stdlib.h>
+#include <hip/hip_vector_types.h> // uint2 (DeviceEdit::fine_head), for the translation units that include nothing of HIP themselves
 
 namespace nrs {
 
@@ -134,6 +135,12 @@ struct DeviceEdit {
 	int32_t         fine_win[kCascades][8]; // per cascade: first fine cell x, y, z, first offset index | extent x, y, z in fine cells (0: no tet reaches this cascade),
 	                                        // log2 of the fine cells per LUT cell and axis (0..2) or kFinePlain: this cascade keeps the LUT's own lists
 	const float*    planes;        // [T x 32] one 128-byte record per tet: its 4 vertices, the 4 face normals exactly as same_side_tet forms them, the 4 sign bits of dotV4 (tet_planes_kernel)
+	// Head word per fine cell (nullable; never set without fine_off): .x = the list's first index into fine_idx, .y = the list's first tet in the low kFineHeadTetBits bits,
+	// the list's length above them -- one 8-byte load instead of fine_off[cell], fine_off[cell + 1] and fine_idx[j0] (fine_lists_kernel<true> writes it with fine_idx)
+	const uint2*    fine_head;     // [fine cells]
+	// [T x 24] one 96-byte map-back record per tet: orig[tets[t].x .. w] (12 floats, tet_mapback_kernel at creation), the tet's rotation columns (9 floats, local_rotations_kernel
+	// on every move; zero without rotations), 3 floats of padding -- with the plane record's vertices all that tet_warp reads of the tet it found
+	const float*    mapback;
 	const uint8_t*  orig_bitfield;
 	const float*    shs;           // nullable unless apply_poisson
 	const float*    out_density;
@@ -261,6 +268,8 @@ constexpr uint32_t kFineScanTiles = kFineMaxCells / 4096;
 constexpr int32_t kFinePlain = 0xff;          // DeviceEdit::fine_win[c][7]: no fine table for cascade c
 constexpr int32_t kFineMaxList = 96;          // cascades whose longest LUT list exceeds this keep the plain scan (the coarse cascades of a small cage: hundreds of tets inside one cell,
                                               // hardly a sample; one wave of the build would walk such a list 64 fine cells wide -- 95 us at 285 tets)
+constexpr uint32_t kFineHeadTetBits = 25;     // DeviceEdit::fine_head[cell].y: first tet | list length << 25 (an edit of 2^25 tets or more keeps no heads)
+static_assert(kFineMaxList < (1 << (32 - kFineHeadTetBits)), "a fine list (a filtered LUT list of at most kFineMaxList tets) must fit the head word's length field");
 int launch_mvc_apply(uint32_t n_points, uint32_t n_cv, const float* d_weights, const float* d_cage, float* d_points, void* stream);
 int launch_bbox(uint32_t n, const float* d_verts, float* d_out6, void* stream);
 int launch_poisson_interpolate(uint32_t n_points, uint32_t n_cv, const float* d_gamma, const float* d_per_cage, float* d_shs, float* d_out_density, float* d_res_density, void* stream);
@@ -275,8 +284,11 @@ int launch_tet_planes(uint32_t n_tets, const float* d_verts, const uint32_t* d_t
 int launch_fine_window(const uint32_t* d_lut_off, int32_t* d_window_out, void* stream);
 // counts (FILL = false: d_counts[n_padded], then the exclusive scan into d_fine_off[n_padded + 1] and *d_total) or fills (FILL = true: d_fine_idx) the fine lists of `de`'s windows
 int launch_fine_count_scan(const DeviceEdit& de, uint32_t n_fine_cells, uint32_t* d_counts, uint32_t* d_tile_sums, uint32_t* d_fine_off, uint32_t* d_total, void* stream);
-int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t* d_fine_off, uint32_t* d_fine_idx, void* stream);
-int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, void* stream);
+int launch_fine_fill(const DeviceEdit& de, uint32_t n_fine_cells, const uint32_t* d_fine_off, uint32_t* d_fine_idx, uint2* d_fine_head /* [fine cells]; nullable: no head words */, void* stream);
+// d_mapback (nullable): the rotation part of the map-back records (DeviceEdit::mapback) is written with d_out
+int launch_local_rotations(uint32_t n_tets, const float* d_verts, const float* d_orig, const uint32_t* d_tets, float* d_out, float* d_mapback, void* stream);
+// the whole map-back record of every tet: canonical vertices, and the rotations d_rot holds now (null: zeros)
+int launch_tet_mapback(uint32_t n_tets, const float* d_orig, const uint32_t* d_tets, const float* d_rot, float* d_mapback, void* stream);
 
 // marching cubes (nrs_mesh.hip).  The lattice is walked by its linear point index i = x + y * rx + z * rx * ry in blocks of kMcBlock points; a point owns the (up to three)
 // vertices on its +x / +y / +z lattice edges and the triangles of the cell it is the lowest corner of.

@@ -611,18 +611,18 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 		if (ops && act) { // map_rays, last-to-first (tn:2899-2902)
 #if NRS_MEASURE == 2
 			{ f3 wp2 = wpos, wd2 = wdir; asm volatile("" : "+v"(wp2.x), "+v"(wp2.y), "+v"(wp2.z)); bool e2 = false;
-			  for (int ei = a2.n_edits - 1; ei >= 0; --ei) e2 |= AFFINE ? edit_warp(a2.edits[ei], true, wp2, wd2) : tet_warp(a2.edits[ei], true, wp2, wd2);
+			  for (int ei = a2.n_edits - 1; ei >= 0; --ei) e2 |= AFFINE ? edit_warp<!POISSON>(a2.edits[ei], true, wp2, wd2) : tet_warp<!POISSON && GATE == 0, GATE == 0>(a2.edits[ei], true, wp2, wd2);
 			  asm volatile("" :: "v"(wp2.x), "v"(wp2.y), "v"(wp2.z), "v"(wd2.x), "v"(wd2.y), "v"(wd2.z), "s"((int)__ballot(e2))); }
 #endif
 			for (int ei = a2.n_edits - 1; ei >= 0; --ei) {
 				if (AFFINE) {
-					empty |= edit_warp(a2.edits[ei], true, wpos, wdir);
+					empty |= edit_warp<!POISSON>(a2.edits[ei], true, wpos, wdir); // (the membrane catch-all rows stand at their register limit like the membrane kernel)
 				} else if (POISSON) {
 					uint32_t scan; // (a local of the iteration, selected below: a pointer that is sometimes null made warp_scan a stack object)
-					empty |= tet_warp(a2.edits[ei], true, wpos, wdir, sm.coarse, &scan);
+					empty |= tet_warp<false>(a2.edits[ei], true, wpos, wdir, sm.coarse, &scan); // (the parent's map-back: no register to spare, nrs_device.cuh)
 					if (ei == a2.n_edits - 1) warp_scan = scan;
 				} else {
-					empty |= tet_warp(a2.edits[ei], true, wpos, wdir, sm.coarse, nullptr, PROF ? &pf_scan : nullptr);
+					empty |= tet_warp<GATE == 0, GATE == 0>(a2.edits[ei], true, wpos, wdir, sm.coarse, nullptr, PROF ? &pf_scan : nullptr); // (the gated kernel keeps the long chain: nrs_device.cuh find_tet)
 				}
 			}
 		}
