@@ -381,6 +381,24 @@ int nrs_network_density(nrs_model* model, void* stream, uint32_t n, const float*
  *   into a 7-row matrix -- the caller that wants that picture forms it from v.  d_in is [n x 7] f32. */
 int nrs_network_input_gradient(nrs_model* model, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, float* d_grad_out_nx3);
 int nrs_network_visualize_activation(nrs_model* model, void* stream, uint32_t layer, uint32_t dimension, uint32_t n, const float* d_in, float* d_out_n);
+/* nrs_network_backward <- NerfNetworkFull::backward (nerf_network_full.h:142-221) for base.json's architecture (density_hidden_layers 1, rgb_hidden_layers 2, sh_degree 4,
+ *   any log2_hashmap_size, n_extra_dims 0) at the default numerics: the gradient of a loss with respect to every parameter, given dL_doutput.  One persistent launch
+ *   that recomputes the forward pass of each 64-sample tile (the values of nrs_network_inference) and stores no activation in global memory.
+ *   d_in [n x ld_in] f32, ld_in >= 7.  d_dL_doutput_fp16: planes [16 x ld_dout] (ld_dout >= n) or interleaved [n x 16]; rows 0..2 are the rgb gradients and row 3 the
+ *   density's (added onto the density network's output 0 in fp16, add_density_gradient); rows 4..15 are never read (extract_rgb copies three rows).  The gradients pass
+ *   the layers in fp16, one rounding per layer boundary, as in tiny-cuda-nn: callers multiply dL_doutput by a loss scale (128 there) and divide the result by it.
+ *   d_dL_dparams: nrs_model_n_params floats in the parameter blob's own order, [density | rgb | grid], matrices W[j * n_in + k]; rows 3..15 of the rgb output matrix
+ *   come out zero.  fp32 sums (tiny-cuda-nn keeps fp16 gradients: DESIGN.md 4).  accumulate 0: the buffer is zeroed on the stream first (EGradientMode::Overwrite);
+ *   1: added to (Accumulate).  Sums are atomic: the last bits depend on the order.
+ *   d_dL_dinput: NULL, or [n x ld_in] f32: floats 0..2 of a record receive dL/dposition through the hash grid, floats 3..ld_in-1 are written as zero -- the gradient through the SH
+ *   encoding of the direction is not propagated.
+ *   NRS_ERR_INVALID_ARG, before any HIP call: a NULL model / d_dL_dparams / (with n > 0) d_in / d_dL_doutput_fp16, ld_in < 7, an unknown layout, planes with ld_dout < n, an n_params
+ *   other than the description implies.  NRS_ERR_UNSUPPORTED naming the field: the other networks of the family, light directions, nrs_model_set_numerics other than
+ *   FP32 / FP32.  NRS_ERR_STATE before parameters were set.  n = 0 is NRS_OK (the buffer is still zeroed when accumulate is 0).  No allocation, no host
+ *   synchronisation.  Callers detect this entry point by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes. */
+int nrs_network_backward(nrs_model* model, void* stream, uint32_t n, const float* d_in, uint32_t ld_in,
+                         const void* d_dL_doutput_fp16, uint32_t ld_dout, int layout, float* d_dL_dparams, size_t n_params, int accumulate,
+                         float* d_dL_dinput);
 /* The network on a regular grid ("next" row f4: the marching-cubes / volume-export callers of the operator).
  * nrs_density_on_grid <- Testbed::get_density_on_grid (src/testbed_nerf.cu:4538): point (x,y,z) of the res3d grid sits at
  *   aabb_min + (x/rx, y/ry, z/rz) * (aabb_max - aabb_min); d_out[x + y*rx + z*rx*ry] = raw density (fp16 network output as float),

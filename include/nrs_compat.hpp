@@ -90,6 +90,13 @@ public:
 		if (dim != 3) throw std::runtime_error("NerfNetwork::input_gradient: the render path differentiates output 3 (the density) only");
 		check(nrs_network_input_gradient(m_model, stream, input.n, input.data, input.rows, d_grad_nx3), "nrs_network_input_gradient");
 	}
+	// tcnn::DifferentiableObject::backward(stream, ctx, input, output, dL_doutput, dL_dinput, use_inference_params, param_gradients_mode) (nerf_network_full.h:142-221).
+	// The forward context and `output` of the reference carry the activations; here the kernel recomputes them, so both are absent.  d_dL_dparams: n_params() floats,
+	// fp32, the blob's order; d_dL_dinput: null, or [n x input.rows] f32 (position rows only: nrs.h).  accumulate = EGradientMode::Accumulate, else Overwrite.
+	void backward(void* stream, const InputMatrix& input, const OutputMatrix& dL_doutput, float* d_dL_dparams, float* d_dL_dinput = nullptr, bool accumulate = false) {
+		check(nrs_network_backward(m_model, stream, input.n, input.data, input.rows, dL_doutput.data, dL_doutput.n, dL_doutput.layout, d_dL_dparams, n_params(),
+		                           accumulate ? 1 : 0, d_dL_dinput), "nrs_network_backward");
+	}
 	// tcnn::Network::visualize_activation(stream, layer, dimension, input, output): the activation itself, f32 [n] (testbed_nerf.cu:2926, :3159)
 	void visualize_activation(void* stream, uint32_t layer, uint32_t dimension, const InputMatrix& input, float* d_out_n) {
 		if (input.rows != NRS_NETWORK_INPUT_FLOATS) throw std::runtime_error("NerfNetwork::visualize_activation: input must have 7 rows");

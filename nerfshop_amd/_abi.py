@@ -194,6 +194,7 @@ EXPORTS = [
     "nrs_selection_create", "nrs_selection_destroy", "nrs_selection_reset", "nrs_selection_grow", "nrs_selection_upscale", "nrs_selection_state",
     "nrs_selection_get_cells", "nrs_selection_get_bitfield", "nrs_selection_set_structuring_elements", "nrs_bitfield_morph", "nrs_bitfield_morph_host",
     "nrs_selection_dilate", "nrs_selection_erode", "nrs_selection_fine_mesh",
+    "nrs_network_backward",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -279,6 +280,8 @@ def load():
     lib.nrs_hashgrid_encode.argtypes = [P, P, U32, P, U32, P]
     lib.nrs_network_input_gradient.argtypes = [P, P, U32, P, U32, P]
     lib.nrs_network_visualize_activation.argtypes = [P, P, U32, U32, U32, P, P]
+    if hasattr(lib, "nrs_network_backward"):  # (an A/B build of the parent tree through NRS_LIB_PATH has none: tools/network_backward_probe.py --parent-lib)
+        lib.nrs_network_backward.argtypes = [P, P, U32, P, U32, P, U32, I, P, C.c_size_t, I, P]
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

@@ -197,6 +197,17 @@ void nrs::make_weight_fragments(const uint16_t* w, uint16_t* frag, uint16_t one)
 				at(8 + mb * 2 + 1, lane, e) = Wr1[(32 * mb + i) * 32 + 16 + 8 * g + e]; // SH coefficient 8g+e
 				at(38 + mb, lane, e) = Wr1x[(32 * mb + i) * 16 + 8 * g + e];            // R1L: light component / padding one 8g+e (rows as in R1)
 			}
+			// The transposed operands of the backward pass (nrs_network_backward.hip), built as Bwd is: dL/din[32 mb + i] = sum_k W[k][32 mb + i] dL/dout[k], the B operand
+			// of k step ks being the packed dL/dout in the layout the D tiles come out in, k = 16 ks + hidden_row(0, g, e).  TD2[mb] (density output layer, 16 outputs: one k
+			// step), T1[ks] (rgb layer 0; rows = its 32 inputs), T2[mb][ks], T3[mb] (rgb output layer: rows 0..2 only -- extract_rgb copies three rows, the padding rows' weights
+			// must not meet anything).
+			const int k0 = hidden_row(0, g, e);
+			for (int mb = 0; mb < 2; ++mb) {
+				at(40 + mb, lane, e) = Wd2[k0 * 64 + 32 * mb + i];
+				at(54 + mb, lane, e) = k0 < 3 ? Wr3[k0 * 64 + 32 * mb + i] : (uint16_t)0;
+				for (int ks = 0; ks < 4; ++ks) at(46 + mb * 4 + ks, lane, e) = Wr2[(16 * ks + k0) * 64 + 32 * mb + i];
+			}
+			for (int ks = 0; ks < 4; ++ks) at(42 + ks, lane, e) = Wr1[(16 * ks + k0) * 32 + i];
 		}
 	}
 }

@@ -43,6 +43,32 @@ int nrs_network_input_gradient(nrs_model* m, void* stream, uint32_t n, const flo
 	NRS_LAUNCH(launch_network(m->dm, 3, n, d_in, ld_in, d_grad_out, 3, 0, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
+// NerfNetwork::backward (nerf_network_full.h:142-221).  Everything that can be refused is refused before the first HIP call; nothing is allocated and nothing waits.
+int nrs_network_backward(nrs_model* m, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, const void* d_dL_doutput_fp16, uint32_t ld_dout, int layout,
+                         float* d_dL_dparams, size_t n_params, int accumulate, float* d_dL_dinput) {
+	if (!m || !d_dL_dparams || (n && (!d_in || !d_dL_doutput_fp16))) return fail(NRS_ERR_INVALID_ARG, "nrs_network_backward: NULL argument");
+	if (ld_in < NRS_NETWORK_INPUT_FLOATS) return fail(NRS_ERR_INVALID_ARG, "nrs_network_backward: ld_in < 7");
+	if (layout != NRS_PLANES && layout != NRS_INTERLEAVED) return fail(NRS_ERR_INVALID_ARG, "nrs_network_backward: layout is neither NRS_PLANES nor NRS_INTERLEAVED");
+	if (layout == NRS_PLANES && ld_dout < n) return fail(NRS_ERR_INVALID_ARG, "nrs_network_backward: ld_dout < n");
+	const size_t expect = (size_t)n_mlp_weights(m->desc, m->n_extra_dims) + (size_t)m->total_entries * 2;
+	if (n_params != expect) {
+		char buf[160];
+		snprintf(buf, sizeof(buf), "nrs_network_backward: n_params is %zu, the description implies %zu", n_params, expect);
+		return fail(NRS_ERR_INVALID_ARG, buf);
+	}
+	const char* field = nullptr;
+	if (m->desc.density_hidden_layers != 1u) field = "density_hidden_layers (1 is supported)";
+	else if (m->desc.sh_degree != 4u) field = "sh_degree (4 is supported: no backward pass for NerfNetworkNoDir)";
+	else if (m->desc.rgb_hidden_layers != 2u) field = "rgb_hidden_layers (2 is supported)";
+	else if (m->n_extra_dims != 0u) field = "n_extra_dims (0 is supported: no backward pass with light directions)";
+	else if (m->dm.numerics != 0u) field = "nrs_model_set_numerics (NRS_GRID_ACC_FP32 / NRS_MLP_ACC_FP32 are supported)";
+	if (field) return fail(NRS_ERR_UNSUPPORTED, std::string("nrs_network_backward: ") + field);
+	if (!m->have_params) return fail(NRS_ERR_STATE, "nrs_network_backward: parameters not set (nrs_model_set_params)");
+	HIP_TRY(hipSetDevice(m->ctx->device));
+	if (!accumulate) HIP_TRY(hipMemsetAsync(d_dL_dparams, 0, n_params * sizeof(float), (hipStream_t)stream)); // EGradientMode::Overwrite
+	NRS_LAUNCH(launch_network_backward(m->dm, n, d_in, ld_in, d_dL_doutput_fp16, ld_dout, layout, d_dL_dparams, d_dL_dinput, m->ctx->n_cus, stream));
+	return NRS_OK;
+}
 int nrs_network_visualize_activation(nrs_model* m, void* stream, uint32_t layer, uint32_t dimension, uint32_t n, const float* d_in, float* d_out) {
 	NRS_TRY(check_net(m, d_in, d_out, "nrs_network_visualize_activation"));
 	if (dimension >= network_layer_width(m->desc, layer, m->n_extra_dims))

@@ -61,8 +61,9 @@ struct LevelParams {
 // These 26 fragments are staged into LDS.  Behind them, in HBM only: Bwd[ks] (4), the A operands of dL/dfeatures = W1^T dL/dhidden (render mode Normals),
 // R2b[mb][ks] (8), the third hidden layer of an rgb network that has one (DeviceModel::rgb_deep; base_3layer.json), and R1L[mb] (2), the third k block of
 // rgb layer 0 of a network trained with light directions (DeviceModel::n_extra_dims; rows in R1's order, k = 8 g + e <-> input column 32 + k).
+// Last, the transposed operands of the backward pass (nrs_network_backward.hip stages them and Bwd into its own LDS): TD2[mb] (2), T1[ks] (4), T2[mb][ks] (8), T3[mb] (2).
 constexpr uint32_t kNumFrags = 26;
-constexpr uint32_t kNumFragsDevice = 40;
+constexpr uint32_t kNumFragsDevice = 56;
 constexpr uint32_t kFragBytes = 64 * 8 * 2;
 constexpr uint32_t kWfragBytes = kNumFrags * kFragBytes; // 26 KiB: the LDS image
 constexpr uint32_t kWfragDeviceBytes = kNumFragsDevice * kFragBytes;
@@ -215,6 +216,10 @@ int launch_trace_samples(const DeviceModel& m, const nrs_render_params& p, uint3
 // ld_light: floats 7..9 of a record are that sample's warped light direction (a model with n_extra_dims = 3 and ld_in >= 10); else DeviceModel::light01
 int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out,
                    int layout, int n_cus, void* stream, bool per_sample_light = false);
+// NerfNetwork::backward for base.json's architecture at the default numerics (nrs_network_backward.hip): parameter gradients ADDED to d_dparams (fp32, the blob's order),
+// optionally dL/dposition into floats 0..2 of d_dinput's records
+int launch_network_backward(const DeviceModel& m, uint32_t n, const float* d_in, uint32_t ld_in, const void* d_dout, uint32_t ld_dout, int layout,
+                            float* d_dparams, float* d_dinput, int n_cus, void* stream);
 int launch_selection_rays(const DeviceModel& m, const nrs_render_params& p, const int32_t* d_pixels, uint32_t n, float threshold,
                           float* d_positions, uint32_t* d_cells, uint8_t* d_found, void* stream);
 int launch_poisson_fit(const DeviceModel& m, uint32_t n_verts, uint32_t n_sh, const float* d_coords, const void* d_net, int is_inside, float scale,

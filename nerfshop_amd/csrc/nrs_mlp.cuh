@@ -56,6 +56,11 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define NRS_FRAG_R3(ks) (20 + (ks))
 #define NRS_FRAG_R2B(mb, ks) (30 + (mb) * 4 + (ks)) // (HBM only, like NRS_FRAG_BWD: the third rgb hidden layer of base_3layer.json)
 #define NRS_FRAG_R1L(mb) (38 + (mb)) // (HBM only: the third k block of rgb layer 0 of a network trained with light directions, n_extra_dims = 3)
+// (HBM only, staged by the backward kernel: the transposed matrices, k = the D-tile row order -- make_weight_fragments)
+#define NRS_FRAG_TD2(mb) (40 + (mb))
+#define NRS_FRAG_T1(ks) (42 + (ks))
+#define NRS_FRAG_T2(mb, ks) (46 + (mb) * 4 + (ks))
+#define NRS_FRAG_T3(mb) (54 + (mb))
 
 enum { KIND_DENSE = 0, KIND_HASHED = 1, KIND_MIXED = 2, KIND_RECORD = 3, KIND_SPARSE = 4, KIND_SKIP = 5 };
 
@@ -120,6 +125,17 @@ __device__ __forceinline__ float fma_mix_hi(float w, uint32_t entry, float acc) 
 	return r;
 }
 
+// Corner c (bit 0 x, bit 1 y, bit 2 z) of the cell (gx, gy, gz) at one level: its entry (tcnn's index function, exact for any position) and its trilinear weight
+// ((wx' * wy') * wz').  The forward's slow path below and the backward pass's scatter (nrs_network_backward.hip) both go through it.
+__device__ __forceinline__ void cell_corner(const LevelParams& lp, uint32_t gx, uint32_t gy, uint32_t gz, float wx, float wy, float wz, int c, uint32_t& index, float& weight) {
+	const uint32_t cx = gx + (c & 1), cy = gy + ((c >> 1) & 1), cz = gz + ((c >> 2) & 1);
+	index = lp.hashed ? ((cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u)) : (cx + cy * lp.resolution + cz * lp.res2);
+	index %= lp.count;
+	weight = 1.0f;
+	weight *= (c & 1) ? wx : 1.0f - wx;
+	weight *= (c & 2) ? wy : 1.0f - wy;
+	weight *= (c & 4) ? wz : 1.0f - wz;
+}
 // Exact tcnn index for any position (also far outside [0,1]^3): the rarely taken out-of-line path.
 template <bool NETACC = false>
 __device__ __forceinline__ void level_eval_slow(const GridView gv, const LevelParams lp, uint32_t gx, uint32_t gy, uint32_t gz,
@@ -128,13 +144,9 @@ __device__ __forceinline__ void level_eval_slow(const GridView gv, const LevelPa
 	_Float16 h0 = (_Float16)0.f, h1 = (_Float16)0.f;
 	#pragma unroll 1
 	for (int c = 0; c < 8; ++c) {
-		const uint32_t cx = gx + (c & 1), cy = gy + ((c >> 1) & 1), cz = gz + ((c >> 2) & 1);
-		uint32_t index = lp.hashed ? ((cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u)) : (cx + cy * lp.resolution + cz * lp.res2);
-		index %= lp.count;
-		float weight = 1.0f;
-		weight *= (c & 1) ? wx : 1.0f - wx;
-		weight *= (c & 2) ? wy : 1.0f - wy;
-		weight *= (c & 4) ? wz : 1.0f - wz;
+		uint32_t index;
+		float weight;
+		cell_corner(lp, gx, gy, gz, wx, wy, wz, c, index, weight);
 		const half2v hv = __builtin_bit_cast(half2v, grid_load(gv, lp.offset + index));
 		if (NETACC) {
 			h0 = h0 + (_Float16)(weight * (float)hv[0]);

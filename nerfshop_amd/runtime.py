@@ -233,6 +233,28 @@ class NerfNetwork:
         assert output.shape == (n, 3) and output.is_contiguous() and input.is_contiguous()
         check(self.lib.nrs_network_input_gradient(self.h, _stream_handle(stream), n, input.data_ptr(), input.shape[1], output.data_ptr()))
 
+    def backward(self, stream, input, dL_doutput, dL_dparams, dL_dinput=None, accumulate=False):
+        """NerfNetwork::backward (nrs_network_backward): input [n, >= 7] f32; dL_doutput fp16, [16, n_el] (planes) or [n, 16], rows 0..2 rgb and row 3 density
+        (callers scale it by their loss scale); dL_dparams [n_params] f32 in the blob's order, overwritten unless `accumulate`; dL_dinput None or an f32 tensor
+        shaped like input (floats 0..2 of a record get dL/dposition, the rest of it zero).  All cuda tensors; base.json's architecture at the default numerics."""
+        _require_cuda(input, torch.float32, "input")
+        _require_cuda(dL_doutput, torch.float16, "dL_doutput")
+        _require_cuda(dL_dparams, torch.float32, "dL_dparams")
+        if input.dim() != 2 or input.shape[1] < 7 or not input.is_contiguous():
+            raise NrsError("NerfNetwork::backward input must be a contiguous [n, >= 7] tensor")
+        if dL_dparams.dim() != 1 or not dL_dparams.is_contiguous() or not dL_doutput.is_contiguous():
+            raise NrsError("NerfNetwork::backward: dL_dparams must be a contiguous 1-d tensor and dL_doutput contiguous")
+        n = input.shape[0]
+        layout, ld = self._out_layout(dL_doutput, n)
+        din = None
+        if dL_dinput is not None:
+            _require_cuda(dL_dinput, torch.float32, "dL_dinput")
+            if tuple(dL_dinput.shape) != tuple(input.shape) or not dL_dinput.is_contiguous():
+                raise NrsError("NerfNetwork::backward: dL_dinput must be contiguous and shaped like input")
+            din = dL_dinput.data_ptr()
+        check(self.lib.nrs_network_backward(self.h, _stream_handle(stream), n, input.data_ptr(), input.shape[1], dL_doutput.data_ptr(), ld, layout,
+                                            dL_dparams.data_ptr(), dL_dparams.numel(), 1 if accumulate else 0, din))
+
     def visualize_activation(self, stream, layer, dimension, input, output):
         """Network::visualize_activation: unit `dimension` of forward_activations(layer), input [n, 7] f32, output [n] f32 (cuda tensors)."""
         _require_cuda(input, torch.float32, "input")
