@@ -832,6 +832,82 @@ int  nrs_selection_dilate(nrs_ctx* ctx, void* stream, nrs_selection* sel);
 int  nrs_selection_erode(nrs_ctx* ctx, void* stream, nrs_selection* sel);
 int  nrs_selection_fine_mesh(nrs_ctx* ctx, void* stream, nrs_selection* sel, int use_morphological, nrs_mesh** mesh_out);
 
+/* ---- training rays: sample generation, the ray loss and its gradient ---------------------------------------------------------------------------- */
+/* The two steps between "rays + the colours they should have" and nrs_network_backward: generate_training_samples_nerf (src/testbed_nerf.cu:1087, from :1188 on: everything
+ * after the ray exists) and compute_loss_kernel_train_nerf (:1685-1985) with the seven losses of :103-171.  Callers detect these entry points by symbol (dlsym);
+ * NRS_ABI_VERSION is unchanged because no existing layout changes.  Not here: the dataset (image / pixel selection, lens distortion, rolling shutter), the envmap and its
+ * gradient, exposure and its gradient, the error map and sharpness, max_level_rand_training, image / pixel PDFs (img_pdf = xy_pdf = 1), fill_rollover_and_rescale
+ * (nrs_network_backward takes any n), the camera-gradient kernels, the distill variants, light-direction models.
+ *
+ * Both calls are asynchronous on `stream`, never wait for the device and keep their per-ray workspace in the model: it is allocated on the first call of a size and
+ * reused afterwards (a larger n_rays grows it, which frees the smaller one: hipFree waits for the device).  Because the workspace belongs to the model, two of these calls
+ * on ONE model must not be in flight on different streams at the same time.  No float atomics anywhere: two calls with the same inputs give bit-identical outputs.
+ *
+ * DEVIATIONS from the reference, all deliberate: the ORDER (next paragraph); per-ray arrays in place of the dataset look-ups (nrs_ray_loss); and two guards of the
+ * generator's walk against rays it could never end on, which the reference would hang on: a ray whose origin is not finite or whose direction's length lies outside
+ * [0.5, 2] has no samples (unit length is otherwise not checked), and a walk gives up after 65 536 empty cells (a ray through the largest box crosses a few thousand).
+ *
+ * ORDER.  The reference takes a ray's first sample (`base`) and its slot from atomicAdd, so its layout depends on arrival order.  Here both come from an exclusive scan in
+ * input order, in both calls; everything else (which rays are kept, what is clipped) follows the reference's rule with the scan's value in place of the atomic's.
+ *
+ * nrs_training_samples <- :1188-1246.  d_rays [n_rays x 6] f32: origin, direction (unit length expected, not checked).  d_jitter [n_rays] f32 in [0, 1) or NULL for 0:
+ *   the reference's random_val(rng).  Per ray: tmin = max(aabb.ray_intersect(o, d).x, 0), startt = tmin + calc_dt(tmin, cone) * jitter, then while the training box contains
+ *   o + t d and j < NERF_STEPS (1024): a sample where the cell is occupied at mip_from_dt(dt, pos) (t += dt), advance_to_next_voxel otherwise.  The box and the density
+ *   bitfield are the model's.  With j_i the count of ray i: base(i) = the sum of j_k over rays k < i; ray i is emitted iff j_i > 0 and base(i) + j_i <= max_samples
+ *   (:1214-1221); emitted rays keep their input order.
+ *   d_coords_out [max_samples x ld] f32, ld >= 7: record base + s = warp_position(pos), warp_dt(dt), warp_direction(d) of sample s; floats 7..ld-1 are never written.
+ *   Every record from the end of the last emitted ray up to max_samples gets floats 0..6 = 0 (a superset of [min(total, max_samples), max_samples): the gap a dropped ray
+ *   leaves is zeroed too), so inference and backward can run on n = max_samples without reading a counter back.
+ *   d_numsteps_out [n_rays x 2] u32: (count, base) per EMITTED ray, compact.  d_ray_indices_out [n_rays] u32: the input index of each emitted ray.  Entries at or past the
+ *   number of emitted rays are not written.  d_counters [2] u32: [0] rays emitted, [1] the sum of all counts (the reference's numsteps_counter: dropped rays count).
+ *   NRS_ERR_INVALID_ARG, before any HIP call: a NULL model / d_coords_out / d_counters / (with n_rays > 0) d_rays / d_numsteps_out / d_ray_indices_out, ld < 7,
+ *   max_samples == 0, a non-finite or negative cone_angle_constant, n_rays > 2^21 (2^21 rays of NERF_STEPS samples are 2^31: the 32-bit sample counters).
+ *   NRS_ERR_UNSUPPORTED: a model with n_extra_dims != 0.  NRS_ERR_STATE: no density bitfield.
+ *   n_rays == 0 is NRS_OK: the counters are zeroed and the records zero-filled.
+ *
+ * nrs_ray_loss <- :1685-1985.  Inputs: d_numsteps [n_rays x 2] (count, base): bases in any order, with gaps; d_coords [n_samples x ld_in] f32 and d_output_fp16
+ *   (planes [16 x ld_out] or interleaved [n_samples x 16], exactly what nrs_network_inference wrote); a ray whose base + count exceeds n_samples, or whose count exceeds NERF_STEPS
+ *   (1024), is treated as count 0.
+ *   d_ray_counter: u32 on the device, the number of live rays (the generator's d_counters[0]), capped at n_rays; NULL = n_rays.  n_rays itself is the normaliser.  Indexed by
+ *   ray slot like d_numsteps (the caller gathers with d_ray_indices_out): d_target_rgba [n_rays x 4] f32, linear and premultiplied (read_rgba); d_background [n_rays x 3],
+ *   sRGB-encoded (train_with_random_bg_color), or NULL for params->background; d_ray_origins [n_rays x 3], or NULL when near_distance <= 0.
+ *   Per live ray, EPS = 1e-4: the forward composite stops before the first sample with T < EPS (M samples consumed of N); target and background by colour space and
+ *   train_in_linear_colors (:1808-1823); if M == N the background is added behind (C += T bg).  cbase(i) = the sum of M_k over live rays k < i,
+ *   M' = min(max_samples_compacted - min(max_samples_compacted, cbase), M).  d_numsteps_out [n_rays x 2] = (M', cbase) for live rays (others not written; it must NOT
+ *   alias d_numsteps: the gradient pass reads both); *d_counter_out = the sum of M, unclipped.  d_loss [n_rays] (may be NULL) = mean(L) / n_rays, 0 for a ray with
+ *   M' == 0 and for rays at or past the counter.  The gradient pass replays samples 0..M'-1 and writes, at compact index cbase + j: d_coords_out = the input record
+ *   (ld_in floats) and rows 0..3 of d_dL_doutput_fp16 (planes [16 x ld_dl], ld_dl >= max_samples_compacted, or interleaved [max_samples_compacted x 16]; rows 4..15 are
+ *   never written and nrs_network_backward never reads them), round-to-nearest fp16, no clamp:
+ *     dL[c] = s (w_j g_c network_to_rgb_derivative(out[c]) + max(0, l2reg out[c])), s = loss_scale / n_rays, l2reg = 1e-4 iff rgb_activation is Exponential;
+ *     dL[3] = s network_to_density_derivative(out[3]) dt_j dot(g, T rgb_j - (C - C2)) + (out[3] < 0 ? -l1 : 0) + (out[3] > -10 && |pos_j - origin| < near_distance ? 1e-4 : 0),
+ *   with T the transmittance AFTER sample j and C2 the running colour including it (:1910-1916); l1 = 1e-4 iff density_l1_reg; the last two terms are not scaled by s,
+ *   as in the reference.  Compact indices [min(sum M, max_samples_compacted), max_samples_compacted) get dL rows 0..3 = 0 and zero records: nrs_network_backward can run
+ *   on n = max_samples_compacted without a read-back, and a zero dL contributes nothing to any sum.
+ *   NRS_ERR_INVALID_ARG, before any HIP call: a NULL model / params / d_coords_out / d_dL_doutput_fp16 / d_counter_out / (with n_rays > 0) d_numsteps / d_coords /
+ *   d_output_fp16 / d_target_rgba / d_numsteps_out, d_numsteps_out == d_numsteps, a struct_size other than sizeof, an unknown loss, colour space or layout, ld_in < 7,
+ *   planes with ld_out < n_samples or ld_dl < max_samples_compacted, max_samples_compacted == 0, a non-finite loss_scale, near_distance > 0 with NULL d_ray_origins,
+ *   n_rays > 2^21, d_coords_out overlapping d_coords (rays read and write different ranges at the same time: the compaction is not done in place).
+ *   n_rays == 0 is NRS_OK (the counter is zeroed, the compact buffers are zero-filled). */
+typedef enum nrs_loss_type { NRS_LOSS_L2 = 0, NRS_LOSS_L1 = 1, NRS_LOSS_MAPE = 2, NRS_LOSS_SMAPE = 3, NRS_LOSS_HUBER = 4, NRS_LOSS_LOG_L1 = 5,
+                             NRS_LOSS_RELATIVE_L2 = 6 } nrs_loss_type; /* ELossType's order, common.h:96 */
+typedef struct nrs_ray_loss_params {
+	uint32_t struct_size;            /* refused unless == sizeof(nrs_ray_loss_params) */
+	uint32_t loss_type;              /* nrs_loss_type */
+	float    loss_scale;
+	uint32_t color_space;            /* NRS_COLOR_LINEAR | NRS_COLOR_SRGB */
+	uint32_t train_in_linear_colors;
+	float    background[3];          /* sRGB-encoded like m_background_color; used when d_background is NULL */
+	float    near_distance;          /* <= 0: term off, d_ray_origins may be NULL */
+	uint32_t density_l1_reg;         /* the caller's evaluation of *mean_density_ptr < NERF_MIN_OPTICAL_THICKNESS (0.01) */
+	uint32_t max_samples_compacted;
+} nrs_ray_loss_params;
+int nrs_training_samples(nrs_model* model, void* stream, uint32_t n_rays, const float* d_rays, const float* d_jitter, float cone_angle_constant, uint32_t max_samples,
+                         float* d_coords_out, uint32_t ld, uint32_t* d_numsteps_out, uint32_t* d_ray_indices_out, uint32_t* d_counters);
+int nrs_ray_loss(nrs_model* model, void* stream, const nrs_ray_loss_params* params, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_numsteps,
+                 uint32_t n_samples, const float* d_coords, uint32_t ld_in, const void* d_output_fp16, uint32_t ld_out, int out_layout, const float* d_target_rgba,
+                 const float* d_background, const float* d_ray_origins, uint32_t* d_numsteps_out, float* d_coords_out, void* d_dL_doutput_fp16, uint32_t ld_dl,
+                 int dl_layout, float* d_loss, uint32_t* d_counter_out);
+
 #ifdef __cplusplus
 }
 #endif

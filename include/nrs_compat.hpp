@@ -97,6 +97,21 @@ public:
 		check(nrs_network_backward(m_model, stream, input.n, input.data, input.rows, dL_doutput.data, dL_doutput.n, dL_doutput.layout, d_dL_dparams, n_params(),
 		                           accumulate ? 1 : 0, d_dL_dinput), "nrs_network_backward");
 	}
+	// generate_training_samples_nerf from the ray on (testbed_nerf.cu:1188-1246; nrs.h "training rays"): coords_out [max_samples x rows] f32, rows >= 7
+	void training_samples(void* stream, uint32_t n_rays, const float* d_rays, const float* d_jitter, float cone_angle_constant, uint32_t max_samples,
+	                      float* d_coords_out, uint32_t rows, uint32_t* d_numsteps_out, uint32_t* d_ray_indices_out, uint32_t* d_counters) {
+		check(nrs_training_samples(m_model, stream, n_rays, d_rays, d_jitter, cone_angle_constant, max_samples, d_coords_out, rows, d_numsteps_out, d_ray_indices_out,
+		                           d_counters), "nrs_training_samples");
+	}
+	// compute_loss_kernel_train_nerf (testbed_nerf.cu:1685-1985): coords = the samples' records (coords.n of them), output what inference wrote for them,
+	// dL_doutput and d_coords_out the compacted results (params.max_samples_compacted records)
+	void ray_loss(void* stream, const nrs_ray_loss_params& params, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_numsteps, const InputMatrix& coords,
+	              const OutputMatrix& output, const float* d_target_rgba, const float* d_background, const float* d_ray_origins, uint32_t* d_numsteps_out,
+	              float* d_coords_out, OutputMatrix& dL_doutput, float* d_loss, uint32_t* d_counter_out) {
+		check(nrs_ray_loss(m_model, stream, &params, n_rays, d_ray_counter, d_numsteps, coords.n, coords.data, coords.rows, output.data, output.n, output.layout,
+		                   d_target_rgba, d_background, d_ray_origins, d_numsteps_out, d_coords_out, dL_doutput.data, dL_doutput.n, dL_doutput.layout, d_loss,
+		                   d_counter_out), "nrs_ray_loss");
+	}
 	// tcnn::Network::visualize_activation(stream, layer, dimension, input, output): the activation itself, f32 [n] (testbed_nerf.cu:2926, :3159)
 	void visualize_activation(void* stream, uint32_t layer, uint32_t dimension, const InputMatrix& input, float* d_out_n) {
 		if (input.rows != NRS_NETWORK_INPUT_FLOATS) throw std::runtime_error("NerfNetwork::visualize_activation: input must have 7 rows");

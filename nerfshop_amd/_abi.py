@@ -166,6 +166,27 @@ class CameraKeyframe(C.Structure):
     _fields_ = [("R", C.c_float * 4), ("T", C.c_float * 3), ("slice", C.c_float), ("scale", C.c_float), ("fov", C.c_float), ("dof", C.c_float)]
 
 
+LOSS_L2, LOSS_L1, LOSS_MAPE, LOSS_SMAPE, LOSS_HUBER, LOSS_LOG_L1, LOSS_RELATIVE_L2 = range(7)  # nrs_loss_type (ELossType's order)
+
+
+class RayLossParams(C.Structure):
+    """nrs_ray_loss_params; the defaults are Testbed's (L2, loss scale 128, Linear, train_in_linear_colors off)"""
+    _fields_ = [("struct_size", C.c_uint32), ("loss_type", C.c_uint32), ("loss_scale", C.c_float), ("color_space", C.c_uint32), ("train_in_linear_colors", C.c_uint32),
+                ("background", C.c_float * 3), ("near_distance", C.c_float), ("density_l1_reg", C.c_uint32), ("max_samples_compacted", C.c_uint32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.struct_size = C.sizeof(RayLossParams)
+        self.loss_type, self.loss_scale, self.color_space, self.train_in_linear_colors = LOSS_L2, 128.0, 0, 0
+        for k, v in kw.items():
+            if k == "background":
+                self.background = (C.c_float * 3)(*[float(x) for x in v])
+            elif k in dict(self._fields_):
+                setattr(self, k, v)
+            else:
+                raise TypeError(f"RayLossParams has no field {k}")
+
+
 # every symbol include/nrs.h declares; tests check the library exports exactly these
 EXPORTS = [
     "nrs_last_error", "nrs_abi_version", "nrs_edit_poisson_interpolate", "nrs_edit_download_poisson", "nrs_comm_unique_id", "nrs_comm_create", "nrs_comm_info", "nrs_comm_destroy", "nrs_gather_tiles", "nrs_comm_probe_self_p2p",
@@ -195,6 +216,7 @@ EXPORTS = [
     "nrs_selection_get_cells", "nrs_selection_get_bitfield", "nrs_selection_set_structuring_elements", "nrs_bitfield_morph", "nrs_bitfield_morph_host",
     "nrs_selection_dilate", "nrs_selection_erode", "nrs_selection_fine_mesh",
     "nrs_network_backward",
+    "nrs_training_samples", "nrs_ray_loss",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -282,6 +304,9 @@ def load():
     lib.nrs_network_visualize_activation.argtypes = [P, P, U32, U32, U32, P, P]
     if hasattr(lib, "nrs_network_backward"):  # (an A/B build of the parent tree through NRS_LIB_PATH has none: tools/network_backward_probe.py --parent-lib)
         lib.nrs_network_backward.argtypes = [P, P, U32, P, U32, P, U32, I, P, C.c_size_t, I, P]
+    if hasattr(lib, "nrs_ray_loss"):  # (detected by symbol, like nrs_network_backward)
+        lib.nrs_training_samples.argtypes = [P, P, U32, P, P, C.c_float, U32, P, U32, P, P, P]
+        lib.nrs_ray_loss.argtypes = [P, P, C.POINTER(RayLossParams), U32, P, P, U32, P, U32, P, U32, I, P, P, P, P, P, P, U32, I, P, P]
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

@@ -148,6 +148,8 @@ struct nrs_model {
 	size_t sparse_bytes = 0;        // tables + slots + records
 	uint32_t sparse_first = 0, sparse_levels = 0;
 	uint32_t slot_first[nrs::kLevels] = {}, slot_count[nrs::kLevels] = {};
+	// per-ray workspace of nrs_training_samples / nrs_ray_loss (nrs_api_train.cpp): grown on the first call of a size, reused afterwards
+	nrs::DeviceBuffer<uint32_t> d_train_ws;
 };
 
 struct nrs_edit {

@@ -1,0 +1,561 @@
+// nrs_train.hip -- the training-ray path (gfx950): rays -> network inputs, and network outputs -> ray loss + dL/doutput, compacted.
+//
+//   train_count_kernel     generate_training_samples_nerf's first walk (tn:1188-1213): samples per ray.
+//   train_tile_*_kernel    exclusive scan of the per-ray counts in input order: tile sums, mc_scan_kernel (nrs_mesh.hip) over them, the scan inside each tile.  It stands where the
+//                          reference has atomicAdd (tn:1218, :1225, :1834), so the layout does not depend on arrival order.
+//   train_write_kernel     the second walk (tn:1232-1246) into the slots the scan fixed; train_fill_kernel zeroes the records behind the last emitted ray.
+//   ray_loss_forward_kernel   compute_loss_kernel_train_nerf's first loop, the target and loss_and_gradient (tn:1745-1828, :1847): M, C, g, loss per ray.
+//   ray_loss_gradient_kernel  its third loop (tn:1895-1944) at the compact base the scan fixed; ray_loss_tail_kernel zeroes the compact tail.
+//
+// The generator has one thread per ray, as in the reference (it is bound by the latency of the bitfield walk).  The two loss kernels have one lane per SAMPLE: see
+// "one lane per sample" below.  No float atomics: every output is a function of the inputs alone.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include "nrs_internal.h"
+#include "nrs_launch.h"
+#include "nrs_device.cuh"
+#include "nrs_train.h"
+
+namespace nrs {
+
+constexpr uint32_t kTrainSteps = 1024;       // NERF_STEPS, common_nerf.h:20
+constexpr uint32_t kTrainMaxAdvances = 65536; // empty cells a ray may cross (a ray through the largest box crosses a few thousand): see train_march
+constexpr uint32_t kTrainBlock = 128;
+
+// ---- rays -> network inputs -------------------------------------------------------------------------------------------------------------------------------
+struct TrainRay { f3 o, d; float startt; bool ok; };
+// tn:1188-1195.  A ray the walk cannot end on (non-finite origin, direction of a length outside [0.5, 2]: advance_to_next_voxel steps t by at least MIN_STEP until it
+// passes a target that such a ray puts out of reach) has no samples.
+__device__ __forceinline__ TrainRay train_ray(const DeviceModel& m, const TrainSamplesArgs& a, uint32_t i) {
+	TrainRay r;
+	const float* p = a.rays + 6 * (size_t)i;
+	r.o = mk3(p[0], p[1], p[2]);
+	r.d = mk3(p[3], p[4], p[5]);
+	const float sq = dot3(r.d, r.d), os = fabsf(r.o.x) + fabsf(r.o.y) + fabsf(r.o.z);
+	r.ok = sq >= 0.25f && sq <= 4.0f && os < 3.0e38f; // false for every NaN
+	float tmin;
+	ray_intersect(m.aabb.mn, m.aabb.mx, r.o, r.d, tmin);
+	tmin = fmaxf(tmin, 0.0f);
+	r.startt = tmin + calc_dt(tmin, a.cone) * (a.jitter ? a.jitter[i] : 0.0f);
+	return r;
+}
+// The walk of tn:1203-1213 (WRITE false) and :1235-1246 (true): up to `limit` samples; o + d * t as the render kernel's marcher forms it.
+template <bool WRITE>
+__device__ __forceinline__ uint32_t train_march(const DeviceModel& m, const TrainRay& r, float cone, uint32_t limit, float* __restrict__ coords, uint32_t ld) {
+	const f3 idir = mk3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
+	const f3 wdir = warp_direction(r.d);
+	float t = r.startt;
+	uint32_t j = 0, advances = 0;
+	while (j < limit) {
+		const f3 pos = r.o + r.d * t;
+		if (!box_contains(m.aabb, pos)) break;
+		const float dt = calc_dt(t, cone);
+		const uint32_t mip = (uint32_t)mip_from_dt(dt, pos);
+		if (density_grid_occupied_at(pos, m.bitfield, mip)) {
+			if (WRITE) {
+				const f3 wpos = warp_position(pos, m.aabb);
+				float* c = coords + (size_t)j * ld;
+				c[0] = wpos.x; c[1] = wpos.y; c[2] = wpos.z;
+				c[3] = warp_dt(dt);
+				c[4] = wdir.x; c[5] = wdir.y; c[6] = wdir.z;
+			}
+			++j;
+			t += dt;
+		} else {
+			if (++advances > kTrainMaxAdvances) break; // (t no longer moves: an origin so far away that a step is below t's spacing)
+			t = advance_to_next_voxel(t, cone, pos, r.d, idir, kGrid >> mip, 1.0f / (float)(kGrid >> mip));
+		}
+	}
+	return j;
+}
+
+__global__ __launch_bounds__(kTrainBlock) void train_count_kernel(const DeviceModel m, const TrainSamplesArgs a) {
+	const uint32_t i = blockIdx.x * kTrainBlock + threadIdx.x;
+	if (i >= a.n_rays) return;
+	const TrainRay r = train_ray(m, a, i);
+	a.ws[i] = r.ok ? train_march<false>(m, r, a.cone, kTrainSteps, nullptr, 0) : 0u;
+}
+
+// The exclusive scan of the per-ray counts, in three launches as the mesh path does it: sums per tile of kScanTile rays (coalesced, any number of workgroups), the
+// one-workgroup scan of the tile sums (mc_scan_kernel itself: 2 x 4 bytes per 1024 rays), and the scan inside each tile on top of its offset.
+// Two sums per ray: its count and whether it has one.  count / base / slot: three arrays of n words; rays at or past *live (NULL: all n) count as empty.
+// GEN (the generator): slot = the rays with samples before this one -- its place among the emitted rays, because a ray with samples that is dropped puts every later
+// one past max_samples too (bases only grow) -- out[0] = emitted rays, out[1] = the sum of all counts, *end = where the last emitted ray ends.
+// Otherwise (the loss): out[0] = the sum of all counts.
+constexpr uint32_t kScanTile = 1024, kScanThreads = 256, kScanPer = kScanTile / kScanThreads;
+// tiles: [n_tiles][2] sums, then [2] totals
+__global__ __launch_bounds__(kScanThreads) void train_tile_sums_kernel(uint32_t n, const uint32_t* __restrict__ live, const uint32_t* __restrict__ count,
+                                                                        uint32_t* __restrict__ tiles, uint32_t* __restrict__ zero0, uint32_t* __restrict__ zero1) {
+	__shared__ uint32_t s_wave[kScanThreads / 64][2];
+	if (blockIdx.x == 0 && threadIdx.x == 0) { if (zero0) *zero0 = 0u; if (zero1) *zero1 = 0u; } // what train_tile_scan_kernel<true> takes maxima into
+	if (live) n = min(n, *live);
+	const uint32_t first = blockIdx.x * kScanTile + threadIdx.x * kScanPer;
+	uint32_t v = 0, t = 0;
+	#pragma unroll
+	for (uint32_t k = 0; k < kScanPer; ++k) if (first + k < n) { const uint32_t c = count[first + k]; v += c; t += c ? 1u : 0u; }
+	#pragma unroll
+	for (uint32_t d = 32; d; d >>= 1) { v += (uint32_t)__shfl_xor((int)v, (int)d); t += (uint32_t)__shfl_xor((int)t, (int)d); }
+	if ((threadIdx.x & 63u) == 0u) { s_wave[threadIdx.x >> 6][0] = v; s_wave[threadIdx.x >> 6][1] = t; }
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t vs = 0, ts = 0;
+		for (uint32_t w = 0; w < kScanThreads / 64; ++w) { vs += s_wave[w][0]; ts += s_wave[w][1]; }
+		tiles[2 * blockIdx.x] = vs;
+		tiles[2 * blockIdx.x + 1] = ts;
+	}
+}
+template <bool GEN>
+__global__ __launch_bounds__(kScanThreads) void train_tile_scan_kernel(uint32_t n, const uint32_t* __restrict__ live, const uint32_t* __restrict__ count,
+                                                                        const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ totals,
+                                                                        uint32_t* __restrict__ base, uint32_t* __restrict__ slot, uint32_t max_samples,
+                                                                        uint32_t* __restrict__ out, uint32_t* __restrict__ end) {
+	__shared__ uint32_t s_wave[kScanThreads / 64][2];
+	__shared__ uint32_t s_emitted, s_end;
+	if (threadIdx.x == 0) { s_emitted = 0; s_end = 0; }
+	if (live) n = min(n, *live);
+	const uint32_t first = blockIdx.x * kScanTile + threadIdx.x * kScanPer;
+	uint32_t c[kScanPer], v = 0, t = 0;
+	#pragma unroll
+	for (uint32_t k = 0; k < kScanPer; ++k) { c[k] = first + k < n ? count[first + k] : 0u; v += c[k]; t += c[k] ? 1u : 0u; }
+	uint32_t vi = v, ti = t; // inclusive scan inside the wave
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	#pragma unroll
+	for (uint32_t d = 1; d < 64; d <<= 1) {
+		const uint32_t vu = (uint32_t)__shfl_up((int)vi, d), tu = (uint32_t)__shfl_up((int)ti, d);
+		if (lane >= d) { vi += vu; ti += tu; }
+	}
+	if (lane == 63u) { s_wave[wave][0] = vi; s_wave[wave][1] = ti; }
+	__syncthreads();
+	uint32_t v_run = tiles[2 * blockIdx.x] + vi - v, t_run = tiles[2 * blockIdx.x + 1] + ti - t; // (tiles: exclusive after the one-workgroup scan)
+	for (uint32_t w = 0; w < kScanThreads / 64; ++w) if (w < wave) { v_run += s_wave[w][0]; t_run += s_wave[w][1]; }
+	uint32_t emitted_to = 0, my_end = 0;
+	#pragma unroll
+	for (uint32_t k = 0; k < kScanPer; ++k) {
+		if (first + k < n) {
+			base[first + k] = v_run;
+			if (GEN) {
+				slot[first + k] = t_run;
+				if (c[k] && v_run <= max_samples && c[k] <= max_samples - v_run) { emitted_to = t_run + 1u; my_end = v_run + c[k]; }
+			}
+		}
+		v_run += c[k];
+		t_run += c[k] ? 1u : 0u;
+	}
+	if (GEN) { // the emitted rays are the first of the rays with samples: their number is the last one's slot + 1.  Integer maxima: the result does not depend on the order
+		if (emitted_to) { atomicMax(&s_emitted, emitted_to); atomicMax(&s_end, my_end); }
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			if (s_emitted) { atomicMax(&out[0], s_emitted); atomicMax(end, s_end); }
+			if (blockIdx.x == 0) out[1] = totals[0];
+		}
+	} else if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = totals[0];
+}
+// tiles: 2 * train_scan_tiles(n) + 2 words of workspace
+template <bool GEN>
+static int launch_train_scan(uint32_t n, const uint32_t* live, const uint32_t* count, uint32_t* tiles, uint32_t* base, uint32_t* slot, uint32_t max_samples, uint32_t* out,
+                             uint32_t* end, hipStream_t st) {
+	const uint32_t n_tiles = train_scan_tiles(n);
+	uint32_t* totals = tiles + 2 * (size_t)n_tiles;
+	hipLaunchKernelGGL(train_tile_sums_kernel, dim3(n_tiles), dim3(kScanThreads), 0, st, n, live, count, tiles, GEN ? out : nullptr, GEN ? end : nullptr);
+	NRS_LAUNCH_CHECK("train_tile_sums_kernel launch");
+	const int status = launch_mc_scan(n_tiles, tiles, totals, st);
+	if (status != NRS_OK) return status;
+	hipLaunchKernelGGL(train_tile_scan_kernel<GEN>, dim3(n_tiles), dim3(kScanThreads), 0, st, n, live, count, (const uint32_t*)tiles, (const uint32_t*)totals, base, slot, max_samples,
+	                   out, end);
+	NRS_LAUNCH_CHECK("train_tile_scan_kernel launch");
+	return NRS_OK;
+}
+
+__global__ __launch_bounds__(kTrainBlock) void train_write_kernel(const DeviceModel m, const TrainSamplesArgs a) {
+	const uint32_t i = blockIdx.x * kTrainBlock + threadIdx.x;
+	if (i >= a.n_rays) return;
+	const uint32_t j = a.ws[i], base = a.ws[a.n_rays + i];
+	if (j == 0u || base > a.max_samples || j > a.max_samples - base) return; // tn:1214-1221
+	const uint32_t s = a.ws[2 * a.n_rays + i];
+	a.ray_indices[s] = i;
+	a.numsteps[2 * s] = j;
+	a.numsteps[2 * s + 1] = base;
+	const TrainRay r = train_ray(m, a, i);
+	train_march<true>(m, r, a.cone, j, a.coords + (size_t)base * a.ld, a.ld);
+}
+// records [*end, max_samples): floats 0..6 zero (end NULL: from 0)
+__global__ __launch_bounds__(256) void train_fill_kernel(uint32_t max_samples, const uint32_t* __restrict__ end, float* __restrict__ coords, uint32_t ld) {
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	if (k >= max_samples || (end && k < *end)) return;
+	float* c = coords + (size_t)k * ld;
+	#pragma unroll
+	for (int q = 0; q < 7; ++q) c[q] = 0.f;
+}
+
+int launch_training_samples(const DeviceModel& m, const TrainSamplesArgs& a, void* stream) {
+	hipStream_t st = (hipStream_t)stream;
+	uint32_t* end = nullptr;
+	if (a.n_rays) {
+		const uint32_t blocks = (a.n_rays + kTrainBlock - 1) / kTrainBlock;
+		end = a.ws + (size_t)kTrainSamplesWsWords * a.n_rays;
+		hipLaunchKernelGGL(train_count_kernel, dim3(blocks), dim3(kTrainBlock), 0, st, m, a);
+		NRS_LAUNCH_CHECK("train_count_kernel launch");
+		const int status = launch_train_scan<true>(a.n_rays, nullptr, a.ws, end + 1, a.ws + a.n_rays, a.ws + 2 * (size_t)a.n_rays, a.max_samples, a.counters, end, st);
+		if (status != NRS_OK) return status;
+		hipLaunchKernelGGL(train_write_kernel, dim3(blocks), dim3(kTrainBlock), 0, st, m, a);
+		NRS_LAUNCH_CHECK("train_write_kernel launch");
+	} else {
+		const hipError_t e = hipMemsetAsync(a.counters, 0, 2 * sizeof(uint32_t), st);
+		if (e != hipSuccess) return hip_fail(e, "nrs_training_samples: zeroing the counters");
+	}
+	hipLaunchKernelGGL(train_fill_kernel, dim3((a.max_samples + 255) / 256), dim3(256), 0, st, a.max_samples, (const uint32_t*)end, a.coords, a.ld);
+	NRS_LAUNCH_CHECK("train_fill_kernel launch");
+	return NRS_OK;
+}
+
+// ---- network outputs -> loss and dL/doutput ------------------------------------------------------------------------------------------------------------------
+constexpr float kLossEps = 1e-4f; // EPSILON, tn:1747
+
+__device__ __forceinline__ float network_to_rgb_derivative(float v, uint32_t act) { // tn:297-306
+	switch (act) {
+		case NRS_ACT_RELU: return v > 0.0f ? 1.0f : 0.0f;
+		case NRS_ACT_LOGISTIC: { const float density = 1.0f / (1.0f + __expf(-v)); return density * (1 - density); }
+		case NRS_ACT_EXPONENTIAL: return __expf(clampf_(v, -10.0f, 10.0f));
+		default: return 1.0f;
+	}
+}
+// common_device.cuh:31-37, :55-61, with powf: once per ray, and the loss is compared more tightly than a displayed colour
+__device__ __forceinline__ float train_srgb_to_linear(float s) { return s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f); }
+__device__ __forceinline__ float train_linear_to_srgb(float l) { return l < 0.0031308f ? 12.92f * l : 1.055f * powf(l, 0.41666f) - 0.055f; }
+
+// loss_and_gradient (tn:173-185) of one channel: the seven functions of tn:103-171, Huber with alpha = 1
+__device__ __forceinline__ void loss_and_gradient(uint32_t type, float target, float pred, float& loss, float& grad) {
+	const float diff = pred - target;
+	switch (type) {
+		case NRS_LOSS_RELATIVE_L2: { const float f = 1.0f / (pred * pred + 1e-2f); loss = diff * diff * f; grad = 2.0f * diff * f; break; }
+		case NRS_LOSS_L1: loss = fabsf(diff); grad = copysignf(1.0f, diff); break;
+		case NRS_LOSS_MAPE: { const float f = 1.0f / (fabsf(pred) + 1e-2f); loss = fabsf(diff) * f; grad = copysignf(f, diff); break; }
+		case NRS_LOSS_SMAPE: { const float f = 1.0f / (0.5f * (fabsf(pred) + fabsf(target)) + 1e-2f); loss = fabsf(diff) * f; grad = copysignf(f, diff); break; }
+		case NRS_LOSS_HUBER: {
+			const float ad = fabsf(diff);
+			loss = ad > 1.0f ? ad - 0.5f : 0.5f * diff * diff;
+			grad = ad > 1.0f ? (diff > 0 ? 1.0f : -1.0f) : diff;
+			break;
+		}
+		case NRS_LOSS_LOG_L1: { const float div = fabsf(diff) + 1.0f; loss = logf(div); grad = copysignf(1.0f / div, diff); break; }
+		default: loss = diff * diff; grad = 2.0f * diff; break; // L2
+	}
+}
+
+// the four raw outputs of sample s
+struct RawOut { float v[4]; };
+__device__ __forceinline__ RawOut load_raw(const __half* __restrict__ out, uint32_t ld, int layout, size_t s) {
+	RawOut r;
+	if (layout == NRS_PLANES) {
+		#pragma unroll
+		for (int c = 0; c < 4; ++c) r.v[c] = __half2float(out[(size_t)c * ld + s]);
+	} else {
+		const uint2 w = *reinterpret_cast<const uint2*>(out + 16 * s); // 32-byte records: aligned
+		const __half2 a = __builtin_bit_cast(__half2, w.x), b = __builtin_bit_cast(__half2, w.y);
+		r.v[0] = __low2float(a); r.v[1] = __high2float(a); r.v[2] = __low2float(b); r.v[3] = __high2float(b);
+	}
+	return r;
+}
+__device__ __forceinline__ void store_dl(__half* __restrict__ dl, uint32_t ld, int layout, size_t s, const float v[4]) {
+	if (layout == NRS_PLANES) {
+		#pragma unroll
+		for (int c = 0; c < 4; ++c) dl[(size_t)c * ld + s] = __float2half(v[c]);
+	} else {
+		const __half2 a = __halves2half2(__float2half(v[0]), __float2half(v[1])), b = __halves2half2(__float2half(v[2]), __float2half(v[3]));
+		*reinterpret_cast<uint2*>(dl + 16 * s) = make_uint2(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b));
+	}
+}
+
+// what one sample adds to the composite (tn:1758-1770 / :1906-1913)
+struct Sample { RawOut raw; f3 rgb; float dt, alpha, rest; }; // rest = 1 - alpha
+__device__ __forceinline__ Sample load_sample(const DeviceModel& m, const RayLossArgs& a, size_t s) {
+	Sample q;
+	q.raw = load_raw(reinterpret_cast<const __half*>(a.output), a.ld_out, a.out_layout, s);
+	q.rgb = mk3(network_to_rgb(q.raw.v[0], m.rgb_activation), network_to_rgb(q.raw.v[1], m.rgb_activation), network_to_rgb(q.raw.v[2], m.rgb_activation));
+	q.dt = unwarp_dt(a.coords[s * a.ld_in + 3]);
+	const float density = network_to_density(q.raw.v[3], m.density_activation);
+	// 1 - alpha is exp(-density dt) itself: the reference's 1.f - alpha = 1 - (1 - e) loses e's low bits (all of them below 6e-8), which its T then carries
+	q.rest = __expf(-density * q.dt);
+	q.alpha = 1.f - q.rest;
+	return q;
+}
+__device__ __forceinline__ uint32_t live_rays(const RayLossArgs& a) { return a.ray_counter ? min(*a.ray_counter, a.n_rays) : a.n_rays; }
+
+// The ray's target, the background behind a ray that was not stopped, loss_and_gradient, and the ray's row of the workspace (tn:1789-1828, :1847-1858)
+__device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uint32_t M, uint32_t n, f3 C, float T) {
+	uint32_t* ws_m = a.ws;
+	float* ws_f = reinterpret_cast<float*>(a.ws) + 2 * (size_t)a.n_rays; // C[3] | g[3] | loss, n_rays apart
+	// tn:1789-1828
+	const nrs_ray_loss_params& p = a.p;
+	const float* bgp = a.background ? a.background + 3 * (size_t)i : p.background;
+	f3 bg = mk3(train_srgb_to_linear(bgp[0]), train_srgb_to_linear(bgp[1]), train_srgb_to_linear(bgp[2]));
+	const float* texp = a.target_rgba + 4 * (size_t)i;
+	const float4 tex = make_float4(texp[0], texp[1], texp[2], texp[3]);
+	f3 target;
+	if (p.train_in_linear_colors || p.color_space == NRS_COLOR_LINEAR) {
+		target = mk3(tex.x, tex.y, tex.z) + (1.0f - tex.w) * bg;
+		if (!p.train_in_linear_colors) {
+			target = mk3(train_linear_to_srgb(target.x), train_linear_to_srgb(target.y), train_linear_to_srgb(target.z));
+			bg = mk3(train_linear_to_srgb(bg.x), train_linear_to_srgb(bg.y), train_linear_to_srgb(bg.z));
+		}
+	} else {
+		bg = mk3(train_linear_to_srgb(bg.x), train_linear_to_srgb(bg.y), train_linear_to_srgb(bg.z));
+		if (tex.w > 0) {
+			target = mk3(train_linear_to_srgb(tex.x / tex.w), train_linear_to_srgb(tex.y / tex.w), train_linear_to_srgb(tex.z / tex.w)) * tex.w + (1.0f - tex.w) * bg;
+		} else target = bg;
+	}
+	if (M == n) C = C + T * bg;
+	float lx, ly, lz, gx, gy, gz;
+	loss_and_gradient(p.loss_type, target.x, C.x, lx, gx);
+	loss_and_gradient(p.loss_type, target.y, C.y, ly, gy);
+	loss_and_gradient(p.loss_type, target.z, C.z, lz, gz);
+	const size_t R = a.n_rays;
+	ws_m[i] = M;
+	ws_f[i] = C.x; ws_f[R + i] = C.y; ws_f[2 * R + i] = C.z;
+	ws_f[3 * R + i] = gx; ws_f[4 * R + i] = gy; ws_f[5 * R + i] = gz;
+	ws_f[6 * R + i] = sum3(lx, ly, lz) / 3.0f / (float)a.n_rays;
+}
+
+// ---- one lane per sample -------------------------------------------------------------------------------------------------------------------------------------
+// A wave owns 64 consecutive rays (lane k holds ray k's count and base) and walks them in packets: consecutive rays whose counts fit into 64 lanes, one lane per
+// sample, so that the loads of outputs and records are contiguous over the wave; a ray of more than 64 samples goes alone, in chunks of 64, and carries (T, C) from
+// chunk to chunk in wave-uniform registers.  T in front of a sample is a segmented exclusive product scan of 1 - alpha; C three segmented sums.  The early stop is a
+// predicate per lane (T in front of it < EPS), balloted: the first set bit of a segment is the ray's M, and every lane at or behind it contributes exactly nothing.
+constexpr uint32_t kWaveBlock = 256;
+__device__ __forceinline__ uint32_t shfl_u(uint32_t v, uint32_t lane) { return (uint32_t)__shfl((int)v, (int)lane); }
+// inclusive scans over the lanes st..lane of a segment (lane >= st)
+__device__ __forceinline__ float seg_scan_mul(float x, uint32_t lane, uint32_t st) {
+	#pragma unroll
+	for (uint32_t d = 1; d < 64; d <<= 1) { const float v = __shfl_up(x, d); if (lane >= st + d) x *= v; }
+	return x;
+}
+__device__ __forceinline__ float seg_scan_add(float x, uint32_t lane, uint32_t st) {
+	#pragma unroll
+	for (uint32_t d = 1; d < 64; d <<= 1) { const float v = __shfl_up(x, d); if (lane >= st + d) x += v; }
+	return x;
+}
+__device__ __forceinline__ unsigned long long lane_range(uint32_t first, uint32_t last) { // bits first..last
+	return ((2ull << last) - 1ull) & ~((1ull << first) - 1ull);
+}
+// A packet of the wave's walk: rays c..e (long: ray c alone), `tot` samples
+struct Packet { uint32_t e, tot; bool lng; };
+__device__ __forceinline__ Packet next_packet(uint32_t c, uint32_t lane, uint32_t n, uint32_t P, uint32_t E) {
+	Packet k;
+	const uint32_t Nc = shfl_u(n, c), Ec = shfl_u(E, c);
+	k.lng = Nc > 64u;
+	k.e = c;
+	k.tot = Nc;
+	if (!k.lng) {
+		const unsigned long long fit = __ballot(lane >= c && P - Ec <= 64u); // P grows with the lane: a run that starts at c
+		k.e = c + (uint32_t)__popcll(fit) - 1u;
+		k.tot = shfl_u(P, k.e) - Ec;
+	}
+	return k;
+}
+// the ray of the packet that sample lane `lane` belongs to: the first k in c..e with P_k - Ec > lane (every lane takes the same six steps)
+__device__ __forceinline__ uint32_t packet_ray(uint32_t c, uint32_t e, uint32_t lane, uint32_t P, uint32_t Ec) {
+	uint32_t lo = c, hi = e;
+	#pragma unroll
+	for (int k = 0; k < 6; ++k) {
+		const uint32_t mid = min((lo + hi) >> 1, e);
+		const uint32_t pm = shfl_u(P, mid) - Ec;
+		if (pm > lane) hi = mid; else lo = mid + 1u;
+	}
+	return min(lo, e);
+}
+__device__ __forceinline__ uint32_t wave_prefix(uint32_t n, uint32_t lane) { // inclusive
+	#pragma unroll
+	for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)n, d); if (lane >= d) n += v; }
+	return n;
+}
+
+__global__ __launch_bounds__(kWaveBlock) void ray_loss_forward_kernel(const DeviceModel m, const RayLossArgs a) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t i = blockIdx.x * kWaveBlock + threadIdx.x;
+	const uint32_t live = live_rays(a);
+	uint32_t n = 0, base = 0;
+	if (i < live) {
+		n = a.numsteps[2 * i];
+		base = a.numsteps[2 * i + 1];
+		if (base > a.n_samples || n > a.n_samples - base || n > kTrainSteps) n = 0u; // not inside the buffers, or longer than a ray can be: no samples
+	}
+	const uint32_t P = wave_prefix(n, lane), E = P - n;
+	f3 C = mk3(0, 0, 0);
+	float T = 1.f;
+	uint32_t M = 0;
+	for (uint32_t c = 0; c < 64u;) {
+		const Packet k = next_packet(c, lane, n, P, E);
+		const uint32_t Ec = shfl_u(E, c);
+		const uint32_t chunks = (k.tot + 63u) / 64u;
+		float Tin = 1.f;
+		f3 Cin = mk3(0, 0, 0);
+		uint32_t Mlong = k.tot;
+		for (uint32_t ch = 0; ch < chunks; ++ch) {
+			uint32_t r = c, st = 0, j = ch * 64u + lane;
+			if (!k.lng) {
+				r = packet_ray(c, k.e, lane, P, Ec);
+				st = shfl_u(E, r) - Ec;
+				j = lane - st;
+			}
+			const bool valid = k.lng ? j < k.tot : lane < k.tot;
+			const uint32_t sbase = shfl_u(base, r);
+			float alpha = 0.f, rest = 1.f;
+			f3 rgb = mk3(0, 0, 0);
+			if (valid) { const Sample q = load_sample(m, a, (size_t)sbase + j); alpha = q.alpha; rest = q.rest; rgb = q.rgb; }
+			const float x = seg_scan_mul(rest, lane, st);
+			float Tb = __shfl_up(x, 1);
+			Tb = (lane == st ? 1.f : Tb) * Tin;
+			const unsigned long long bad = __ballot(valid && Tb < kLossEps);
+			const bool active = valid && !(bad & lane_range(st, lane));
+			const float w = active ? alpha * Tb : 0.f;
+			const float y0 = seg_scan_add(w * rgb.x, lane, st), y1 = seg_scan_add(w * rgb.y, lane, st), y2 = seg_scan_add(w * rgb.z, lane, st);
+			// A ray's sums are read at the lane of its last consumed sample, not at the end of its segment: the scan's value there is formed from the same lanes in the
+			// same order as the gradient pass forms C2 at that sample, so C - C2 is exactly what lies behind the sample (0 behind the last one of a stopped ray).
+			if (k.lng) {
+				if (bad) {
+					const uint32_t fb = (uint32_t)__builtin_ctzll(bad);
+					Mlong = ch * 64u + fb;
+					if (fb) Cin = Cin + mk3(__shfl(y0, (int)fb - 1), __shfl(y1, (int)fb - 1), __shfl(y2, (int)fb - 1));
+					break;
+				}
+				const int lv = (int)min(63u, k.tot - 1u - ch * 64u);
+				Cin = Cin + mk3(__shfl(y0, lv), __shfl(y1, lv), __shfl(y2, lv));
+				Tin *= __shfl(x, lv);
+			} else {
+				const bool mine = lane >= c && lane <= k.e && n > 0u;
+				const uint32_t first = mine ? E - Ec : 0u, last = mine ? first + n - 1u : 0u;
+				const unsigned long long stop = bad & lane_range(first, last);
+				const uint32_t Mr = stop ? (uint32_t)__builtin_ctzll(stop) - first : n; // >= 1 for a ray with samples: T in front of its first sample is 1
+				const int src = mine ? (int)(first + Mr - 1u) : 0;
+				const float p0 = __shfl(y0, src), p1 = __shfl(y1, src), p2 = __shfl(y2, src), px = __shfl(x, (int)last);
+				if (mine) {
+					M = Mr;
+					C = mk3(p0, p1, p2);
+					T = px;
+				}
+			}
+		}
+		if (k.lng && lane == c) { C = Cin; T = Tin; M = Mlong; }
+		c = k.e + 1u;
+	}
+	if (i >= a.n_rays) return;
+	if (i >= live) {
+		a.ws[i] = 0u;
+		if (a.loss) a.loss[i] = 0.f;
+		return;
+	}
+	finish_ray(a, i, M, n, C, T);
+}
+
+__global__ __launch_bounds__(kWaveBlock) void ray_loss_gradient_kernel(const DeviceModel m, const RayLossArgs a) {
+	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t i = blockIdx.x * kWaveBlock + threadIdx.x;
+	const size_t R = a.n_rays;
+	const float* ws_f = reinterpret_cast<const float*>(a.ws) + 2 * R;
+	const nrs_ray_loss_params& p = a.p;
+	uint32_t n = 0, base = 0, cbase = 0; // n: the samples to replay, M' (tn:1835)
+	f3 C = mk3(0, 0, 0), g = mk3(0, 0, 0);
+	if (i < live_rays(a)) {
+		const uint32_t M = a.ws[i], cap = p.max_samples_compacted;
+		cbase = a.ws[R + i];
+		n = min(cap - min(cap, cbase), M);
+		a.numsteps_out[2 * i] = n;
+		a.numsteps_out[2 * i + 1] = cbase;
+		if (a.loss) a.loss[i] = n ? ws_f[6 * R + i] : 0.f;
+		if (n) {
+			base = a.numsteps[2 * i + 1];
+			C = mk3(ws_f[i], ws_f[R + i], ws_f[2 * R + i]);
+			g = mk3(ws_f[3 * R + i], ws_f[4 * R + i], ws_f[5 * R + i]);
+		}
+	}
+	const uint32_t P = wave_prefix(n, lane), E = P - n;
+	const float s = p.loss_scale / (float)a.n_rays;
+	const float l2reg = m.rgb_activation == NRS_ACT_EXPONENTIAL ? 1e-4f : 0.0f, l1reg = p.density_l1_reg ? 1e-4f : 0.0f;
+	const bool use_near = p.near_distance > 0.f;
+	for (uint32_t c = 0; c < 64u;) {
+		const Packet k = next_packet(c, lane, n, P, E);
+		const uint32_t Ec = shfl_u(E, c);
+		const uint32_t chunks = (k.tot + 63u) / 64u;
+		float Tin = 1.f;
+		f3 Cin = mk3(0, 0, 0);
+		for (uint32_t ch = 0; ch < chunks; ++ch) {
+			uint32_t r = c, st = 0, j = ch * 64u + lane;
+			if (!k.lng) {
+				r = packet_ray(c, k.e, lane, P, Ec);
+				st = shfl_u(E, r) - Ec;
+				j = lane - st;
+			}
+			const bool valid = k.lng ? j < k.tot : lane < k.tot;
+			const uint32_t sbase = shfl_u(base, r), scbase = shfl_u(cbase, r);
+			const f3 Cr = mk3(__shfl(C.x, (int)r), __shfl(C.y, (int)r), __shfl(C.z, (int)r)), gr = mk3(__shfl(g.x, (int)r), __shfl(g.y, (int)r), __shfl(g.z, (int)r));
+			Sample q;
+			q.alpha = 0.f; q.rest = 1.f; q.dt = 0.f; q.rgb = mk3(0, 0, 0); q.raw.v[0] = q.raw.v[1] = q.raw.v[2] = q.raw.v[3] = 0.f;
+			const size_t si = (size_t)sbase + j, so = (size_t)scbase + j;
+			const float* cin = a.coords + si * a.ld_in;
+			if (valid) {
+				q = load_sample(m, a, si);
+				float* cout = a.coords_out + so * a.ld_in;
+				for (uint32_t f = 0; f < a.ld_in; ++f) cout[f] = cin[f];
+			}
+			const float x = seg_scan_mul(q.rest, lane, st);
+			float Tb = __shfl_up(x, 1);
+			Tb = (lane == st ? 1.f : Tb) * Tin;
+			const float T = x * Tin; // after the sample
+			const float w = q.alpha * Tb;
+			const f3 C2 = Cin + mk3(seg_scan_add(w * q.rgb.x, lane, st), seg_scan_add(w * q.rgb.y, lane, st), seg_scan_add(w * q.rgb.z, lane, st));
+			if (valid) {
+				const f3 suffix = Cr - C2;
+				const f3 dr = w * gr;
+				float dl[4];
+				dl[0] = s * (dr.x * network_to_rgb_derivative(q.raw.v[0], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[0]));
+				dl[1] = s * (dr.y * network_to_rgb_derivative(q.raw.v[1], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[1]));
+				dl[2] = s * (dr.z * network_to_rgb_derivative(q.raw.v[2], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[2]));
+				const float by_mlp = network_to_density_derivative(q.raw.v[3], m.density_activation) * (q.dt * dot3(gr, T * q.rgb - suffix));
+				float near_term = 0.0f;
+				if (use_near && q.raw.v[3] > -10.0f) {
+					const size_t ray = (size_t)(i - lane) + r;
+					const f3 dv = unwarp_position(mk3(cin[0], cin[1], cin[2]), m.aabb) - mk3(a.origins[3 * ray], a.origins[3 * ray + 1], a.origins[3 * ray + 2]);
+					if (sqrtf(dot3(dv, dv)) < p.near_distance) near_term = 1e-4f;
+				}
+				dl[3] = s * by_mlp + (q.raw.v[3] < 0.0f ? -l1reg : 0.0f) + near_term;
+				store_dl(reinterpret_cast<__half*>(a.dl), a.ld_dl, a.dl_layout, so, dl);
+			}
+			if (k.lng) { // what the next chunk starts from
+				Cin = mk3(__shfl(C2.x, 63), __shfl(C2.y, 63), __shfl(C2.z, 63));
+				Tin = __shfl(T, 63);
+			}
+		}
+		c = k.e + 1u;
+	}
+}
+
+// compact indices [min(*total, cap), cap): a zero record and dL rows 0..3 zero
+__global__ __launch_bounds__(256) void ray_loss_tail_kernel(const RayLossArgs a) {
+	const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+	if (k >= a.p.max_samples_compacted || k < *a.counter_out) return;
+	float* c = a.coords_out + (size_t)k * a.ld_in;
+	for (uint32_t q = 0; q < a.ld_in; ++q) c[q] = 0.f;
+	const float z[4] = {0.f, 0.f, 0.f, 0.f};
+	store_dl(reinterpret_cast<__half*>(a.dl), a.ld_dl, a.dl_layout, k, z);
+}
+
+int launch_ray_loss(const DeviceModel& m, const RayLossArgs& a, void* stream) {
+	hipStream_t st = (hipStream_t)stream;
+	if (a.n_rays) {
+		const uint32_t blocks = (a.n_rays + kWaveBlock - 1) / kWaveBlock;
+		hipLaunchKernelGGL(ray_loss_forward_kernel, dim3(blocks), dim3(kWaveBlock), 0, st, m, a);
+		NRS_LAUNCH_CHECK("ray_loss_forward_kernel launch");
+		const int status = launch_train_scan<false>(a.n_rays, a.ray_counter, a.ws, a.ws + (size_t)kRayLossWsWords * a.n_rays, a.ws + a.n_rays, nullptr, 0u, a.counter_out, nullptr, st);
+		if (status != NRS_OK) return status;
+		hipLaunchKernelGGL(ray_loss_gradient_kernel, dim3(blocks), dim3(kWaveBlock), 0, st, m, a);
+		NRS_LAUNCH_CHECK("ray_loss_gradient_kernel launch");
+	} else {
+		const hipError_t e = hipMemsetAsync(a.counter_out, 0, sizeof(uint32_t), st);
+		if (e != hipSuccess) return hip_fail(e, "nrs_ray_loss: zeroing the counter");
+	}
+	hipLaunchKernelGGL(ray_loss_tail_kernel, dim3((a.p.max_samples_compacted + 255) / 256), dim3(256), 0, st, a);
+	NRS_LAUNCH_CHECK("ray_loss_tail_kernel launch");
+	return NRS_OK;
+}
+
+} // namespace nrs

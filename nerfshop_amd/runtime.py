@@ -255,6 +255,82 @@ class NerfNetwork:
         check(self.lib.nrs_network_backward(self.h, _stream_handle(stream), n, input.data_ptr(), input.shape[1], dL_doutput.data_ptr(), ld, layout,
                                             dL_dparams.data_ptr(), dL_dparams.numel(), 1 if accumulate else 0, din))
 
+    def ray_loss(self, stream, params, numsteps, coords, output, target_rgba, background=None, ray_origins=None, ray_counter=None, n_rays=None,
+                 out=None, dl_planes=False):
+        """compute_loss_kernel_train_nerf (nrs_ray_loss): composite the samples of every ray, take the loss against target_rgba and write its gradient, compacted.
+        params: RayLossParams (max_samples_compacted set).  numsteps [n_rays, 2] u32-as-int32 (count, base); coords [n_samples, >= 7] f32; output fp16 as
+        inference wrote it ([16, n_el] or [n_samples, 16]); target_rgba [n_rays, 4] f32; background [n_rays, 3] / ray_origins [n_rays, 3] f32 or None; ray_counter: a
+        one-element int32 CUDA tensor (live rays) or None; n_rays: the normaliser, default numsteps.shape[0].
+        Returns (numsteps_out [n_rays, 2] int32, coords_out [max, ld] f32, dL_doutput fp16 [max, 16] or -- dl_planes -- [16, max], loss [n_rays] f32, counter [1] int32);
+        `out` may bring these five tensors to reuse.  Rows 4..15 of dL_doutput are not written (a fresh one is zero)."""
+        if not isinstance(params, _abi.RayLossParams):
+            raise NrsError("ray_loss: params must be a RayLossParams")
+        _require_cuda(numsteps, torch.int32, "numsteps")
+        _require_cuda(coords, torch.float32, "coords")
+        _require_cuda(output, torch.float16, "output")
+        _require_cuda(target_rgba, torch.float32, "target_rgba")
+        if numsteps.dim() != 2 or numsteps.shape[1] != 2:
+            raise NrsError("ray_loss: numsteps must be [n_rays, 2]")
+        n = int(numsteps.shape[0]) if n_rays is None else int(n_rays)
+        if n > numsteps.shape[0] or tuple(target_rgba.shape) != (numsteps.shape[0], 4):
+            raise NrsError("ray_loss: target_rgba must be [n_rays, 4] and n_rays no more than numsteps has rows")
+        if coords.dim() != 2 or coords.shape[1] < 7:
+            raise NrsError("ray_loss: coords must be a contiguous [n_samples, >= 7] tensor")
+        n_samples, ld_in = int(coords.shape[0]), int(coords.shape[1])
+        layout, ld_out = self._out_layout(output, n_samples)
+        for t, name in ((background, "background"), (ray_origins, "ray_origins")):
+            if t is not None:
+                _require_cuda(t, torch.float32, name)
+                if tuple(t.shape) != (numsteps.shape[0], 3):
+                    raise NrsError(f"ray_loss: {name} must be [n_rays, 3]")
+        if ray_counter is not None:
+            _require_cuda(ray_counter, torch.int32, "ray_counter")
+        cap = int(params.max_samples_compacted)
+        if cap <= 0:
+            raise NrsError("ray_loss: params.max_samples_compacted must be positive")
+        dev = coords.device
+        if out is None:
+            out = (torch.empty_like(numsteps), torch.empty(cap, ld_in, dtype=torch.float32, device=dev),
+                   torch.zeros((16, cap) if dl_planes else (cap, 16), dtype=torch.float16, device=dev),
+                   torch.empty(numsteps.shape[0], dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+        numsteps_out, coords_out, dl, loss, counter = out
+        _require_cuda(numsteps_out, torch.int32, "numsteps_out")
+        _require_cuda(coords_out, torch.float32, "coords_out")
+        _require_cuda(dl, torch.float16, "dL_doutput")
+        _require_cuda(loss, torch.float32, "loss")
+        _require_cuda(counter, torch.int32, "counter")
+        if tuple(numsteps_out.shape) != tuple(numsteps.shape) or tuple(coords_out.shape) != (cap, ld_in) or loss.numel() < numsteps.shape[0] or counter.numel() < 1:
+            raise NrsError("ray_loss: an output tensor has the wrong shape")
+        dl_layout, ld_dl = self._out_layout(dl, cap)
+        check(self.lib.nrs_ray_loss(self.h, _stream_handle(stream), C.byref(params), n, None if ray_counter is None else ray_counter.data_ptr(), numsteps.data_ptr(),
+                                    n_samples, coords.data_ptr(), ld_in, output.data_ptr(), ld_out, layout, target_rgba.data_ptr(),
+                                    None if background is None else background.data_ptr(), None if ray_origins is None else ray_origins.data_ptr(),
+                                    numsteps_out.data_ptr(), coords_out.data_ptr(), dl.data_ptr(), ld_dl, dl_layout, loss.data_ptr(), counter.data_ptr()))
+        return numsteps_out, coords_out, dl, loss, counter
+
+    def training_samples(self, stream, rays, jitter, cone_angle_constant, max_samples, ld=7):
+        """generate_training_samples_nerf from the ray on (nrs_training_samples): rays [n, 6] f32 (origin, unit direction), jitter [n] f32 in [0, 1) or None.
+        Returns (coords [max_samples, ld] f32, numsteps [n, 2] int32 (count, base) per emitted ray, ray_indices [n] int32, counters [2] int32 = rays emitted,
+        sum of all counts).  Rows of numsteps / ray_indices at or past counters[0] are zero (never written)."""
+        _require_cuda(rays, torch.float32, "rays")
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise NrsError("training_samples: rays must be [n, 6]")
+        n = int(rays.shape[0])
+        if jitter is not None:
+            _require_cuda(jitter, torch.float32, "jitter")
+            if jitter.numel() != n:
+                raise NrsError("training_samples: jitter must be [n]")
+        if int(max_samples) <= 0 or int(ld) < 7:
+            raise NrsError("training_samples: max_samples must be positive and ld >= 7")
+        dev = rays.device
+        coords = torch.zeros(int(max_samples), int(ld), dtype=torch.float32, device=dev)
+        numsteps = torch.zeros(n, 2, dtype=torch.int32, device=dev)
+        ray_indices = torch.zeros(n, dtype=torch.int32, device=dev)
+        counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        check(self.lib.nrs_training_samples(self.h, _stream_handle(stream), n, rays.data_ptr(), None if jitter is None else jitter.data_ptr(), float(cone_angle_constant),
+                                            int(max_samples), coords.data_ptr(), int(ld), numsteps.data_ptr(), ray_indices.data_ptr(), counters.data_ptr()))
+        return coords, numsteps, ray_indices, counters
+
     def visualize_activation(self, stream, layer, dimension, input, output):
         """Network::visualize_activation: unit `dimension` of forward_activations(layer), input [n, 7] f32, output [n] f32 (cuda tensors)."""
         _require_cuda(input, torch.float32, "input")
@@ -720,6 +796,11 @@ class Testbed:
 
     def add_edit_operator(self, op):
         self.edit_operators.append(op)
+
+    def training_samples(self, rays, jitter=None, max_samples=1 << 18, cone_angle_constant=None, stream=None):
+        """The network inputs of a batch of training rays (NerfNetwork.training_samples) with this testbed's cone angle: coords, numsteps, ray_indices, counters."""
+        cone = self.cone_angle_constant if cone_angle_constant is None else cone_angle_constant
+        return self.nerf_network.training_samples(stream, rays, jitter, cone, max_samples)
 
     def make_params(self, render_buffer, focal_length, camera_matrix0, camera_matrix1, rolling_shutter, screen_center, apply_operators):
         p = RenderParams()

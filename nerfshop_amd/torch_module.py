@@ -68,6 +68,49 @@ class _NerfNetworkFunction(torch.autograd.Function):
         return (grad_params if ctx.needs_input_grad[0] else None), grad_coords, None
 
 
+class _RayLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, outputs, coords, numsteps, target_rgba, network, params, background, ray_origins, ray_counter):
+        out16 = outputs.detach().to(torch.float16).contiguous()
+        numsteps_out, _, dl, loss, _ = network.ray_loss(None, params, numsteps, coords, out16, target_rgba, background=background, ray_origins=ray_origins,
+                                                        ray_counter=ray_counter)
+        ctx.save_for_backward(numsteps, numsteps_out, dl, ray_counter if ray_counter is not None else torch.empty(0, device=outputs.device))
+        ctx.loss_scale, ctx.shape = float(params.loss_scale), tuple(outputs.shape)
+        return loss.sum()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        numsteps, numsteps_out, dl, ray_counter = ctx.saved_tensors
+        n_rays, cap, dev = numsteps.shape[0], dl.shape[0], dl.device
+        grad = torch.zeros(ctx.shape, dtype=torch.float32, device=dev)
+        if n_rays == 0 or ctx.shape[0] == 0:
+            return grad, None, None, None, None, None, None, None, None
+        # The kernel wrote sample j < M' of ray r at compact index cbase_r + j; the output it belongs to is row base_r + j.  Found with a search over the rays' compact
+        # ends instead of a read-back: rays at or past the counter have no samples.
+        ray = torch.arange(n_rays, device=dev)
+        live = ray < (ray_counter[0] if ray_counter.numel() else n_rays)
+        cbase = numsteps_out[:, 1].to(torch.int64)
+        ends = torch.where(live, cbase + numsteps_out[:, 0].to(torch.int64), torch.full_like(cbase, 1 << 40))
+        k = torch.arange(cap, device=dev)
+        r = torch.searchsorted(ends, k, right=True).clamp_(max=n_rays - 1)
+        valid = live[r] & (k >= cbase[r]) & (k < ends[r])
+        src = (numsteps[:, 1].to(torch.int64)[r] + (k - cbase[r])).clamp_(0, ctx.shape[0] - 1)
+        vals = torch.where(valid[:, None], dl[:, :4].to(torch.float32), torch.zeros((), device=dev)) * (grad_loss / ctx.loss_scale)
+        grad[:, :4].index_add_(0, src, vals)  # one non-zero term per row at most: the sum does not depend on the order
+        return grad, None, None, None, None, None, None, None, None
+
+
+def ray_loss(outputs, coords, numsteps, target_rgba, network, params, background=None, ray_origins=None, ray_counter=None):
+    """The mean ray loss of compute_loss_kernel_train_nerf as a differentiable scalar.  outputs [n, 16] f32 (what NerfNetworkModule.forward returns for `coords`),
+    coords [n, >= 7] f32, numsteps [n_rays, 2] int32 (count, base), target_rgba [n_rays, 4] f32; network: the runtime.NerfNetwork whose activations and box apply
+    (module.network); params: RayLossParams with max_samples_compacted set.  The backward pass returns the kernel's dL/doutput divided by params.loss_scale: the derivative of
+    the returned value with respect to `outputs` (plus the reference's regularisation terms, which have no loss behind them).  Early stops are decided on values."""
+    if outputs.dim() != 2 or outputs.shape[1] != 16 or outputs.shape[0] != coords.shape[0]:
+        raise NrsError("ray_loss: outputs must be [n, 16] with one row per coords record")
+    return _RayLossFunction.apply(outputs, coords.contiguous(), numsteps, target_rgba, network, params, background, ray_origins, ray_counter)
+
+
 class NerfNetworkModule(torch.nn.Module):
     """input [n, 7] f32 (warped position, dt, warped direction) -> [n, 16] f32: rgb raw, density raw, the rgb network's padding outputs."""
 
@@ -90,8 +133,36 @@ class NerfNetworkModule(torch.nn.Module):
         self.params = torch.nn.Parameter(init.to(f"cuda:{self.ctx.device}"))
         self.loss_scale = float(loss_scale)
         self._resident = None
+        self._ray_bufs = None  # ray_step's device buffers, kept while the shapes stay
 
     def forward(self, coords):
         if coords.dim() != 2 or coords.shape[1] != 7:
             raise NrsError("NerfNetworkModule: input must be [n, 7]")
         return _NerfNetworkFunction.apply(self.params, coords.contiguous(), self)
+
+    def ray_step(self, coords, numsteps, target_rgba, params, background=None, ray_origins=None, ray_counter=None):
+        """One fused training step up to the optimiser: parameters to fp16, inference, nrs_ray_loss, nrs_network_backward on n = params.max_samples_compacted, then
+        self.params.grad (+)= dL/dparams / params.loss_scale.  Returns the mean loss (a 0-d tensor on the device).  The outputs and dL/doutput stay fp16 on the device and
+        nothing is read back; the caller runs optimizer.step().  coords [n, 7] f32, numsteps [n_rays, 2] int32, target_rgba [n_rays, 4] f32 as for ray_loss."""
+        net = self.network
+        coords = coords.contiguous()
+        p16 = self.params.detach().to(torch.float16)
+        net.set_params_device(p16)
+        self._resident = p16
+        key = (coords.shape[0], numsteps.shape[0], int(params.max_samples_compacted), coords.shape[1])
+        if self._ray_bufs is None or self._ray_bufs[0] != key:
+            dev, cap = coords.device, int(params.max_samples_compacted)
+            self._ray_bufs = (key, torch.empty((coords.shape[0], 16), dtype=torch.float16, device=dev),
+                              (torch.empty_like(numsteps), torch.empty(cap, coords.shape[1], dtype=torch.float32, device=dev),
+                               torch.zeros((cap, 16), dtype=torch.float16, device=dev), torch.empty(numsteps.shape[0], dtype=torch.float32, device=dev),
+                               torch.empty(1, dtype=torch.int32, device=dev)),
+                              torch.empty(self.params.numel(), dtype=torch.float32, device=dev))
+        _, out16, bufs, grad = self._ray_bufs
+        net.inference_strided(None, coords, out16)
+        _, coords_out, dl, loss, _ = net.ray_loss(None, params, numsteps, coords, out16, target_rgba, background=background, ray_origins=ray_origins,
+                                                  ray_counter=ray_counter, out=bufs)
+        net.backward(None, coords_out, dl, grad, None, accumulate=False)
+        if self.params.grad is None:  # (once, or after every zero_grad(set_to_none=True): with set_to_none=False a step allocates nothing)
+            self.params.grad = torch.zeros_like(self.params)
+        self.params.grad.add_(grad, alpha=1.0 / float(params.loss_scale))
+        return loss.sum()

@@ -1,0 +1,346 @@
+"""nrs_training_samples and nrs_ray_loss on the GPU against the twins of tests/ray_loss_ref.py, and the torch surface on top of them.
+
+dL/doutput is always judged in the accuracy unit of ray_loss_ref.error_units (what is left of |got - exact| after 2^-11 of the value, the rounding of the stored
+fp16, in float32 steps of the sizes of the terms that form the element), against closed_form (float64).  The bar is 4 x the worst error of closed_form32 -- the
+reference's own float32 arithmetic, its result stored as fp16 like the kernel's -- on the same inputs.  A ray is left out of a comparison iff the twin sees a
+transmittance within a relative 1e-3 of the stop threshold.
+
+Measured (MI355X; every case is in profiles/ray_loss.md): over all elements the kernel meets the bar in all 42 cases that compare a gradient, but in 35 of them
+both sides are 8 384 512 = 2^23 (1 - 2^-11): an element whose only term is below half of fp16's smallest step is stored as 0 and scores 2^23 whoever computes it,
+and the measure, kept as the issue states it, has no allowance for that step -- so that assertion alone could not fail.  judge() therefore also asserts the same
+unit and factor over the elements whose exact value is a normal fp16 (|v| >= 2^-14); there the kernel scores between 0 and 8097 units, closed_form32 between 0
+and 9072."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import ray_loss_ref as ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def ctx(built):
+    from nerfshop_amd import runtime
+    return runtime.Context(0)
+
+
+_NETS = {}
+
+
+def network(ctx, rgb_act=ref.ACT_LOGISTIC, den_act=ref.ACT_EXPONENTIAL):
+    """a model that carries the two activations and the unit box (nrs_ray_loss reads nothing else of it)"""
+    from nerfshop_amd import runtime, synth
+    if (rgb_act, den_act) not in _NETS:
+        desc = synth.model_desc(1, log2_hashmap_size=14)
+        desc.rgb_activation, desc.density_activation = rgb_act, den_act
+        _NETS[(rgb_act, den_act)] = runtime.NerfNetwork(ctx, desc, cell_cache_bytes=0)
+    return _NETS[(rgb_act, den_act)]
+
+
+def gpu_params(b):
+    from nerfshop_amd import _abi
+    p = b["p"]
+    return _abi.RayLossParams(loss_type=p["loss_type"], loss_scale=p["loss_scale"], color_space=p["color_space"], train_in_linear_colors=int(p["lin"]),
+                              background=p["background"], near_distance=p["near_distance"], density_l1_reg=int(p["l1"]), max_samples_compacted=p["cap"])
+
+
+def run(ctx, b, planes_in=False, planes_out=False, live=None):
+    """the batch through NerfNetwork.ray_loss with NaN-prefilled outputs; numpy results"""
+    net = network(ctx, b["rgb_act"], b["den_act"])
+    n, R, cap, ld = b["out"].shape[0], b["numsteps"].shape[0], b["p"]["cap"], b["coords"].shape[1]
+    rng = np.random.default_rng(1)
+    full = rng.normal(size=(n, 16)).astype(np.float16)  # rows 4..15: the rgb network's padding outputs, never read
+    full[:, :4] = b["out"].astype(np.float16)
+    assert (full[:, :4].astype(np.float64) == b["out"]).all(), "the batch's outputs must be fp16 values"
+    if planes_in:
+        out16 = torch.zeros((16, n + 5), dtype=torch.float16)
+        out16[:, :n] = torch.from_numpy(full.T.copy())
+    else:
+        out16 = torch.from_numpy(full)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(DEV)
+    nan = float("nan")
+    bufs = (torch.full((R, 2), -1, dtype=torch.int32, device=DEV), torch.full((cap, ld), nan, dtype=torch.float32, device=DEV),
+            torch.full((16, cap + 3) if planes_out else (cap, 16), nan, dtype=torch.float16, device=DEV), torch.full((R,), nan, dtype=torch.float32, device=DEV),
+            torch.full((1,), -1, dtype=torch.int32, device=DEV))
+    counter = None if live is None else torch.tensor([live], dtype=torch.int32, device=DEV)
+    got = net.ray_loss(None, gpu_params(b), t(b["numsteps"], torch.int32), t(b["coords"], torch.float32), out16.to(DEV), t(b["target"], torch.float32),
+                       background=None if b["background"] is None else t(b["background"], torch.float32),
+                       ray_origins=None if b["origins"] is None else t(b["origins"], torch.float32), ray_counter=counter, out=bufs)
+    torch.cuda.synchronize()
+    numsteps_out, coords_out, dl, loss, count = (x.cpu().numpy() for x in got)
+    dl = dl.T[:cap] if planes_out else dl
+    return numsteps_out, coords_out, dl.astype(np.float64), loss, int(count[0])
+
+
+def judge(name, b, got, exact_layout):
+    """Compare one run with the twins; returns (worst GPU error, worst closed_form32 error, left-out share)."""
+    numsteps_out, coords_out, dl, loss, count = got
+    c, c32 = ref.closed_form(b), ref.closed_form32(b)
+    f = c.f
+    R, cap, live = f.R, b["p"]["cap"], f.live
+    left_out = f.near_threshold.numpy().copy()
+    if exact_layout:
+        assert not left_out.any(), "a constructed batch has no transmittance near the threshold"
+        assert count == c.counter
+        assert (numsteps_out[:live] == c.numsteps_out.numpy()[:live]).all()
+    assert (numsteps_out[live:] == -1).all(), "rays at or past the counter are not written"
+    assert (loss[live:] == 0).all()
+    want_M, want_dl, A, dl32 = c.numsteps_out.numpy()[:, 0], c.dl.numpy(), c.A.numpy(), c32.dl.numpy()
+    same32 = (c32.f.M == f.M).numpy()
+    worst_gpu = worst_32 = worst_gpu_n = worst_32_n = 0.0
+    n_el = n_normal = beyond = 0
+    beyond_by = 0.0
+    end = 0
+    for r in range(live):
+        m, cb = int(numsteps_out[r, 0]), int(numsteps_out[r, 1])
+        if not exact_layout:  # (these batches' compact buffers hold every sample: nothing is clipped, so a ray starts where the one before it ends)
+            assert cb == end, (name, r)
+            end = cb + m
+        if left_out[r]:
+            continue
+        assert m == want_M[r], (name, r, m, int(want_M[r]))
+        # 1e-5 relative; outside the constructed case a ray's colour may also lie within float32's reach of its target, where the loss (a function of C - target)
+        # has no relative accuracy to speak of: there the float32 error of C itself is allowed for, 2^-20 (|C| + |target|) per channel -- sixteen float32 steps for
+        # a sum of up to 130 terms -- carried into the loss by its derivative g
+        slack = 0.0 if exact_layout else float((f.g[r].abs() * 2.0 ** -20 * (f.C[r].abs() + f.target[r].abs())).sum()) / 3.0 / float(b.get("n_rays", R))
+        loss_err = abs(float(loss[r]) - float(c.loss[r]))
+        if loss_err > 1e-5 * float(c.loss[r]):  # (reported: how many rays need the slack, and the largest miss as a multiple of 1e-5 relative)
+            beyond += 1
+            beyond_by = max(beyond_by, loss_err / (1e-5 * float(c.loss[r])))
+        assert loss_err <= 1e-5 * float(c.loss[r]) + slack, (name, r, float(loss[r]), float(c.loss[r]))
+        if m == 0:
+            continue
+        k0, src0 = int(c.numsteps_out[r, 1]), int(f.base[r])
+        assert (coords_out[cb:cb + m].view(np.uint32) == b["coords"][src0:src0 + m].view(np.uint32)).all(), "compacted records are copies"
+        e = ref.error_units(dl[cb:cb + m, :4], want_dl[k0:k0 + m], A[k0:k0 + m])
+        worst_gpu = max(worst_gpu, float(e.max()))
+        normal = np.abs(want_dl[k0:k0 + m]) >= 2.0 ** -14  # the exact value is a normal fp16: 2^-11 of it IS the stored value's rounding
+        n_el, n_normal = n_el + normal.size, n_normal + int(normal.sum())
+        worst_gpu_n = max(worst_gpu_n, float(np.where(normal, e, 0.0).max()))
+        if same32[r]:
+            e32 = ref.error_units(ref.to_fp16_values(dl32[k0:k0 + m]), want_dl[k0:k0 + m], A[k0:k0 + m])
+            worst_32 = max(worst_32, float(e32.max()))
+            worst_32_n = max(worst_32_n, float(np.where(normal, e32, 0.0).max()))
+    tail = min(count, cap)
+    assert (dl[tail:cap, :4] == 0).all() and (coords_out[tail:] == 0).all(), "the compact tail is zero"
+    assert np.isnan(dl[:, 4:]).all(), "rows 4..15 are never written"
+    share = float(left_out[:live].mean()) if live else 0.0
+    print(f"{name}: dL/doutput worst error GPU {worst_gpu:.1f}, closed_form32 {worst_32:.1f} (units of 2^-23 A); left out {share * 100:.2f} % of {live} rays")
+    print(f"{name}: fp16-normal elements ({n_normal} of {n_el}): GPU {worst_gpu_n:.1f}, closed_form32 {worst_32_n:.1f}; loss beyond 1e-5 relative: {beyond} rays, "
+          f"worst {beyond_by:.2f} x 1e-5")
+    # The issue's assertion stays with the callers.  Beside it, the same unit and the same factor over the elements whose exact value is a normal fp16 only: over all
+    # elements both sides saturate at 2^23 on a gradient that underflows fp16 (an all-zero dL would pass); here a wrong sign, suffix or carry scores 10^6 and more.
+    # In this range an element scores 0 unless its float32 error carries the value across an fp16 rounding boundary, and then it scores up to that float32 error;
+    # closed_form32 has no such element at all in 5 of the 42 cases (a bar of 0).  So the bar has a floor, from the formats alone: a product of M factors and sums
+    # of M terms carry up to M float32 half-steps each, M / 2 + M / 2 = M units for the longest ray consumed in the batch (130, or 1024 in the constructed case).
+    floor = float(f.M.max())
+    assert n_normal >= 0.3 * n_el
+    assert worst_gpu_n <= 4.0 * max(worst_32_n, floor), (name, worst_gpu_n, worst_32_n, floor)
+    return worst_gpu, worst_32, share
+
+
+@pytest.mark.parametrize("planes_in,planes_out,ld", [(False, False, 7), (True, True, 8), (True, False, 7), (False, True, 8)])
+def test_constructed_lengths(ctx, planes_in, planes_out, ld):
+    """Counts either side of 32, 64, 128 and a 1024-sample ray, decisive stops at sample 0, mid-chunk, lanes 31|32, 63|64, N - 2 and N - 1; no ray is left out."""
+    b, expect = ref.constructed_batch(3, ld=ld)
+    f = ref.closed_form(b).f
+    assert (f.M.numpy() == expect).all()
+    assert not bool(f.in_band.any()), "no transmittance in front of a sample lies in [0.5e-4, 2e-4]"
+    for stop in (1, 32, 33, 64, 65):
+        assert ((expect == stop) & (f.N.numpy() > stop)).any(), stop
+    assert ((expect == f.N.numpy() - 1) & (expect > 0)).any() and ((expect == f.N.numpy()) & (f.N.numpy() > 1)).any()
+    got = run(ctx, b, planes_in, planes_out)
+    worst_gpu, worst_32, share = judge(f"constructed (planes {planes_in}/{planes_out}, ld {ld})", b, got, True)
+    assert share == 0.0
+    assert worst_gpu <= 4.0 * worst_32
+
+
+@pytest.mark.parametrize("loss_type", range(7))
+@pytest.mark.parametrize("colour", [(ref.LINEAR, False), (ref.SRGB, False), (ref.SRGB, True)])
+def test_every_loss_and_colour_path(ctx, loss_type, colour):
+    """200 random rays of 0..130 samples, alpha of the target in {0, 0.5, 1}; per-ray background for even losses, the constant one for odd."""
+    b = ref.random_batch(140 + loss_type, loss_type=loss_type, color_space=colour[0], lin=colour[1], per_ray_bg=loss_type % 2 == 0)
+    worst_gpu, worst_32, share = judge(f"loss {loss_type} colour {colour}", b, run(ctx, b), False)
+    assert share <= 0.01
+    assert worst_gpu <= 4.0 * worst_32
+
+
+@pytest.mark.parametrize("rgb_act", range(4))
+@pytest.mark.parametrize("den_act", range(4))
+def test_activations(ctx, rgb_act, den_act):
+    """Every pair of activations, with the density regulariser and the near-distance term on.  Raw densities stay within the reach of each activation's step: a
+    ReLU or plain density of up to 9 per unit length never stops a ray, the exponential one does."""
+    b = ref.random_batch(70 + 4 * rgb_act + den_act, rgb_act_kind=rgb_act, den_act_kind=den_act, l1=True, near_distance=0.7, with_origins=True,
+                         loss_type=ref.HUBER)
+    worst_gpu, worst_32, share = judge(f"rgb activation {rgb_act} density activation {den_act}", b, run(ctx, b), False)
+    assert share <= 0.01
+    assert worst_gpu <= 4.0 * worst_32
+
+
+def test_counter_cap_and_determinism(ctx):
+    """Rays at or past the device counter do nothing; a compact buffer smaller than the sum of M clips the last rays (the counter stays unclipped); two calls agree bit for bit."""
+    b = ref.random_batch(91, n_rays=120, max_count=80)
+    total = ref.closed_form(b).counter
+    b["live"] = 111
+    live_total = ref.closed_form(b).counter
+    assert live_total < total
+    b["p"]["cap"] = live_total - 37
+    c = ref.closed_form(b)
+    assert int((c.numsteps_out[:111, 0] < c.f.M[:111]).sum()) >= 1 and c.counter == live_total
+    first = run(ctx, b, live=111)
+    judge("clipped", b, first, True)
+    again = run(ctx, b, live=111)
+    for x, y in zip(first[:4], again[:4]):
+        assert x.tobytes() == y.tobytes()
+    assert first[4] == again[4] == live_total
+
+
+def test_no_rays_and_refusals(ctx):
+    from nerfshop_amd import _abi, runtime
+    net = network(ctx)
+    p = _abi.RayLossParams(max_samples_compacted=6)
+    e = lambda *shape, dt=torch.float32: torch.full(shape, 7, dtype=dt, device=DEV)
+    numsteps_out, coords_out, dl, loss, count = net.ray_loss(None, p, e(0, 2, dt=torch.int32), e(0, 7), e(0, 16, dt=torch.float16), e(0, 4),
+                                                             out=(e(0, 2, dt=torch.int32), e(6, 7), e(6, 16, dt=torch.float16), e(0), e(1, dt=torch.int32)))
+    torch.cuda.synchronize()
+    assert int(count[0]) == 0 and float(coords_out.abs().max()) == 0 and float(dl[:, :4].abs().max()) == 0 and float(dl[:, 4:].min()) == 7
+    with pytest.raises(runtime.NrsError):
+        net.ray_loss(None, p, e(3, 2, dt=torch.int32), e(5, 6), e(5, 16, dt=torch.float16), e(3, 4))
+    with pytest.raises(runtime.NrsError):
+        net.ray_loss(None, p, e(3, 2, dt=torch.int32), e(5, 7), e(5, 16, dt=torch.float16), e(2, 4))
+    rays = torch.zeros(4, 6, device=DEV)
+    with pytest.raises(runtime.NrsError, match="occupancy"):  # NRS_ERR_STATE: no density bitfield yet
+        net.training_samples(None, rays, None, 0.0, 16)
+    from nerfshop_amd import synth
+    lit = runtime.NerfNetwork(ctx, synth.model_desc(1, log2_hashmap_size=14), cell_cache_bytes=0, n_extra_dims=3)
+    with pytest.raises(runtime.NrsError, match="n_extra_dims"):
+        lit.training_samples(None, rays, None, 0.0, 16)
+    lit.close()
+
+
+# ---- the generator -----------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def generated(ctx, scene):
+    """100 rays from outside the box (tests/test_ray_loss_host.py's), the twin's walk at three entry distances, and a model that holds the scene's occupancy"""
+    from nerfshop_amd import runtime
+    from oracle import oracle as orc
+    rng = np.random.default_rng(21)
+    o = rng.normal(size=(100, 3))
+    o = (0.5 + 1.6 * o / np.linalg.norm(o, axis=1, keepdims=True)).astype(np.float32)
+    d = rng.uniform(0.3, 0.7, (100, 3)).astype(np.float32) - o
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    rays, jitter = np.concatenate([o, d], 1).astype(np.float32), rng.random(100).astype(np.float32)
+    lib = orc.load()
+    walks = {k: ref.march(lib, scene.bitfield, ref.AABB_UNIT, rays, jitter, 0.0, tmin_nudge_ulps=k) for k in (-2, 0, 2)}
+    counts = {k: np.array([len(r) for r in w]) for k, w in walks.items()}
+    stable = (counts[-2] == counts[0]) & (counts[0] == counts[2])
+    net = runtime.NerfNetwork(ctx, scene.desc, cell_cache_bytes=0)
+    net.set_density_bitfield(scene.bitfield)
+    return net, rays, jitter, walks[0], counts[0], stable
+
+
+def test_training_samples_against_the_twin(generated):
+    net, rays, jitter, walk, counts, stable = generated
+    assert stable.mean() >= 0.98 and (counts > 0).sum() >= 30
+    total = int(counts.sum())
+    max_samples = total + 11
+    coords, numsteps, ray_indices, counters = (x.cpu().numpy() for x in net.training_samples(None, torch.from_numpy(rays).to(DEV), torch.from_numpy(jitter).to(DEV), 0.0,
+                                                                                              max_samples, ld=8))
+    emitted = int(counters[0])
+    got_counts = np.zeros(len(counts), np.int64)
+    got_counts[ray_indices[:emitted]] = numsteps[:emitted, 0]
+    assert (got_counts[stable] == counts[stable]).all(), "stable rays have the twin's sample count"
+    # the layout is a function of the counts: the scan in input order, whatever the counts are
+    want_numsteps, want_idx, want_counters, bases = ref.layout_from_counts(got_counts, max_samples)
+    assert emitted == want_counters[0] and int(counters[1]) == want_counters[1]
+    assert (ray_indices[:emitted] == want_idx).all() and (numsteps[:emitted] == want_numsteps).all()
+    assert (numsteps[emitted:] == 0).all() and (ray_indices[emitted:] == 0).all()
+    compared = 0
+    for i in np.nonzero(stable & (counts > 0))[0]:
+        rec = coords[bases[i]:bases[i] + counts[i], :7]
+        assert (rec.view(np.uint32) == walk[i].view(np.uint32)).all(), f"ray {i}: records differ from the twin's"
+        compared += len(rec)
+    assert compared > 5000
+    end = int(want_counters[1])
+    assert (coords[end:, :7] == 0).all() and (coords[:, 7] == 0).all(), "zero tail; float 7 of a record is never written"
+
+
+def test_training_samples_drops_clips_and_repeats(generated):
+    """max_samples below the total: the ray that does not fit and every later one are dropped, the counter still counts them, the records behind the last emitted ray
+    are zero; no jitter (NULL) and no rays are handled; two calls agree bit for bit."""
+    net, rays, jitter, walk, counts, stable = generated
+    d_rays = torch.from_numpy(rays).to(DEV)
+    full = [x.cpu().numpy() for x in net.training_samples(None, d_rays, None, 0.0, 1 << 16)]
+    got_counts = np.zeros(len(counts), np.int64)
+    got_counts[full[2][:full[3][0]]] = full[1][:full[3][0], 0]
+    cut = int(got_counts.sum()) * 2 // 3
+    runs = [[x.cpu().numpy() for x in net.training_samples(None, d_rays, None, 0.0, cut)] for _ in range(2)]
+    for x, y in zip(*runs):
+        assert x.tobytes() == y.tobytes()
+    coords, numsteps, ray_indices, counters = runs[0]
+    want_numsteps, want_idx, want_counters, bases = ref.layout_from_counts(got_counts, cut)
+    assert 0 < want_counters[0] < (got_counts > 0).sum()
+    assert tuple(counters) == want_counters and (numsteps[:counters[0]] == want_numsteps).all() and (ray_indices[:counters[0]] == want_idx).all()
+    end = int(want_numsteps[-1].sum())
+    assert (coords[:end] == full[0][:end]).all() and (coords[end:] == 0).all()
+    coords, numsteps, ray_indices, counters = net.training_samples(None, torch.zeros(0, 6, device=DEV), None, 0.0, 9)
+    assert counters.tolist() == [0, 0] and float(coords.abs().max()) == 0
+    # a ray the walk could not end on has no samples: zero direction, non-finite origin
+    bad = rays[:4].copy()
+    bad[0, 3:] = 0
+    bad[1, 0] = np.inf
+    bad[2, 3:] *= 1e-20
+    c = net.training_samples(None, torch.from_numpy(bad).to(DEV), None, 0.0, 4096)[3].cpu().numpy()
+    assert c[1] == got_counts[3] and c[0] == (1 if got_counts[3] else 0)
+
+
+# ---- torch -------------------------------------------------------------------------------------------------------------------------------------------------------
+def test_ray_loss_function_and_ray_step(ctx, generated, scene):
+    """torch_module.ray_loss differentiates the mean loss with respect to the outputs (the kernel's dL/doutput over the loss scale, scattered back to the samples'
+    rows), and NerfNetworkModule.ray_step leaves the same parameter gradient as forward -> ray_loss -> backward; a few Adam steps lower the loss."""
+    from nerfshop_amd import _abi, synth, torch_module
+    net, rays, jitter, walk, counts, stable = generated
+    coords, numsteps, ray_indices, counters = net.training_samples(None, torch.from_numpy(rays).to(DEV), torch.from_numpy(jitter).to(DEV), 0.0, 20000)
+    emitted, n = int(counters[0]), int(counters[1])
+    assert n <= 20000
+    numsteps, coords = numsteps[:emitted].contiguous(), coords[:n].contiguous()
+    rng = np.random.default_rng(2)
+    target = torch.from_numpy(np.concatenate([rng.random((emitted, 3)), np.ones((emitted, 1))], 1).astype(np.float32)).to(DEV)
+    module = torch_module.NerfNetworkModule(desc=synth.model_desc(1, log2_hashmap_size=14), seed=5, ctx=ctx)
+    params = _abi.RayLossParams(max_samples_compacted=n + 64)
+    module.zero_grad()
+    outputs = module(coords)
+    outputs.retain_grad()
+    loss = torch_module.ray_loss(outputs, coords, numsteps, target, module.network, params)
+    loss.backward()
+    manual = module.params.grad.clone()
+    # the derivative with respect to the outputs, against the twin on the very outputs the network gave
+    b = dict(out=outputs.detach()[:, :4].double().cpu().numpy(), coords=coords.cpu().numpy(), numsteps=numsteps.cpu().numpy().astype(np.int64), target=target.cpu().numpy(),
+             background=None, origins=None, rgb_act=ref.ACT_LOGISTIC, den_act=ref.ACT_EXPONENTIAL, aabb=ref.AABB_UNIT,
+             p=dict(loss_type=ref.L2, color_space=ref.LINEAR, lin=False, loss_scale=128.0, background=(0.0, 0.0, 0.0), near_distance=0.0, l1=False, cap=n + 64))
+    c = ref.closed_form(b)
+    np.testing.assert_allclose(float(loss.detach()), float(c.loss.sum()), rtol=1e-5)
+    want = np.zeros((n, 4))
+    used = (c.src >= 0).numpy()
+    want[c.src.numpy()[used]] = c.dl.numpy()[used] / 128.0
+    got = outputs.grad[:, :4].double().cpu().numpy()
+    assert float(outputs.grad[:, 4:].abs().max()) == 0
+    scale = np.abs(want).max()
+    assert scale > 0 and np.abs(got - want).max() <= 2e-3 * scale
+    module.zero_grad()
+    fused = module.ray_step(coords, numsteps, target, params)
+    np.testing.assert_allclose(float(fused), float(loss.detach()), rtol=1e-6)
+    g = module.params.grad
+    assert float((g - manual).abs().max()) <= 1e-3 * float(manual.abs().max()) and float(manual.abs().max()) > 0
+    opt = torch.optim.Adam(module.parameters(), lr=1e-2, eps=1e-15)
+    history = []
+    for _ in range(12):
+        opt.zero_grad()
+        history.append(float(module.ray_step(coords, numsteps, target, params)))
+        opt.step()
+    print("ray_step losses:", " ".join(f"{v:.5f}" for v in history))
+    assert history[-1] < history[0]
