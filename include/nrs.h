@@ -908,6 +908,80 @@ int nrs_ray_loss(nrs_model* model, void* stream, const nrs_ray_loss_params* para
                  const float* d_background, const float* d_ray_origins, uint32_t* d_numsteps_out, float* d_coords_out, void* d_dL_doutput_fp16, uint32_t ld_dl,
                  int dl_layout, float* d_loss, uint32_t* d_counter_out);
 
+/* ---- optimiser: the fused Adam step between nrs_network_backward and the next forward pass ------------------------------------------------------- */
+/* The optimiser the reference trains with -- Ema(0.95) over ExponentialDecay(20000, 10000, 0.33) over Adam(1e-2, 0.9, 0.99, 1e-15, l2_reg 1e-6), configs/nerf/base.json,
+ * stepped by m_trainer->optimizer_step(stream, LOSS_SCALE) (src/testbed_nerf.cu:3761) -- as one pass over the parameters.  tiny-cuda-nn itself is not part of the
+ * reference tree, so THIS TEXT IS THE DEFINITION of the rule (as recalled from tiny-cuda-nn's adam.h); tests/optimizer_ref.py restates it in float64.  Callers detect
+ * these entry points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  Not here (tiny-cuda-nn's defaults are "off"): AdaBound limits,
+ * weight clipping, relative and absolute weight decay.  Non-finite gradients are not filtered, as in tiny-cuda-nn.
+ *
+ * THE RULE.  n parameters in the blob's order, the first n_matrix of them matrix weights.  Per element i, in fp32 without contraction, in exactly this order:
+ *     g = grad[i] / loss_scale
+ *     if i >= n_matrix and g == 0:  master, m, v, steps and fp16 of i stay untouched   (the skip; -0 counts as 0: no momentum drift, no step count)
+ *     if i <  n_matrix:             g = g + l2_reg * w                                (w = master[i])
+ *     m = beta1 * m[i] + (1 - beta1) * g
+ *     v = beta2 * v[i] + (1 - beta2) * (g * g)
+ *     t = ++steps[i]                                                                  (uint32, one counter per parameter)
+ *     lr_i = learning_rate * (i >= n_matrix ? non_matrix_lr_factor : 1) * bias(t)
+ *     w' = w - (lr_i / (sqrt(v) + epsilon)) * m
+ *     master[i] = w';  fp16[i] = round-to-nearest-even(w')
+ *   bias(t) = sqrt(1 - beta2^t) / (1 - beta1^t) comes from a table: the host evaluates it in float64 for t = 1 .. T_sat and rounds each value once to fp32; T_sat is the
+ *   first t FROM WHICH ON the rounded value is exactly 1.0f (about 1 650 for base.json's betas; "from which on" because bias(1) is 1 as well whenever
+ *   1 - beta2 == (1 - beta1)^2, as with 0.9 / 0.99); the kernel reads table[min(t, T_sat)].  A DEVIATION from tiny-cuda-nn's fp32 powf per element, deliberate: more
+ *   accurate, exactly reproducible, and the step stays memory-bound.
+ *   EMA, when ema_decay = d > 0: every step and for EVERY element (the skip does not apply) ema[i] = a * ema[i] + b * float(fp16[i]), where with T the optimiser's own
+ *   step count after this step a = d (1 - d^(T-1)) / (1 - d^T) and b = (1 - d) / (1 - d^T), computed by the host in float64 and rounded once.  ema is fp32 (tiny-cuda-nn
+ *   keeps it in fp16: a deviation).  With ema_decay == 0 the ema array is never touched by a step.
+ *   zero_grad != 0: 0.0f is stored to grad[i] wherever a non-zero value (any bit set) was read, so the caller's next nrs_network_backward can run with accumulate = 1
+ *   and no memset.
+ *
+ * nrs_adam_bias_table (host only): out[t - 1] = bias(t) for t = 1 .. T_sat, *n_out = T_sat; `out` may be NULL to ask for the size; NRS_ERR_INVALID_ARG when cap < T_sat
+ *   (with out != NULL), for a beta outside [0, 1), and when T_sat would exceed 65 536 (a beta very close to 1).
+ * nrs_exponential_decay_lr (host only): base * decay_base^k with k = 0 while steps_done < decay_start, else floor((steps_done - decay_start) / decay_interval) + 1,
+ *   evaluated in float64 and rounded once.  decay_interval == 0 counts as 1.  This is the definition (as recalled from tiny-cuda-nn's exponential_decay.h).
+ *
+ * nrs_optimizer_create: an optimiser over n_params elements with its own fp16 array.  nrs_optimizer_create_for_model: n_params and n_matrix are the model's (all MLP
+ *   weights, then the hash table); the fp16 of the hash table is the model's RESIDENT table -- a step writes it in place, no staging and no copy -- the fp16 MLP weights go to
+ *   a small buffer of the optimiser's, from which the step re-arranges the MFMA fragments on the same stream (the kernel of nrs_model_set_params_device), and the model's
+ *   cell records, if it keeps any, are rebuilt behind that.  The model must outlive the optimiser; while it is bound, nrs_model_set_params / _device on it would put the
+ *   fp16 out of step with the master weights (call nrs_optimizer_set_weights instead).  Supported for models without light directions.
+ * nrs_optimizer_set_weights: the fp32 master weights from a host (on_device == 0; returns when the copy is done) or device pointer; zeroes m, v, steps and the step
+ *   count, sets ema to the weights and writes the fp16 copy (into the model if bound: from then on it has parameters).
+ * nrs_optimizer_step: asynchronous on `stream`, never waits for the device.  d_grad [n_params] f32, any 4-byte alignment.
+ * nrs_optimizer_get_state / _set_state: synchronous (they wait for the device first); `which` is nrs_optimizer_state, n must be n_params; MASTER / M / V / EMA are f32,
+ *   STEPS u32, PARAMS_FP16 u16.  For tests and checkpoints, with nrs_optimizer_step_count / _set_step_count.  set_state on a bound optimiser with PARAMS_FP16 also
+ *   refreshes the model's fragments and records.
+ * nrs_optimizer_export_fp16: the whole blob as fp16 into d_out [n_params], asynchronous: NRS_OPT_EXPORT_WEIGHTS copies the fp16 the network reads,
+ *   NRS_OPT_EXPORT_EMA rounds ema (round to nearest even): what a second model renders with (nrs_model_set_params_device) while the first one trains.
+ * Refused before any HIP call.  NRS_ERR_INVALID_ARG: a NULL argument; a struct_size other than sizeof(nrs_adam_params); a beta outside [0, 1); a negative or non-finite
+ *   epsilon, l2_reg, learning_rate or non_matrix_lr_factor; a loss_scale that is not finite or <= 0; ema_decay outside [0, 1); n_matrix > n_params; n_params == 0 or
+ *   > 2^31; an unknown `which`; n != n_params in get / set.  NRS_ERR_UNSUPPORTED: a model with n_extra_dims != 0.  NRS_ERR_STATE: a step, export or
+ *   get / set before nrs_optimizer_set_weights. */
+typedef struct nrs_optimizer nrs_optimizer;
+typedef struct nrs_adam_params {
+	uint32_t struct_size;          /* refused unless == sizeof(nrs_adam_params) */
+	float    beta1, beta2;         /* base.json: 0.9, 0.99 */
+	float    epsilon;              /* 1e-15 */
+	float    l2_reg;               /* 1e-6, matrix weights only */
+	float    non_matrix_lr_factor; /* 1 */
+	float    ema_decay;            /* 0.95; 0 = no EMA */
+} nrs_adam_params;
+typedef enum nrs_optimizer_state { NRS_OPT_MASTER = 0, NRS_OPT_M = 1, NRS_OPT_V = 2, NRS_OPT_STEPS = 3, NRS_OPT_EMA = 4, NRS_OPT_PARAMS_FP16 = 5 } nrs_optimizer_state;
+typedef enum nrs_optimizer_export { NRS_OPT_EXPORT_WEIGHTS = 0, NRS_OPT_EXPORT_EMA = 1 } nrs_optimizer_export;
+int      nrs_adam_bias_table(float beta1, float beta2, float* out, uint32_t cap, uint32_t* n_out);
+float    nrs_exponential_decay_lr(float base, uint32_t decay_start, uint32_t decay_interval, float decay_base, uint32_t steps_done);
+int      nrs_optimizer_create(nrs_ctx* ctx, size_t n_params, size_t n_matrix, const nrs_adam_params* params, nrs_optimizer** out);
+int      nrs_optimizer_create_for_model(nrs_model* model, const nrs_adam_params* params, nrs_optimizer** out);
+void     nrs_optimizer_destroy(nrs_optimizer* opt);
+int      nrs_optimizer_set_weights(nrs_optimizer* opt, const float* weights_f32, int on_device, void* stream);
+int      nrs_optimizer_step(nrs_optimizer* opt, void* stream, float* d_grad, float loss_scale, float learning_rate, int zero_grad);
+int      nrs_optimizer_get_state(nrs_optimizer* opt, int which, void* h_out, size_t n);
+int      nrs_optimizer_set_state(nrs_optimizer* opt, int which, const void* h_in, size_t n);
+int      nrs_optimizer_export_fp16(nrs_optimizer* opt, int which, void* d_out_fp16, void* stream);
+uint32_t nrs_optimizer_step_count(const nrs_optimizer* opt);
+int      nrs_optimizer_set_step_count(nrs_optimizer* opt, uint32_t steps);
+size_t   nrs_optimizer_n_params(const nrs_optimizer* opt, size_t* n_matrix);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,48 @@ private:
 	nrs_model* m_model = nullptr;
 };
 
+// tcnn::Trainer's optimiser half as the training loop uses it: m_trainer->optimizer_step(stream, LOSS_SCALE) (testbed_nerf.cu:3761) over the optimiser of
+// configs/nerf/base.json (nrs.h "optimiser").  Bound to a network, a step writes the parameters the network reads: no set_params call follows it.  The gradient buffer is
+// the caller's (n_params() floats, what NerfNetwork::backward accumulates into); the learning rate is the caller's schedule (exponential_decay_lr).
+class Optimizer {
+public:
+	static nrs_adam_params base_params() { return nrs_adam_params{(uint32_t)sizeof(nrs_adam_params), 0.9f, 0.99f, 1e-15f, 1e-6f, 1.0f, 0.95f}; }
+	Optimizer(NerfNetwork& network, const nrs_adam_params& params) { check(nrs_optimizer_create_for_model(network.get(), &params, &m_opt), "nrs_optimizer_create_for_model"); }
+	Optimizer(Context& ctx, size_t n_params, size_t n_matrix, const nrs_adam_params& params) {
+		check(nrs_optimizer_create(ctx.get(), n_params, n_matrix, &params, &m_opt), "nrs_optimizer_create");
+	}
+	~Optimizer() { nrs_optimizer_destroy(m_opt); }
+	Optimizer(const Optimizer&) = delete;
+	Optimizer& operator=(const Optimizer&) = delete;
+
+	size_t n_params() const { return nrs_optimizer_n_params(m_opt, nullptr); }
+	// Trainer::set_params_full_precision / initialize_params: fp32 master weights from the host or the device
+	void set_weights(const float* weights, bool on_device, void* stream) { check(nrs_optimizer_set_weights(m_opt, weights, on_device ? 1 : 0, stream), "nrs_optimizer_set_weights"); }
+	void set_gradients(float* d_grad, bool zero_after_step = true) { m_grad = d_grad; m_zero_grad = zero_after_step; }
+	void set_learning_rate(float lr) { m_lr = lr; }
+	float learning_rate() const { return m_lr; }
+	// ExponentialDecay(decay_start, decay_interval, decay_base) over `base`, for the step after steps_done finished ones
+	static float exponential_decay_lr(float base, uint32_t decay_start, uint32_t decay_interval, float decay_base, uint32_t steps_done) {
+		return nrs_exponential_decay_lr(base, decay_start, decay_interval, decay_base, steps_done);
+	}
+	void step(void* stream, float loss_scale) {
+		if (!m_grad) throw std::runtime_error("Optimizer::step: no gradient buffer (set_gradients)");
+		check(nrs_optimizer_step(m_opt, stream, m_grad, loss_scale, m_lr, m_zero_grad ? 1 : 0), "nrs_optimizer_step");
+	}
+	uint32_t step() const { return nrs_optimizer_step_count(m_opt); }
+	// the blob as fp16 on the device: the weights, or the EMA a second network renders with (NerfNetwork::set_params_device)
+	void export_fp16(nrs_optimizer_export which, void* d_out_fp16, void* stream) { check(nrs_optimizer_export_fp16(m_opt, which, d_out_fp16, stream), "nrs_optimizer_export_fp16"); }
+	void get_state(nrs_optimizer_state which, void* h_out, size_t n) { check(nrs_optimizer_get_state(m_opt, which, h_out, n), "nrs_optimizer_get_state"); }
+	void set_state(nrs_optimizer_state which, const void* h_in, size_t n) { check(nrs_optimizer_set_state(m_opt, which, h_in, n), "nrs_optimizer_set_state"); }
+	nrs_optimizer* get() const { return m_opt; }
+
+private:
+	nrs_optimizer* m_opt = nullptr;
+	float* m_grad = nullptr;
+	float m_lr = 1e-2f;
+	bool m_zero_grad = true;
+};
+
 // EditOperator (edit_operator.h:43-91): the interface NerfTracer::m_edit_operators holds (testbed.h:237) -- cage deformations and affine
 // duplications alike.  An operator owns its device tables.
 class EditOperator {

@@ -187,6 +187,26 @@ class RayLossParams(C.Structure):
                 raise TypeError(f"RayLossParams has no field {k}")
 
 
+class AdamParams(C.Structure):
+    """nrs_adam_params; the defaults are the optimiser of configs/nerf/base.json (Adam 0.9 / 0.99 / 1e-15, l2_reg 1e-6, Ema 0.95)"""
+    _fields_ = [("struct_size", C.c_uint32), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("l2_reg", C.c_float),
+                ("non_matrix_lr_factor", C.c_float), ("ema_decay", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.struct_size = C.sizeof(AdamParams)
+        self.beta1, self.beta2, self.epsilon, self.l2_reg, self.non_matrix_lr_factor, self.ema_decay = 0.9, 0.99, 1e-15, 1e-6, 1.0, 0.95
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"AdamParams has no field {k}")
+            setattr(self, k, v)
+
+
+OPT_MASTER, OPT_M, OPT_V, OPT_STEPS, OPT_EMA, OPT_PARAMS_FP16 = range(6)  # nrs_optimizer_state
+OPT_EXPORT_WEIGHTS, OPT_EXPORT_EMA = 0, 1  # nrs_optimizer_export
+# the schedule of configs/nerf/base.json: ExponentialDecay(decay_start, decay_interval, decay_base) over a learning rate of 1e-2
+BASE_LEARNING_RATE, BASE_DECAY_START, BASE_DECAY_INTERVAL, BASE_DECAY_BASE = 1e-2, 20000, 10000, 0.33
+
 # every symbol include/nrs.h declares; tests check the library exports exactly these
 EXPORTS = [
     "nrs_last_error", "nrs_abi_version", "nrs_edit_poisson_interpolate", "nrs_edit_download_poisson", "nrs_comm_unique_id", "nrs_comm_create", "nrs_comm_info", "nrs_comm_destroy", "nrs_gather_tiles", "nrs_comm_probe_self_p2p",
@@ -217,6 +237,9 @@ EXPORTS = [
     "nrs_selection_dilate", "nrs_selection_erode", "nrs_selection_fine_mesh",
     "nrs_network_backward",
     "nrs_training_samples", "nrs_ray_loss",
+    "nrs_adam_bias_table", "nrs_exponential_decay_lr", "nrs_optimizer_create", "nrs_optimizer_create_for_model", "nrs_optimizer_destroy", "nrs_optimizer_set_weights",
+    "nrs_optimizer_step", "nrs_optimizer_get_state", "nrs_optimizer_set_state", "nrs_optimizer_export_fp16", "nrs_optimizer_step_count", "nrs_optimizer_set_step_count",
+    "nrs_optimizer_n_params",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -307,6 +330,24 @@ def load():
     if hasattr(lib, "nrs_ray_loss"):  # (detected by symbol, like nrs_network_backward)
         lib.nrs_training_samples.argtypes = [P, P, U32, P, P, C.c_float, U32, P, U32, P, P, P]
         lib.nrs_ray_loss.argtypes = [P, P, C.POINTER(RayLossParams), U32, P, P, U32, P, U32, P, U32, I, P, P, P, P, P, P, U32, I, P, P]
+    if hasattr(lib, "nrs_optimizer_step"):  # (detected by symbol, like nrs_network_backward)
+        lib.nrs_adam_bias_table.argtypes = [C.c_float, C.c_float, P, U32, C.POINTER(U32)]
+        lib.nrs_exponential_decay_lr.argtypes = [C.c_float, U32, U32, C.c_float, U32]
+        lib.nrs_exponential_decay_lr.restype = C.c_float
+        lib.nrs_optimizer_create.argtypes = [P, C.c_size_t, C.c_size_t, C.POINTER(AdamParams), C.POINTER(P)]
+        lib.nrs_optimizer_create_for_model.argtypes = [P, C.POINTER(AdamParams), C.POINTER(P)]
+        lib.nrs_optimizer_destroy.argtypes = [P]
+        lib.nrs_optimizer_destroy.restype = None
+        lib.nrs_optimizer_set_weights.argtypes = [P, P, I, P]
+        lib.nrs_optimizer_step.argtypes = [P, P, P, C.c_float, C.c_float, I]
+        lib.nrs_optimizer_get_state.argtypes = [P, I, P, C.c_size_t]
+        lib.nrs_optimizer_set_state.argtypes = [P, I, P, C.c_size_t]
+        lib.nrs_optimizer_export_fp16.argtypes = [P, I, P, P]
+        lib.nrs_optimizer_step_count.argtypes = [P]
+        lib.nrs_optimizer_step_count.restype = U32
+        lib.nrs_optimizer_set_step_count.argtypes = [P, U32]
+        lib.nrs_optimizer_n_params.argtypes = [P, C.POINTER(C.c_size_t)]
+        lib.nrs_optimizer_n_params.restype = C.c_size_t
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

@@ -1,5 +1,6 @@
 // nrs_api_model.cpp -- the model: create / destroy, parameters, both cell-record caches, numerics, light direction, occupancy set / get / refresh.
 #include "nrs_host.h"
+#include "nrs_optimizer.h"
 
 #include <cmath>
 #include <cstdio>
@@ -264,6 +265,36 @@ size_t nrs_model_cell_cache_bytes(const nrs_model* m, uint32_t* n_levels) {
 	return m->records_bytes;
 }
 
+// ---- shared with the optimiser (nrs_optimizer.h): the two halves of nrs_model_set_params_device ------------------------------------------------------------
+} // extern "C"
+void nrs::model_param_counts(const nrs_model* m, uint32_t* n_mlp, size_t* n_params) {
+	const uint32_t k = n_mlp_weights(m->desc, m->n_extra_dims);
+	if (n_mlp) *n_mlp = k;
+	if (n_params) *n_params = (size_t)k + (size_t)m->total_entries * 2;
+}
+uint16_t* nrs::model_grid_fp16(nrs_model* m) { return (uint16_t*)m->d_grid.get(); }
+int nrs::model_mlp_from_device(nrs_model* m, const uint16_t* d, void* stream) {
+	if (!m->d_wfrag_src.get()) { // the fragment permutation as indices: run the host routine on the identity (index + 1; 0 stays "padding")
+		static_assert(kDensityW + 64 * 48 + 2 * 64 * 64 + 16 * 64 < kFragNegate, "weight indices + 1 fit 15 bits");
+		std::vector<uint16_t> ident(n_mlp_weights(m->desc, m->n_extra_dims)), canon(kCanonW), src(kWfragDeviceBytes / 2);
+		for (size_t i = 0; i < ident.size(); ++i) ident[i] = (uint16_t)(i + 1);
+		lower_weights(m->desc, ident.data(), canon.data(), kLowerIndices, m->n_extra_dims);
+		make_weight_fragments(canon.data(), src.data(), kFragOne);
+		DeviceBuffer<uint16_t> fresh;
+		HIP_TRY(fresh.alloc(kWfragDeviceBytes / 2));
+		const hipError_t up = hipMemcpy(fresh.get(), src.data(), kWfragDeviceBytes, hipMemcpyHostToDevice);
+		if (up != hipSuccess) return fail_hip(up, "nrs_model_set_params_device: upload of the weight permutation");
+		m->d_wfrag_src = std::move(fresh); // (never keep a permutation that was not uploaded: later calls would scramble the weights silently)
+	}
+	NRS_LAUNCH(launch_weight_fragments(d, m->d_wfrag_src.get(), (uint16_t*)m->d_wfrag.get(), kWfragDeviceBytes / 2, stream));
+	return NRS_OK;
+}
+int nrs::model_grid_written(nrs_model* m, void* stream) {
+	m->have_params = true;
+	return rebuild_cell_cache(m, stream, false);
+}
+extern "C" {
+
 int nrs_model_set_params(nrs_model* m, const void* h_params_fp16, size_t n_params) {
 	if (!m || !h_params_fp16) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_params: NULL argument");
 	const uint32_t n_mlp = n_mlp_weights(m->desc, m->n_extra_dims);
@@ -299,24 +330,10 @@ int nrs_model_set_params_device(nrs_model* m, const void* d_params_fp16, size_t 
 		return fail(NRS_ERR_INVALID_ARG, buf);
 	}
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	hipStream_t s = (hipStream_t)stream;
 	const uint16_t* d = (const uint16_t*)d_params_fp16;
-	if (!m->d_wfrag_src.get()) { // the fragment permutation as indices: run the host routine on the identity (index + 1; 0 stays "padding")
-		static_assert(kDensityW + 64 * 48 + 2 * 64 * 64 + 16 * 64 < kFragNegate, "weight indices + 1 fit 15 bits");
-		std::vector<uint16_t> ident(n_mlp), canon(kCanonW), src(kWfragDeviceBytes / 2);
-		for (size_t i = 0; i < ident.size(); ++i) ident[i] = (uint16_t)(i + 1);
-		lower_weights(m->desc, ident.data(), canon.data(), kLowerIndices, m->n_extra_dims);
-		make_weight_fragments(canon.data(), src.data(), kFragOne);
-		DeviceBuffer<uint16_t> fresh;
-		HIP_TRY(fresh.alloc(kWfragDeviceBytes / 2));
-		const hipError_t up = hipMemcpy(fresh.get(), src.data(), kWfragDeviceBytes, hipMemcpyHostToDevice);
-		if (up != hipSuccess) return fail_hip(up, "nrs_model_set_params_device: upload of the weight permutation");
-		m->d_wfrag_src = std::move(fresh); // (never keep a permutation that was not uploaded: later calls would scramble the weights silently)
-	}
-	NRS_LAUNCH(launch_weight_fragments(d, m->d_wfrag_src.get(), (uint16_t*)m->d_wfrag.get(), kWfragDeviceBytes / 2, stream));
-	HIP_TRY(hipMemcpyAsync(m->d_grid.get(), d + n_mlp, (size_t)m->total_entries * 4, hipMemcpyDeviceToDevice, s));
-	m->have_params = true;
-	return rebuild_cell_cache(m, stream, false);
+	NRS_TRY(model_mlp_from_device(m, d, stream));
+	HIP_TRY(hipMemcpyAsync(m->d_grid.get(), d + n_mlp, (size_t)m->total_entries * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+	return model_grid_written(m, stream);
 }
 int nrs_model_set_numerics(nrs_model* m, uint32_t grid_acc, uint32_t mlp_acc) {
 	if (!m) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_numerics: NULL model");

@@ -1,4 +1,4 @@
-// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
+// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, optimiser), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
 // work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp, nrs_api_selection.cpp) includes
 // this header alone.  Host-only C++17: no .hip / .cuh includes it.
 #pragma once
@@ -206,4 +206,21 @@ struct nrs_selection {
 	int device = -1;                    // of the buffers below, once a device call has allocated them
 	nrs::DeviceBuffer<uint32_t> d_work; // [3][kMorphLevelWords]: the growing level in Morton order | two levels of rows
 	nrs::DeviceBuffer<float> d_lattice; // [128^3]
+};
+
+// The optimiser's state (nrs_api_optimizer.cpp, nrs_optimizer.hip): every array in the blob's order, n elements.
+struct nrs_optimizer {
+	nrs_ctx* ctx = nullptr;
+	nrs_model* model = nullptr;         // bound: the fp16 of the hash table is the model's resident table, d_fp16 holds the MLP weights only
+	nrs_adam_params p{};
+	uint32_t n = 0, n_matrix = 0;
+	uint32_t split = 0;                 // elements of d_fp16: n when unbound, the number of MLP weights when bound
+	nrs::DeviceBuffer<float> d_master, d_m, d_v, d_ema;
+	nrs::DeviceBuffer<uint32_t> d_steps;
+	nrs::DeviceBuffer<uint16_t> d_fp16;
+	nrs::DeviceBuffer<float> d_table;   // [t_sat + 1]: bias(t) at index t
+	uint32_t t_sat = 0;
+	uint32_t step_count = 0;
+	uint32_t variant = 0;               // NRS_OPTIMIZER_VARIANT at creation (measurements: nrs_optimizer.h)
+	bool have_weights = false;
 };
