@@ -33,6 +33,9 @@
  *   nrs_tonemap              <- CudaRenderBuffer::tonemap / tonemap_kernel                                         src/render_buffer.cu:562 / :471
  *   nrs_detile               <- (new) inverse of the multi-GPU tile packing, no reference counterpart
  *   nrs_mesh_extract / nrs_mesh_from_density / nrs_mesh_write <- Testbed::marching_cubes src/testbed_nerf.cu:4614, marching_cubes_gpu / save_mesh src/marching_cubes.cu:730 / :760
+ *   nrs_dataset_rays         <- generate_training_samples_nerf up to the ray   src/testbed_nerf.cu:1087-1186, and the target / background look-ups of :1777-1806
+ *   nrs_dataset_set_image    <- from_rgba32 / from_fullp                       common_device.cuh:513, src/nerf_loader.cu:62
+ *   nrs_dataset_mark_untrained <- mark_untrained_density_grid                  src/testbed_nerf.cu:353
  *
  * Conventions: every function returns NRS_OK (0) or a negative nrs_status; nrs_last_error() returns a
  * thread-local message.  All buffers named d_* are DEVICE pointers owned by the caller; h_* are HOST
@@ -835,7 +838,8 @@ int  nrs_selection_fine_mesh(nrs_ctx* ctx, void* stream, nrs_selection* sel, int
 /* ---- training rays: sample generation, the ray loss and its gradient ---------------------------------------------------------------------------- */
 /* The two steps between "rays + the colours they should have" and nrs_network_backward: generate_training_samples_nerf (src/testbed_nerf.cu:1087, from :1188 on: everything
  * after the ray exists) and compute_loss_kernel_train_nerf (:1685-1985) with the seven losses of :103-171.  Callers detect these entry points by symbol (dlsym);
- * NRS_ABI_VERSION is unchanged because no existing layout changes.  Not here: the dataset (image / pixel selection, lens distortion, rolling shutter), the envmap and its
+ * NRS_ABI_VERSION is unchanged because no existing layout changes.  The rays themselves -- image / pixel selection, lens distortion, rolling shutter -- come from a
+ * dataset (nrs_dataset_rays, below) or from the caller.  Not here: the envmap and its
  * gradient, exposure and its gradient, the error map and sharpness, max_level_rand_training, image / pixel PDFs (img_pdf = xy_pdf = 1), fill_rollover_and_rescale
  * (nrs_network_backward takes any n), the camera-gradient kernels, the distill variants, light-direction models.
  *
@@ -981,6 +985,86 @@ int      nrs_optimizer_export_fp16(nrs_optimizer* opt, int which, void* d_out_fp
 uint32_t nrs_optimizer_step_count(const nrs_optimizer* opt);
 int      nrs_optimizer_set_step_count(nrs_optimizer* opt, uint32_t steps);
 size_t   nrs_optimizer_n_params(const nrs_optimizer* opt, size_t* n_matrix);
+
+/* ---- the dataset: posed images on the device, pixel rays and their targets ------------------------------------------------------------------------- */
+/* What stands in front of nrs_training_samples: the first half of generate_training_samples_nerf (src/testbed_nerf.cu:1087-1186: image and pixel selection, the camera
+ * of the pixel's time, lens distortion), the look-ups compute_loss_kernel_train_nerf repeats for a ray's target and background (:1777-1806), the loader's image
+ * conversion (from_rgba32, common_device.cuh:513-540; from_fullp, src/nerf_loader.cu:62) and mark_untrained_density_grid (:353-400).  Callers detect these entry
+ * points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  Not here: the error-map CDFs (cdf_img, cdf_x_cond_y: the `cdf == nullptr`
+ * branches are the ones built), explicit per-pixel rays (rays_in), the trainable per-pixel distortion map, the envmap and exposure, light directions (a dataset serves
+ * n_extra_dims == 0 models), sharpening and the sharpness map, EXR, the adaptive rays_per_batch of train_nerf (it reads counters back), decoding image files (the
+ * Python package does that).
+ *
+ * A dataset owns n_images images of one resolution, stored as the reference stores them (NerfDataset::images_data): fp16 RGBA, linear, premultiplied, 8 bytes per pixel,
+ * image after image, rows top to bottom -- a ray reads its pixel in one 64-bit load -- and one camera record per image.  A dataset is used from one host thread and its
+ * calls on ONE stream at a time (the staging buffer of host pixels and the camera block are the dataset's own).
+ *
+ * nrs_dataset_set_image: `pixels` is width x height pixels of `format`, a host pointer or (is_device_pointer != 0) a device pointer; asynchronous on `stream` for device
+ *   pixels, host pixels have been read when it returns (they travel through a staging buffer of the dataset, allocated once).
+ *   NRS_IMAGE_RGBA8_SRGB  <- from_rgba32<__half>: alpha = a * (1 / 255), colour = srgb_to_linear(c * (1 / 255)) * alpha with srgb_to_linear(s) = s / 12.92 for
+ *     s <= 0.04045, else powf((s + 0.055) / 1.055, 2.4), rounded to fp16 once.  NRS_IMAGE_WHITE_TRANSPARENT / _BLACK_TRANSPARENT: a pixel whose colour bytes are all 255 /
+ *     all 0 gets alpha 0.  A pixel whose four bytes, read as a little-endian word, equal a non-zero mask_color becomes (-1, -1, -1, -1): masked away.
+ *   NRS_IMAGE_RGBA32F_LINEAR <- from_fullp: each float rounded to fp16 (flags and mask_color are ignored).  NRS_IMAGE_RGBA16F_LINEAR: copied as it is.
+ * nrs_dataset_get_image: image `index` as the dataset holds it, width x height x 4 halves to the host; synchronous (it waits for the device first).  For tests and checkpoints.
+ *   NRS_ERR_STATE while that image has never been set.
+ * nrs_dataset_set_camera: xform_start / xform_end are 3 x 4 column-major like nrs_render_params::camera_matrix0 (the camera at pixel time 0 / 1), focal_length in pixels,
+ *   principal_point in [0, 1]^2 (screen_center), rolling_shutter, distortion_mode (0 none, 1 iterative, 2 f-theta) and distortion_params as in nrs_render_params.  The
+ *   records stay on the host until a device call needs them and then travel in one block (that call waits for the copy).
+ *
+ * nrs_dataset_rays: one thread per ray i, outputs in input order, in the reference's order and float32 expressions:
+ *   img = (((i + n_rays_total) * n_images) / n_rays) % n_images in 32-bit unsigned arithmetic (image_idx, :1072; the product wraps as the reference's does);
+ *   the generator pcg32 (rng_state, rng_inc: nrs_rng_seed) advanced by 8 i (N_MAX_RANDOM_SAMPLES_PER_RAY); draws 0 and 1 are xy, draw 2 motionblur_time, draw 3 the
+ *   jitter; the background is draws 2, 3 and 4 -- what the loss kernel gets when it re-seeds and draws three floats behind xy (:1780-1791; max_level_rand_training is off
+ *   everywhere in this library);  snap_to_pixel_centers as :1047;  the pixel is image_pos (:1075: multiply, truncate, clamp);  target_rgba = the pixel's four halves as
+ *   float (read_rgba);  the camera is start + (end - start) * pixel_t, pixel_t = rs.x + rs.y u + rs.z v + rs.w motionblur_time (get_xform_given_rolling_shutter,
+ *   common_device.cuh:226 -- NOT the render path's blend);  the direction is :1169-1185: f_theta_undistortion with error direction (0, 0, 1), or
+ *   ((xy - pp) * res / focal, 1) with iterative_camera_undistortion in mode 1, then xform.block<3, 3>(0, 0) * d, normalised.
+ *   A masked pixel (first channel < 0, :1127) makes a DEAD ray: direction (0, 0, 0), origin the camera's, target 0; jitter, background and pixel are written as for any
+ *   ray.  nrs_training_samples gives such a ray no samples (its length guard), so it is never emitted and never gathered.
+ *   Outputs: d_rays [n x 6] f32, d_jitter [n] f32, d_target_rgba [n x 4] f32, d_background [n x 3] f32 (sRGB-encoded, as nrs_ray_loss expects it; written only when
+ *   random_bg_color, NULL allowed otherwise), d_pixels [n x 2] u32 (img, x + y * width) or NULL.  Two calls with the same inputs give bit-identical outputs.
+ * nrs_dataset_mark_untrained <- mark_untrained_density_grid on the model's float density grid, all five cascades: a cell that no camera sees (the start transform, the
+ *   frustum test widened by the voxel radius; an f-theta camera counts as "sees everything") gets -1, a seen cell gets 0 under the reference's condition
+ *   (clear_visible_voxels, or the cell's sign disagrees with what was found); then mean, bitfield and mips are rebuilt as nrs_model_set_density_grid rebuilds them
+ *   (the call waits for the stream there, like every bitfield rebuild).  nrs_model_update_density_grid keeps negative cells negative.
+ * nrs_rng_advance (host only): pcg32's skip-ahead, *state moved by `delta` steps of the generator (state, inc).  The reference advances m_rng once per training step
+ *   (src/testbed_nerf.cu:4435) by tiny-cuda-nn's default delta, which is not in the reference tree: NRS_RNG_STEP_DELTA = 2^32 is the value used here (pcg32::advance's
+ *   default argument as recalled from tiny-cuda-nn's pcg32.h; the occupancy refresh already steps by it).
+ *
+ * Refused before any HIP call, NRS_ERR_INVALID_ARG: NULL handles or outputs; an index past n_images; a zero resolution or n_images == 0; an unknown format or distortion
+ *   mode; a wrong struct_size; a non-finite camera entry or a focal length that is not positive; n_rays > 2^21 (the generator's own limit); a dataset and a model of
+ *   different contexts.  NRS_ERR_STATE: nrs_dataset_rays or nrs_dataset_mark_untrained while an image or a camera has never been set.  n_rays == 0 is NRS_OK. */
+typedef struct nrs_dataset nrs_dataset;
+typedef enum nrs_image_format { NRS_IMAGE_RGBA8_SRGB = 0, NRS_IMAGE_RGBA32F_LINEAR = 1, NRS_IMAGE_RGBA16F_LINEAR = 2 } nrs_image_format;
+#define NRS_IMAGE_WHITE_TRANSPARENT 1u
+#define NRS_IMAGE_BLACK_TRANSPARENT 2u
+#define NRS_RNG_STEP_DELTA (1ull << 32)
+typedef struct nrs_training_camera {
+	uint32_t struct_size;          /* refused unless == sizeof(nrs_training_camera) */
+	float    xform_start[12];      /* TrainingXForm::start, column-major 3 x 4 */
+	float    xform_end[12];        /* TrainingXForm::end */
+	float    focal_length[2];      /* pixels */
+	float    principal_point[2];   /* fraction of the image */
+	float    rolling_shutter[4];
+	uint32_t distortion_mode;      /* 0 none, 1 iterative (k1 k2 p1 p2), 2 f-theta (p0..p4, w, h) */
+	float    distortion_params[7];
+} nrs_training_camera;
+typedef struct nrs_dataset_rays_params {
+	uint32_t struct_size;          /* refused unless == sizeof(nrs_dataset_rays_params) */
+	uint32_t n_rays_total;         /* rays generated by the steps before this one (m_nerf.training.n_rays_total) */
+	uint64_t rng_state, rng_inc;   /* m_rng for this step */
+	uint32_t snap_to_pixel_centers;
+	uint32_t random_bg_color;
+} nrs_dataset_rays_params;
+int  nrs_dataset_create(nrs_ctx* ctx, uint32_t n_images, uint32_t width, uint32_t height, nrs_dataset** out);
+void nrs_dataset_destroy(nrs_dataset* ds);
+int  nrs_dataset_set_image(nrs_dataset* ds, uint32_t index, int format, const void* pixels, int is_device_pointer, uint32_t flags, uint32_t mask_color, void* stream);
+int  nrs_dataset_set_camera(nrs_dataset* ds, uint32_t index, const nrs_training_camera* camera);
+int  nrs_dataset_get_image(nrs_dataset* ds, uint32_t index, void* h_out_fp16);
+int  nrs_dataset_rays(nrs_dataset* ds, void* stream, const nrs_dataset_rays_params* params, uint32_t n_rays, float* d_rays, float* d_jitter, float* d_target_rgba,
+                      float* d_background, uint32_t* d_pixels);
+int  nrs_dataset_mark_untrained(nrs_model* model, nrs_dataset* ds, int clear_visible_voxels, void* stream);
+void nrs_rng_advance(uint64_t* state, uint64_t inc, uint64_t delta);
 
 #ifdef __cplusplus
 }

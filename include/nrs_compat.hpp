@@ -174,6 +174,42 @@ private:
 	bool m_zero_grad = true;
 };
 
+// NerfDataset on the device (nerf_loader.h: images_data, xforms, metadata) with the front half of generate_training_samples_nerf.  A thin owner of the handle: images arrive
+// decoded (the loader and its file formats stay with the caller).
+class Dataset {
+public:
+	Dataset(Context& ctx, uint32_t n_images, uint32_t width, uint32_t height) { check(nrs_dataset_create(ctx.get(), n_images, width, height, &m_ds), "nrs_dataset_create"); }
+	~Dataset() { nrs_dataset_destroy(m_ds); }
+	Dataset(const Dataset&) = delete;
+	Dataset& operator=(const Dataset&) = delete;
+
+	static nrs_training_camera camera() { // identity transforms, principal point in the centre, no distortion: fill in the rest
+		nrs_training_camera c{};
+		c.struct_size = (uint32_t)sizeof(nrs_training_camera);
+		c.xform_start[0] = c.xform_start[4] = c.xform_start[8] = c.xform_end[0] = c.xform_end[4] = c.xform_end[8] = 1.f;
+		c.principal_point[0] = c.principal_point[1] = 0.5f;
+		return c;
+	}
+	void set_image(uint32_t index, nrs_image_format format, const void* pixels, bool on_device, void* stream, uint32_t flags = 0, uint32_t mask_color = 0) {
+		check(nrs_dataset_set_image(m_ds, index, format, pixels, on_device ? 1 : 0, flags, mask_color, stream), "nrs_dataset_set_image");
+	}
+	void get_image(uint32_t index, void* h_out_fp16) { check(nrs_dataset_get_image(m_ds, index, h_out_fp16), "nrs_dataset_get_image"); }
+	void set_camera(uint32_t index, const nrs_training_camera& camera) { check(nrs_dataset_set_camera(m_ds, index, &camera), "nrs_dataset_set_camera"); }
+	// the rays of one training step: m_rng's (state, inc), the rays of the steps before; d_background may be NULL without random_bg_color, d_pixels always
+	void rays(void* stream, uint32_t n_rays, uint32_t n_rays_total, uint64_t rng_state, uint64_t rng_inc, float* d_rays, float* d_jitter, float* d_target_rgba,
+	          float* d_background, uint32_t* d_pixels = nullptr, bool snap_to_pixel_centers = true, bool random_bg_color = true) {
+		const nrs_dataset_rays_params p{(uint32_t)sizeof(nrs_dataset_rays_params), n_rays_total, rng_state, rng_inc, snap_to_pixel_centers ? 1u : 0u, random_bg_color ? 1u : 0u};
+		check(nrs_dataset_rays(m_ds, stream, &p, n_rays, d_rays, d_jitter, d_target_rgba, d_background, d_pixels), "nrs_dataset_rays");
+	}
+	void mark_untrained(NerfNetwork& network, bool clear_visible_voxels, void* stream) {
+		check(nrs_dataset_mark_untrained(network.get(), m_ds, clear_visible_voxels ? 1 : 0, stream), "nrs_dataset_mark_untrained");
+	}
+	nrs_dataset* get() const { return m_ds; }
+
+private:
+	nrs_dataset* m_ds = nullptr;
+};
+
 // EditOperator (edit_operator.h:43-91): the interface NerfTracer::m_edit_operators holds (testbed.h:237) -- cage deformations and affine
 // duplications alike.  An operator owns its device tables.
 class EditOperator {

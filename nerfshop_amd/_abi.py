@@ -202,6 +202,29 @@ class AdamParams(C.Structure):
             setattr(self, k, v)
 
 
+class TrainingCamera(C.Structure):
+    """nrs_training_camera; struct_size is filled in on construction.  Matrices are 3 x 4 column-major like RenderParams.camera_matrix0."""
+    _fields_ = [("struct_size", C.c_uint32), ("xform_start", C.c_float * 12), ("xform_end", C.c_float * 12), ("focal_length", C.c_float * 2),
+                ("principal_point", C.c_float * 2), ("rolling_shutter", C.c_float * 4), ("distortion_mode", C.c_uint32), ("distortion_params", C.c_float * 7)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(TrainingCamera)
+
+
+class DatasetRaysParams(C.Structure):
+    """nrs_dataset_rays_params; struct_size is filled in on construction."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays_total", C.c_uint32), ("rng_state", C.c_uint64), ("rng_inc", C.c_uint64), ("snap_to_pixel_centers", C.c_uint32),
+                ("random_bg_color", C.c_uint32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(DatasetRaysParams)
+
+
+IMAGE_RGBA8_SRGB, IMAGE_RGBA32F_LINEAR, IMAGE_RGBA16F_LINEAR = 0, 1, 2  # nrs_image_format
+IMAGE_WHITE_TRANSPARENT, IMAGE_BLACK_TRANSPARENT = 1, 2  # NRS_IMAGE_WHITE_TRANSPARENT / _BLACK_TRANSPARENT
+RNG_STEP_DELTA = 1 << 32  # NRS_RNG_STEP_DELTA
 OPT_MASTER, OPT_M, OPT_V, OPT_STEPS, OPT_EMA, OPT_PARAMS_FP16 = range(6)  # nrs_optimizer_state
 OPT_EXPORT_WEIGHTS, OPT_EXPORT_EMA = 0, 1  # nrs_optimizer_export
 # the schedule of configs/nerf/base.json: ExponentialDecay(decay_start, decay_interval, decay_base) over a learning rate of 1e-2
@@ -240,6 +263,7 @@ EXPORTS = [
     "nrs_adam_bias_table", "nrs_exponential_decay_lr", "nrs_optimizer_create", "nrs_optimizer_create_for_model", "nrs_optimizer_destroy", "nrs_optimizer_set_weights",
     "nrs_optimizer_step", "nrs_optimizer_get_state", "nrs_optimizer_set_state", "nrs_optimizer_export_fp16", "nrs_optimizer_step_count", "nrs_optimizer_set_step_count",
     "nrs_optimizer_n_params",
+    "nrs_dataset_create", "nrs_dataset_destroy", "nrs_dataset_set_image", "nrs_dataset_set_camera", "nrs_dataset_get_image", "nrs_dataset_rays", "nrs_dataset_mark_untrained", "nrs_rng_advance",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -348,6 +372,17 @@ def load():
         lib.nrs_optimizer_set_step_count.argtypes = [P, U32]
         lib.nrs_optimizer_n_params.argtypes = [P, C.POINTER(C.c_size_t)]
         lib.nrs_optimizer_n_params.restype = C.c_size_t
+    if hasattr(lib, "nrs_dataset_rays"):  # (detected by symbol, like nrs_network_backward)
+        lib.nrs_dataset_create.argtypes = [P, U32, U32, U32, C.POINTER(P)]
+        lib.nrs_dataset_destroy.argtypes = [P]
+        lib.nrs_dataset_destroy.restype = None
+        lib.nrs_dataset_set_image.argtypes = [P, U32, I, P, I, U32, U32, P]
+        lib.nrs_dataset_set_camera.argtypes = [P, U32, C.POINTER(TrainingCamera)]
+        lib.nrs_dataset_get_image.argtypes = [P, U32, P]
+        lib.nrs_dataset_rays.argtypes = [P, P, C.POINTER(DatasetRaysParams), U32, P, P, P, P, P]
+        lib.nrs_dataset_mark_untrained.argtypes = [P, P, I, P]
+        lib.nrs_rng_advance.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64]
+        lib.nrs_rng_advance.restype = None
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

@@ -36,6 +36,15 @@ DeviceModel nrs::model_for_launch(const nrs_model* m, const nrs_render_params& p
 	dm.occ = (p.cone_angle_constant == 0.f && p.min_mip == 0) ? m->accel_exact : m->accel_any;
 	return dm;
 }
+// bitfield + mips from m->d_density_grid, then the marching shortcut's bounds and masks (all on the device; synchronises for 96 bytes)
+int nrs::model_refresh_bitfield(nrs_model* m, void* stream) {
+	hipStream_t s = (hipStream_t)stream;
+	HIP_TRY(hipMemsetAsync(m->d_bitfield.get(), 0, NRS_BITFIELD_BYTES, s));
+	NRS_LAUNCH(launch_grid_to_bitfield(m->d_density_grid.get(), m->d_bitfield.get(), m->ctx->d_mean.get(), stream));
+	NRS_TRY(refresh_accel(m, stream));
+	m->have_bitfield = true;
+	return NRS_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" {
@@ -350,21 +359,12 @@ int nrs_model_set_density_bitfield(nrs_model* m, const uint8_t* h_bitfield, size
 	m->have_bitfield = true;
 	return NRS_OK;
 }
-// bitfield + mips from m->d_density_grid, then the marching shortcut's bounds and masks (all on the device; synchronises for 96 bytes)
-static int refresh_bitfield(nrs_model* m, void* stream) {
-	hipStream_t s = (hipStream_t)stream;
-	HIP_TRY(hipMemsetAsync(m->d_bitfield.get(), 0, NRS_BITFIELD_BYTES, s));
-	NRS_LAUNCH(launch_grid_to_bitfield(m->d_density_grid.get(), m->d_bitfield.get(), m->ctx->d_mean.get(), stream));
-	NRS_TRY(refresh_accel(m, stream));
-	m->have_bitfield = true;
-	return NRS_OK;
-}
 int nrs_model_set_density_grid(nrs_model* m, const float* h_grid, size_t n_floats) {
 	if (!m || !h_grid) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_density_grid: NULL argument");
 	if (n_floats != (size_t)kGridVol * kCascades) return fail(NRS_ERR_INVALID_ARG, "nrs_model_set_density_grid: expected 5*128^3 floats");
 	HIP_TRY(hipSetDevice(m->ctx->device));
 	HIP_TRY(hipMemcpy(m->d_density_grid.get(), h_grid, n_floats * 4, hipMemcpyHostToDevice));
-	return refresh_bitfield(m, nullptr);
+	return model_refresh_bitfield(m, nullptr);
 }
 int nrs_model_get_density_grid(nrs_model* m, float* h_out, size_t n_floats) {
 	if (!m || !h_out || n_floats != (size_t)kGridVol * kCascades) return fail(NRS_ERR_INVALID_ARG, "nrs_model_get_density_grid: bad argument");
@@ -373,7 +373,7 @@ int nrs_model_get_density_grid(nrs_model* m, float* h_out, size_t n_floats) {
 	return NRS_OK;
 }
 
-// tcnn::pcg32 on the host: only seeding and the skip-ahead the refresh needs
+// tcnn::pcg32 on the host: only seeding and the skip-ahead (the refresh's two draws, a training step's advance)
 static const uint64_t kPcgMult = 0x5851f42d4c957f2dULL;
 static uint64_t pcg_advance(uint64_t state, uint64_t inc, uint64_t delta) {
 	uint64_t cur_mult = kPcgMult, cur_plus = inc, acc_mult = 1u, acc_plus = 0u;
@@ -384,6 +384,9 @@ static uint64_t pcg_advance(uint64_t state, uint64_t inc, uint64_t delta) {
 		delta >>= 1;
 	}
 	return acc_mult * state + acc_plus;
+}
+void nrs_rng_advance(uint64_t* state, uint64_t inc, uint64_t delta) {
+	if (state) *state = pcg_advance(*state, inc, delta);
 }
 void nrs_rng_seed(uint64_t seed, uint64_t* state_out, uint64_t* inc_out) {
 	const uint64_t inc = (1u << 1u) | 1u; // initseq = 1
@@ -424,7 +427,7 @@ int nrs_model_update_density_grid(nrs_model* m, nrs_edit* const* edits, int n_ed
 	NRS_LAUNCH(launch_grid_update(m->dm, d_refresh_edits, n_edits, *u, rng_nonuniform, m->d_density_grid.get(), m->d_density_tmp.get(), ctx->n_cus, stream));
 	u->rng_state = pcg_advance(u->rng_state, u->rng_inc, 2ull << 32);
 	u->ema_step += 1;
-	return refresh_bitfield(m, stream);
+	return model_refresh_bitfield(m, stream);
 }
 int nrs_model_get_march_accelerator(nrs_model* m, int which, float* h_box12, uint32_t* h_mask) {
 	if (!m || !h_box12 || !h_mask || which < 0 || which > 1) return fail(NRS_ERR_INVALID_ARG, "nrs_model_get_march_accelerator: bad argument");

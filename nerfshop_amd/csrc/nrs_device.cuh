@@ -264,6 +264,20 @@ __device__ __forceinline__ void iterative_camera_undistortion(const float* prm, 
 	}
 	u = x0; v = x1;
 }
+// f_theta_undistortion (common_device.cuh:231-243): the direction through (uvx, uvy) of an f-theta lens with screen centre (cx, cy) -- the params are r0..r4, width, height --
+// into `dir`; false where the reference returns its error direction (the caller's: the render path and the dataset's rays name different ones), `dir` untouched.
+template <typename P>
+__device__ __forceinline__ bool f_theta_undistortion(P prm, float uvx, float uvy, float cx, float cy, f3& dir) {
+	const float xpix = (uvx - cx) * prm[5], ypix = (uvy - cy) * prm[6];
+	const float norm = sqrtf(xpix * xpix + ypix * ypix);
+	const float alpha = prm[0] + norm * (prm[1] + norm * (prm[2] + norm * (prm[3] + norm * prm[4])));
+	float sin_alpha, cos_alpha;
+	sincosf(alpha, &sin_alpha, &cos_alpha);
+	if (cos_alpha <= 1.17549435e-38f || norm == 0.f) return false;
+	sin_alpha *= 1.f / norm;
+	dir = {sin_alpha * xpix, sin_alpha * ypix, cos_alpha};
+	return true;
+}
 // read_image<2> (common_device.cuh:80-110): bilinear, texels clamped
 __device__ __forceinline__ void read_image2(const float* __restrict__ data, const int32_t* res, float px, float py, float& o0, float& o1) {
 	const float fx = px * (float)(res[0] - 1), fy = py * (float)(res[1] - 1);
@@ -335,19 +349,11 @@ __device__ __forceinline__ void pixel_ray_raw(const nrs_render_params& p, uint32
 	float uvx = ((float)x + off_x) / W;
 	float uvy = ((float)y + off_y) / H;
 	f3 dir = {(uvx - p.screen_center[0]) * W / (viewed ? v_focal_x : p.focal_length[0]), (uvy - p.screen_center[1]) * H / (viewed ? v_focal_y : p.focal_length[1]), 1.0f};
-	if (LENS && p.distortion_mode == 2u) { // FTheta, common_device.cuh:231-243, :263-267
-		const float* prm = p.distortion_params;
-		const float xpix = (uvx - p.screen_center[0]) * prm[5], ypix = (uvy - p.screen_center[1]) * prm[6];
-		const float norm = sqrtf(xpix * xpix + ypix * ypix);
-		const float alpha = prm[0] + norm * (prm[1] + norm * (prm[2] + norm * (prm[3] + norm * prm[4])));
-		float sin_alpha, cos_alpha;
-		sincosf(alpha, &sin_alpha, &cos_alpha);
-		if (cos_alpha <= 1.17549435e-38f || norm == 0.f) { // the error direction: a point outside the aabb so that the pixel is not rendered
+	if (LENS && p.distortion_mode == 2u) { // FTheta, :263-267
+		if (!f_theta_undistortion(p.distortion_params, uvx, uvy, p.screen_center[0], p.screen_center[1], dir)) { // the error direction: a point outside the aabb so that the pixel is not rendered
 			o = mk3(1000.f, 0.f, 0.f); d = mk3(0.f, 0.f, 1.f);
 			return;
 		}
-		sin_alpha *= 1.f / norm;
-		dir = {sin_alpha * xpix, sin_alpha * ypix, cos_alpha};
 	} else if (LENS && p.distortion_mode == 1u) {
 		iterative_camera_undistortion(p.distortion_params, dir.x, dir.y);
 	}

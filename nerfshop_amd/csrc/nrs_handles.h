@@ -1,4 +1,4 @@
-// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, optimiser), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
+// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, dataset, optimiser), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
 // work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp, nrs_api_selection.cpp) includes
 // this header alone.  Host-only C++17: no .hip / .cuh includes it.
 #pragma once
@@ -80,6 +80,8 @@ private:
 // marching_cubes_gpu + compute_mesh_1ring on a lattice that is already on the device (nrs_api_mesh.cpp; the arguments have been checked); `fn` names the caller in messages
 int mesh_from_lattice(int device, void* stream, const uint32_t res3d[3], const float aabb_min[3], const float aabb_max[3], float thresh, const float* d_density,
                       nrs_mesh** mesh_out, const char* fn);
+// mean, bitfield, mips and the marching accelerator from m->d_density_grid (nrs_api_model.cpp; waits for `stream`): what follows every change of the density grid
+int model_refresh_bitfield(nrs_model* m, void* stream);
 
 } // namespace nrs
 
@@ -206,6 +208,19 @@ struct nrs_selection {
 	int device = -1;                    // of the buffers below, once a device call has allocated them
 	nrs::DeviceBuffer<uint32_t> d_work; // [3][kMorphLevelWords]: the growing level in Morton order | two levels of rows
 	nrs::DeviceBuffer<float> d_lattice; // [128^3]
+};
+
+// Posed images on the device (nrs_api_dataset.cpp, nrs_dataset.hip)
+struct nrs_dataset {
+	nrs_ctx* ctx = nullptr;
+	uint32_t n_images = 0, width = 0, height = 0;
+	nrs::DeviceBuffer<uint64_t> d_images;  // [n_images][height][width] fp16 RGBA, linear, premultiplied (NerfDataset::images_data)
+	nrs::DeviceBuffer<float> d_cameras;    // [n_images][kCameraWords]
+	nrs::DeviceBuffer<uint8_t> d_staging;  // one image of host pixels on its way to the conversion kernel, allocated by the first such image
+	std::vector<float> cameras;            // what d_cameras holds once cameras_dirty is cleared
+	std::vector<uint8_t> image_set, camera_set;
+	uint32_t n_images_set = 0, n_cameras_set = 0;
+	bool cameras_dirty = false;
 };
 
 // The optimiser's state (nrs_api_optimizer.cpp, nrs_optimizer.hip): every array in the blob's order, n elements.

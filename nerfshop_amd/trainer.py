@@ -7,6 +7,11 @@
         loss = trainer.step(rays, target_rgba)          # rays [n, 6] f32 (origin, unit direction), target_rgba [n, 4] f32 linear premultiplied; CUDA tensors
     ema_blob = trainer.optimizer.export_fp16(_abi.OPT_EXPORT_EMA)                 # what a second NerfNetwork renders with (set_params_device)
 
+or, from posed images (a transforms.json folder):
+
+    ds = dataset.load_transforms("data/nerf/fox").to_device(ctx)                  # runtime.Dataset
+    losses = trainer.fit(ds, n_steps=1000)                                        # mark_untrained + grid updates every 16 steps + step_dataset
+
 Everything in `step` is enqueued on the current stream and nothing is read back: the loss comes back as a 0-d tensor on the device.  The optimiser is
 configs/nerf/base.json's -- Ema(0.95) over ExponentialDecay(20000, 10000, 0.33) over Adam(1e-2, 0.9, 0.99, 1e-15, l2_reg 1e-6) -- and writes the network's parameters
 in place (runtime.Optimizer bound to the network), so no set_params call and no gradient memset sits between two steps.
@@ -45,6 +50,7 @@ class Trainer:
         self.loss_params.max_samples_compacted = self.max_samples
         self.learning_rate, self.decay = float(learning_rate), tuple(decay)
         self.training_step = 0
+        self.n_rays_total = 0  # m_nerf.training.n_rays_total: rays drawn from a dataset so far (step_dataset)
         self._out16 = torch.empty((self.max_samples, 16), dtype=torch.float16, device=dev)
         self._loss_bufs = None
         self._grid_update = _abi.GridUpdate()
@@ -102,3 +108,28 @@ class Trainer:
         self.optimizer.step(self.grad, loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate(), zero_grad=True)
         self.training_step += 1
         return loss.sum()
+
+    def step_dataset(self, dataset, n_rays=4096, snap=True, random_bg=True):
+        """One training step on n_rays pixels of a runtime.Dataset: dataset.rays (image and pixel selection, the pixel's camera, lens distortion; the target colour and
+        the random background the loss composites behind it) -> step().  The generator is the trainer's m_rng (the one update_density_grid draws from), advanced once per
+        step by NRS_RNG_STEP_DELTA as the reference advances it (src/testbed_nerf.cu:4435); n_rays_total counts the rays of the steps before.  snap and random_bg
+        default to the reference's Testbed initialisers (include/neural-graphics-primitives/testbed.h:584 and :581).  Like step, nothing waits for the device."""
+        u = self._grid_update
+        rays, jitter, target, background, _ = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg, want_pixels=False)
+        loss = self.step(rays, target, jitter=jitter, background=background)
+        self.n_rays_total = (self.n_rays_total + int(n_rays)) & 0xffffffff
+        u.rng_state = runtime.rng_advance(u.rng_state, u.rng_inc)
+        return loss
+
+    def fit(self, dataset, n_steps, n_rays=4096, grid_every=16, snap=True, random_bg=True):
+        """Train on a runtime.Dataset for n_steps steps.  At training step 0 the cells no camera sees are marked untrained (mark_untrained_density_grid with
+        clear_visible_voxels, src/testbed_nerf.cu:3452-3465) in front of the first grid update; the grid is updated every grid_every steps (the reference's cadence: 16).
+        Returns the losses, 0-d CUDA tensors."""
+        losses = []
+        for _ in range(int(n_steps)):
+            if self.training_step == 0:
+                dataset.mark_untrained(self.network, clear_visible=True)
+            if self.training_step % int(grid_every) == 0:
+                self.update_density_grid()
+            losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg))
+        return losses
