@@ -334,7 +334,7 @@ int nrs_mesh_extract(nrs_model* model, void* stream, const uint32_t res3d[3], co
 	DeviceBuffer<float> d_density;
 	hipError_t he = d_density.alloc((size_t)res[0] * res[1] * res[2]);
 	if (he != hipSuccess) return fail_hip(he, "nrs_mesh_extract: device allocation (lattice)");
-	NRS_LAUNCH(launch_grid_eval(model->dm, 0, res, aabb_min, aabb_max, nullptr, mask_with_density_grid ? model->d_density_grid.get() : nullptr, d_density.get(), model->ctx->n_cus,
+	NRS_LAUNCH(launch_grid_eval(model->dm, kGridDensity, res, aabb_min, aabb_max, nullptr, mask_with_density_grid ? model->d_density_grid.get() : nullptr, d_density.get(), model->ctx->n_cus,
 	                            stream));
 	std::unique_ptr<nrs_mesh> mesh;
 	NRS_TRY(build_mesh(model->ctx->device, stream, res, aabb_min, aabb_max, thresh, d_density.get(), mesh, "nrs_mesh_extract"));
@@ -349,7 +349,7 @@ int nrs_mesh_extract(nrs_model* model, void* stream, const uint32_t res3d[3], co
 	mesh->has_colors = true;
 	if (np) {
 		NRS_LAUNCH(launch_mesh_color_inputs(np, mesh->d_verts.get(), model->dm.aabb, d_coords.get(), stream));
-		NRS_LAUNCH(launch_network(model->dm, 0, np, d_coords.get(), NRS_NETWORK_INPUT_FLOATS, d_net.get(), NRS_NETWORK_OUTPUT_WIDTH, NRS_INTERLEAVED, model->ctx->n_cus, stream));
+		NRS_LAUNCH(launch_network(model->dm, kNetInference, np, d_coords.get(), NRS_NETWORK_INPUT_FLOATS, d_net.get(), NRS_NETWORK_OUTPUT_WIDTH, NRS_INTERLEAVED, model->ctx->n_cus, stream));
 		NRS_LAUNCH(launch_mesh_colors(np, d_net.get(), model->dm.rgb_activation, linear_colors, mesh->d_colors.get(), stream));
 		HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); // the temporaries go when this returns
 	}

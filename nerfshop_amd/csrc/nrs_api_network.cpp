@@ -17,7 +17,7 @@ int nrs_network_inference(nrs_model* m, void* stream, uint32_t n, const float* d
 	NRS_TRY(check_net(m, d_in, d_out, "nrs_network_inference"));
 	if (layout == NRS_PLANES && ld_out < n) return fail(NRS_ERR_INVALID_ARG, "nrs_network_inference: ld_out < n");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_network(m->dm, 0, n, d_in, NRS_NETWORK_INPUT_FLOATS, d_out, ld_out, layout, m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_network(m->dm, kNetInference, n, d_in, NRS_NETWORK_INPUT_FLOATS, d_out, ld_out, layout, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
 int nrs_network_inference_strided(nrs_model* m, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout) {
@@ -25,7 +25,7 @@ int nrs_network_inference_strided(nrs_model* m, void* stream, uint32_t n, const 
 	if (ld_in < NRS_NETWORK_INPUT_FLOATS) return fail(NRS_ERR_INVALID_ARG, "nrs_network_inference_strided: ld_in < 7");
 	if (layout == NRS_PLANES && ld_out < n) return fail(NRS_ERR_INVALID_ARG, "nrs_network_inference_strided: ld_out < n");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_network(m->dm, 0, n, d_in, ld_in, d_out, ld_out, layout, m->ctx->n_cus, stream, m->n_extra_dims != 0u && ld_in >= 10u));
+	NRS_LAUNCH(launch_network(m->dm, kNetInference, n, d_in, ld_in, d_out, ld_out, layout, m->ctx->n_cus, stream, m->n_extra_dims != 0u && ld_in >= 10u));
 	return NRS_OK;
 }
 int nrs_network_density(nrs_model* m, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout) {
@@ -33,14 +33,14 @@ int nrs_network_density(nrs_model* m, void* stream, uint32_t n, const float* d_i
 	if (ld_in < 3) return fail(NRS_ERR_INVALID_ARG, "nrs_network_density: ld_in < 3");
 	if (layout == NRS_PLANES && ld_out < n) return fail(NRS_ERR_INVALID_ARG, "nrs_network_density: ld_out < n");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_network(m->dm, 1, n, d_in, ld_in, d_out, ld_out, layout, m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_network(m->dm, kNetDensity, n, d_in, ld_in, d_out, ld_out, layout, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
 int nrs_network_input_gradient(nrs_model* m, void* stream, uint32_t n, const float* d_in, uint32_t ld_in, float* d_grad_out) {
 	NRS_TRY(check_net(m, d_in, d_grad_out, "nrs_network_input_gradient"));
 	if (ld_in < 3) return fail(NRS_ERR_INVALID_ARG, "nrs_network_input_gradient: ld_in < 3");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_network(m->dm, 3, n, d_in, ld_in, d_grad_out, 3, 0, m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_network(m->dm, kNetInputGradient, n, d_in, ld_in, d_grad_out, 0, 0, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
 // NerfNetwork::backward (nerf_network_full.h:142-221).  Everything that can be refused is refused before the first HIP call; nothing is allocated and nothing waits.
@@ -74,7 +74,7 @@ int nrs_network_visualize_activation(nrs_model* m, void* stream, uint32_t layer,
 	if (dimension >= network_layer_width(m->desc, layer, m->n_extra_dims))
 		return fail(NRS_ERR_INVALID_ARG, "nrs_network_visualize_activation: no such unit (layers: hash grid 32 | density hidden 64 | rgb input 32, 48 with light directions | one of 64 per rgb hidden layer)");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_network(m->dm, 4, n, d_in, NRS_NETWORK_INPUT_FLOATS, d_out, 1, (int)(kernel_layer(m->desc, layer) | (dimension << 8)), m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_network(m->dm, kNetVisualizeActivation, n, d_in, NRS_NETWORK_INPUT_FLOATS, d_out, 0, 0, m->ctx->n_cus, stream, false, kernel_layer(m->desc, layer), dimension));
 	return NRS_OK;
 }
 int nrs_density_on_grid(nrs_model* m, void* stream, const uint32_t res3d[3], const float aabb_min[3], const float aabb_max[3], int mask_with_density_grid,
@@ -83,7 +83,7 @@ int nrs_density_on_grid(nrs_model* m, void* stream, const uint32_t res3d[3], con
 	if (!m->have_params) return fail(NRS_ERR_STATE, "nrs_density_on_grid: parameters not set (nrs_model_set_params)");
 	if ((uint64_t)res3d[0] * res3d[1] * res3d[2] > 0x7fffffffull) return fail(NRS_ERR_INVALID_ARG, "nrs_density_on_grid: more than 2^31 grid points");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_grid_eval(m->dm, 0, res3d, aabb_min, aabb_max, nullptr, mask_with_density_grid ? m->d_density_grid.get() : nullptr, d_out, m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_grid_eval(m->dm, kGridDensity, res3d, aabb_min, aabb_max, nullptr, mask_with_density_grid ? m->d_density_grid.get() : nullptr, d_out, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
 int nrs_rgba_on_grid(nrs_model* m, void* stream, const uint32_t res3d[3], const float render_aabb_min[3], const float render_aabb_max[3],
@@ -93,7 +93,7 @@ int nrs_rgba_on_grid(nrs_model* m, void* stream, const uint32_t res3d[3], const 
 	if ((uint64_t)res3d[0] * res3d[1] * res3d[2] > 0x7fffffffull) return fail(NRS_ERR_INVALID_ARG, "nrs_rgba_on_grid: more than 2^31 grid points");
 	HIP_TRY(hipSetDevice(m->ctx->device));
 	const float dir01[3] = {(ray_dir[0] + 1.0f) * 0.5f, (ray_dir[1] + 1.0f) * 0.5f, (ray_dir[2] + 1.0f) * 0.5f}; // warp_direction, not normalised (tn:430)
-	NRS_LAUNCH(launch_grid_eval(m->dm, 1, res3d, render_aabb_min, render_aabb_max, dir01, nullptr, d_out_rgba, m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_grid_eval(m->dm, kGridRgba, res3d, render_aabb_min, render_aabb_max, dir01, nullptr, d_out_rgba, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
 int nrs_project_selection_pixels(nrs_model* m, void* stream, const nrs_render_params* p, const int32_t* d_pixels_xy, uint32_t n_pixels,
@@ -148,7 +148,7 @@ int nrs_poisson_boundary(nrs_model* m, const float* h_vertices, uint32_t n_verts
 	if (he == hipSuccess) he = d_sh.alloc((size_t)n_verts * 27);
 	if (he != hipSuccess) return fail_hip(he, "nrs_poisson_boundary: device allocation");
 	if (hipMemcpy(d_coords.get(), coords.data(), n * 7 * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(NRS_ERR_HIP, "nrs_poisson_boundary: upload");
-	NRS_LAUNCH(launch_network(m->dm, 0, (uint32_t)n, d_coords.get(), NRS_NETWORK_INPUT_FLOATS, d_net.get(), 16, NRS_INTERLEAVED, m->ctx->n_cus, nullptr));
+	NRS_LAUNCH(launch_network(m->dm, kNetInference, (uint32_t)n, d_coords.get(), NRS_NETWORK_INPUT_FLOATS, d_net.get(), 16, NRS_INTERLEAVED, m->ctx->n_cus, nullptr));
 	NRS_LAUNCH(launch_poisson_fit(m->dm, n_verts, n_sh, d_coords.get(), d_net.get(), is_inside, (float)(4 * M_PI / n_sh), d_density.get(), d_sh.get(), nullptr));
 	if (hipMemcpy(h_density_out, d_density.get(), (size_t)n_verts * 4, hipMemcpyDeviceToHost) != hipSuccess ||
 	    hipMemcpy(h_sh_out, d_sh.get(), (size_t)n_verts * 27 * 4, hipMemcpyDeviceToHost) != hipSuccess)
@@ -159,7 +159,7 @@ int nrs_hashgrid_encode(nrs_model* m, void* stream, uint32_t n, const float* d_i
 	NRS_TRY(check_net(m, d_in, d_out, "nrs_hashgrid_encode"));
 	if (ld_in < 3) return fail(NRS_ERR_INVALID_ARG, "nrs_hashgrid_encode: ld_in < 3");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	NRS_LAUNCH(launch_network(m->dm, 2, n, d_in, ld_in, d_out, 0, NRS_INTERLEAVED, m->ctx->n_cus, stream));
+	NRS_LAUNCH(launch_network(m->dm, kNetEncode, n, d_in, ld_in, d_out, 0, NRS_INTERLEAVED, m->ctx->n_cus, stream));
 	return NRS_OK;
 }
 

@@ -212,10 +212,19 @@ unsigned long long launch_render_dispatches(); // render-kernel dispatches of th
 int launch_slice(const DeviceModel& m, const RenderArgs& a, int n_cus, void* stream);
 int launch_trace_samples(const DeviceModel& m, const nrs_render_params& p, uint32_t n_pixels, const uint32_t* d_pixel_idx,
                          uint32_t max_samples, float* d_t, float* d_dt, uint32_t* d_count, void* stream);
-// mode 0: full inference (16 channels, c3 = density), 1: density MLP outputs, 2: hash-grid features [n x 32]
-// ld_light: floats 7..9 of a record are that sample's warped light direction (a model with n_extra_dims = 3 and ld_in >= 10); else DeviceModel::light01
-int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out,
-                   int layout, int n_cus, void* stream, bool per_sample_light = false);
+// The operators of network_kernel on caller batches (its MODE template argument: an unscoped enum, so the kernels keep their `int` symbol names).
+enum NetOp : int {
+	kNetInference = 0,          // inference_mixed_precision: 16 channels, c3 = density raw
+	kNetDensity = 1,            // density(): the density MLP's outputs
+	kNetEncode = 2,             // the hash-grid features, fp16 [n x 32]
+	kNetInputGradient = 3,      // input_gradient(stream, 3, ...): d density_raw / d position, f32 [n x 3]
+	kNetVisualizeActivation = 4,// visualize_activation(vis_layer, vis_dim): f32 [n]
+	kNetInferenceDeep = 5,      // kNetInference of a network with a third rgb hidden layer: the launcher's choice (DeviceModel::rgb_deep), never a caller's
+};
+// ld_out, layout: kNetInference / kNetDensity / kNetEncode only; vis_layer (a kernel layer: nrs_api_network.cpp kernel_layer), vis_dim: kNetVisualizeActivation only.
+// per_sample_light: floats 7..9 of a record are that sample's warped light direction (a model with n_extra_dims = 3 and ld_in >= 10); else DeviceModel::light01
+int launch_network(const DeviceModel& m, NetOp op, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out,
+                   int layout, int n_cus, void* stream, bool per_sample_light = false, uint32_t vis_layer = 0, uint32_t vis_dim = 0);
 // NerfNetwork::backward for base.json's architecture at the default numerics (nrs_network_backward.hip): parameter gradients ADDED to d_dparams (fp32, the blob's order),
 // optionally dL/dposition into floats 0..2 of d_dinput's records
 int launch_network_backward(const DeviceModel& m, uint32_t n, const float* d_in, uint32_t ld_in, const void* d_dout, uint32_t ld_dout, int layout,
@@ -246,7 +255,8 @@ inline uint32_t brick_slot(uint32_t x, uint32_t y, uint32_t z) {
 }
 int launch_brick_mark(const DeviceModel& m, const LevelParams& lp, const uint8_t* d_mask, uint32_t* d_table, uint32_t* d_counter, uint32_t* d_slots, uint32_t capacity, void* stream);
 int launch_brick_fill(const DeviceModel& m, const LevelParams& lp, const uint32_t* d_slots, uint32_t n_bricks, void* d_records2, void* stream);
-int launch_grid_eval(const DeviceModel& m, int mode, const uint32_t res[3], const float box_mn[3], const float box_mx[3], const float dir01[3],
+enum GridEvalOp : int { kGridDensity = 0, kGridRgba = 1 }; // get_density_on_grid / get_rgba_on_grid (grid_eval_kernel's MODE)
+int launch_grid_eval(const DeviceModel& m, GridEvalOp op, const uint32_t res[3], const float box_mn[3], const float box_mx[3], const float dir01[3],
                      const float* d_density_grid, float* d_out, int n_cus, void* stream);
 int launch_map_rays(const DeviceEdit& e, uint32_t n, float* d_coords, uint32_t ld, int with_dir, uint8_t* d_empty, void* stream);
 int launch_grid_to_bitfield(const float* d_grid, uint8_t* d_bitfield, float* d_scratch_mean, void* stream);

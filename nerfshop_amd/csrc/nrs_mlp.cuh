@@ -703,26 +703,38 @@ __device__ __forceinline__ floatx16 mfma_first(half8 a, half8 b) {
 // the MLP, which costs a wave of occupancy.  The gather, not the MLP, is the phase that needs the latency hiding.
 #define NRS_STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-// Density MLP 32 -> 64 (ReLU) -> 16 for one 32-sample block.  x0/x1: features (k-steps 0/1).
-// Returns the fp16-rounded outputs as the next B operand: element e of lane (j, g) = output row (e&3) + 8*(e>>2) + 4g.
-template <bool ACC16 = false>
-__device__ __forceinline__ half8 density_mlp(const half8* lds_w, int lane, half8 x0, half8 x1) {
-	// hidden rows 0..31 then 32..63, each reduced to its two packed B operands before the next accumulator is started
-	// (ACC16: mfma_step rounds the sum it is handed before it adds its own k step; the last sum of a layer is rounded by relu_pack / pack themselves)
+// The layers of the two MLPs for one 32-sample block, each stated once: the inference kernels, the introspection operators and the backward kernel's forward
+// pass all run these.  A layer's packed outputs are the B operands of the next: element e of lane (j, g) = output row (e&3) + 8*(e>>2) + 4g of its 32-row tile.
+// Density hidden layer 32 -> 64 (ReLU).  x0/x1: features (k-steps 0/1); p0..p3: hidden rows 0..31 then 32..63, each tile reduced to its two packed operands
+// before the next accumulator is started.
+// (ACC16: mfma_step rounds the sum it is handed before it adds its own k step; the last sum of a layer is rounded by relu_pack / pack themselves)
+template <bool ACC16>
+__device__ __forceinline__ void density_hidden(const half8* lds_w, int lane, half8 x0, half8 x1, half8& p0, half8& p1, half8& p2, half8& p3) {
 	floatx16 h = mfma_first(lds_w[NRS_FRAG_D1(0, 0) * 64 + lane], x0);
 	h = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D1(0, 1) * 64 + lane], x1, h);
-	const half8 p0 = relu_pack(h, 0), p1 = relu_pack(h, 8);
+	p0 = relu_pack(h, 0); p1 = relu_pack(h, 8);
 	NRS_STAGE_FENCE();
 	h = mfma_first(lds_w[NRS_FRAG_D1(1, 0) * 64 + lane], x0);
 	h = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D1(1, 1) * 64 + lane], x1, h);
-	const half8 p2 = relu_pack(h, 0), p3 = relu_pack(h, 8);
+	p2 = relu_pack(h, 0); p3 = relu_pack(h, 8);
 	NRS_STAGE_FENCE();
+}
+// Density output layer 64 -> 16 (no activation).
+template <bool ACC16>
+__device__ __forceinline__ half8 density_output(const half8* lds_w, int lane, half8 p0, half8 p1, half8 p2, half8 p3) {
 	floatx16 o = mfma_first(lds_w[NRS_FRAG_D2(0) * 64 + lane], p0);
 	o = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D2(1) * 64 + lane], p1, o);
 	o = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D2(2) * 64 + lane], p2, o);
 	o = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D2(3) * 64 + lane], p3, o);
 	NRS_STAGE_FENCE();
 	return pack(o, 0);
+}
+// Density MLP 32 -> 64 (ReLU) -> 16: the fp16-rounded outputs, the rgb MLP's first B operand.
+template <bool ACC16 = false>
+__device__ __forceinline__ half8 density_mlp(const half8* lds_w, int lane, half8 x0, half8 x1) {
+	half8 p0, p1, p2, p3;
+	density_hidden<ACC16>(lds_w, lane, x0, x1, p0, p1, p2, p3);
+	return density_output<ACC16>(lds_w, lane, p0, p1, p2, p3);
 }
 
 // One 64 -> 64 ReLU layer of the rgb MLP whose fragments `w` (8: [mb][ks]) may live in LDS or in HBM: b0..b3 in, the packed B operands of the next layer out.
@@ -764,14 +776,20 @@ __device__ __forceinline__ floatx16 rgb_layer0_tile(const half8* lds_w, int lane
 	if (LIGHT && light_w) a = mfma_step<ACC16>(lds_w, lane, light_w[NRS_FRAG_R1L(mb) * 64 + lane], lb, a);
 	return a;
 }
-template <bool ACC16 = false, bool DEEP = false, bool LIGHT = false>
-__device__ __forceinline__ half8 rgb_mlp(const half8* lds_w, int lane, half8 din, half8 sh, const half8* deep_w = nullptr, const half8* light_w = nullptr, half8 lb = half8{}) {
+// rgb layer 0 (32 or 48 -> 64, ReLU): b0..b3 as density_hidden's p0..p3
+template <bool ACC16, bool LIGHT>
+__device__ __forceinline__ void rgb_hidden0(const half8* lds_w, int lane, half8 din, half8 sh, const half8* light_w, half8 lb, half8& b0, half8& b1, half8& b2, half8& b3) {
 	floatx16 a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 0, din, sh, light_w, lb);
-	half8 b0 = relu_pack(a, 0), b1 = relu_pack(a, 8);
+	b0 = relu_pack(a, 0); b1 = relu_pack(a, 8);
 	NRS_STAGE_FENCE();
 	a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 1, din, sh, light_w, lb);
-	half8 b2 = relu_pack(a, 0), b3 = relu_pack(a, 8);
+	b2 = relu_pack(a, 0); b3 = relu_pack(a, 8);
 	NRS_STAGE_FENCE();
+}
+template <bool ACC16 = false, bool DEEP = false, bool LIGHT = false>
+__device__ __forceinline__ half8 rgb_mlp(const half8* lds_w, int lane, half8 din, half8 sh, const half8* deep_w = nullptr, const half8* light_w = nullptr, half8 lb = half8{}) {
+	half8 b0, b1, b2, b3;
+	rgb_hidden0<ACC16, LIGHT>(lds_w, lane, din, sh, light_w, lb, b0, b1, b2, b3);
 	hidden_layer_64<ACC16>(lds_w, lds_w + NRS_FRAG_R2(0, 0) * 64, lane, b0, b1, b2, b3);
 	if (DEEP && deep_w) hidden_layer_64<ACC16>(lds_w, deep_w + NRS_FRAG_R2B(0, 0) * 64, lane, b0, b1, b2, b3);
 	floatx16 o = mfma_first(lds_w[NRS_FRAG_R3(0) * 64 + lane], b0);
@@ -782,7 +800,7 @@ __device__ __forceinline__ half8 rgb_mlp(const half8* lds_w, int lane, half8 din
 	return pack(o, 0);
 }
 
-// ---- network introspection: render modes EncodingVis and Normals (render_body's INTRO instantiation only) ----------------------------------------
+// ---- network introspection: the pieces of wave_visualize_activation / wave_density_input_gradient below ------------------------------------------
 // tiny-cuda-nn's visualize_activation / input_gradient as restated in oracle/nrs_oracle.cpp (network_activation_one, density_input_gradient_one).
 // register r (wave-uniform) of a D tile
 __device__ __forceinline__ float pick16(const floatx16& d, int r) {
@@ -812,12 +830,8 @@ __device__ __forceinline__ float mlp_hidden_activation(const half8* lds_w, int l
 	} else if (layer == 3u) {
 		t = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, mb, din, sh, light_w, lb);
 	} else {
-		floatx16 a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 0, din, sh, light_w, lb);
-		half8 b0 = relu_pack(a, 0), b1 = relu_pack(a, 8);
-		NRS_STAGE_FENCE();
-		a = rgb_layer0_tile<ACC16, LIGHT>(lds_w, lane, 1, din, sh, light_w, lb);
-		half8 b2 = relu_pack(a, 0), b3 = relu_pack(a, 8);
-		NRS_STAGE_FENCE();
+		half8 b0, b1, b2, b3;
+		rgb_hidden0<ACC16, LIGHT>(lds_w, lane, din, sh, light_w, lb, b0, b1, b2, b3);
 		const half8* w = lds_w + NRS_FRAG_R2(mb, 0) * 64;
 		if (layer == 5u && deep_w) { // the third hidden layer: behind the whole second one
 			hidden_layer_64<ACC16>(lds_w, lds_w + NRS_FRAG_R2(0, 0) * 64, lane, b0, b1, b2, b3);
@@ -839,14 +853,8 @@ __device__ __forceinline__ float mlp_hidden_activation(const half8* lds_w, int l
 __device__ __forceinline__ int level_of_pair(int q, int gg) { const int r = 2 * q; return ((r & 3) + 8 * (r >> 2) + 4 * gg) >> 1; }
 template <bool ACC16>
 __device__ __forceinline__ void density_backward_features(const half8* lds_w, const half8* __restrict__ gfrag, int lane, half8 x0, half8 x1, uint32_t out[8]) {
-	floatx16 h = mfma_first(lds_w[NRS_FRAG_D1(0, 0) * 64 + lane], x0);
-	h = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D1(0, 1) * 64 + lane], x1, h);
-	const half8 p0 = relu_pack(h, 0), p1 = relu_pack(h, 8);
-	NRS_STAGE_FENCE();
-	h = mfma_first(lds_w[NRS_FRAG_D1(1, 0) * 64 + lane], x0);
-	h = mfma_step<ACC16>(lds_w, lane, lds_w[NRS_FRAG_D1(1, 1) * 64 + lane], x1, h);
-	const half8 p2 = relu_pack(h, 0), p3 = relu_pack(h, 8);
-	NRS_STAGE_FENCE();
+	half8 p0, p1, p2, p3;
+	density_hidden<ACC16>(lds_w, lane, x0, x1, p0, p1, p2, p3);
 	// W2[0][k] for the k's this lane's hidden registers stand for: what lane (0, lane >> 5) of the D2 fragments holds (output row 0)
 	const int row0 = lane & 32;
 	auto dhidden = [&](const half8& p, int ks) {
@@ -905,6 +913,7 @@ __device__ __forceinline__ void level_input_gradient(const GridView& gv, const L
 		for (int d = 0; d < 3; ++d) result[d] = fmaf((float)dlh[f], grads[f][d], result[d]);
 }
 
+
 // tiny-cuda-nn's roundings as a template value: NUM >= 0 fixes them at compile time (bit 0 grid accumulation in network precision, bit 1 fp16 MLP
 // accumulators), kNumRuntime reads them from `nm` (DeviceModel::numerics, wave-uniform) -- both flavours compiled in, one scalar branch.
 template <int NUM, bool QUADS = false, bool ZERO = true, int GATE = 0>
@@ -922,11 +931,132 @@ __device__ __forceinline__ half8 rgb_mlp_num(uint32_t nm, const half8* lds_w, in
 	if (NUM == kNumRuntime ? (nm & 2u) != 0u : (NUM & 2) != 0) return rgb_mlp<true, DEEP, LIGHT>(lds_w, lane, din, sh, deep_w, light_w, lb);
 	return rgb_mlp<false, DEEP, LIGHT>(lds_w, lane, din, sh, deep_w, light_w, lb);
 }
+template <int NUM, bool LIGHT>
+__device__ __forceinline__ float mlp_hidden_activation_num(uint32_t nm, const half8* lds_w, int lane, half8 x0, half8 x1, half8 din, half8 sh, uint32_t layer, uint32_t unit, const half8* deep_w,
+                                                           const half8* light_w, half8 lb) {
+	if (NUM == kNumRuntime ? (nm & 2u) != 0u : (NUM & 2) != 0) return mlp_hidden_activation<true, LIGHT>(lds_w, lane, x0, x1, din, sh, layer, unit, deep_w, light_w, lb);
+	return mlp_hidden_activation<false, LIGHT>(lds_w, lane, x0, x1, din, sh, layer, unit, deep_w, light_w, lb);
+}
+template <int NUM>
+__device__ __forceinline__ void density_backward_features_num(uint32_t nm, const half8* lds_w, const half8* __restrict__ gfrag, int lane, half8 x0, half8 x1, uint32_t out[8]) {
+	if (NUM == kNumRuntime ? (nm & 2u) != 0u : (NUM & 2) != 0) density_backward_features<true>(lds_w, gfrag, lane, x0, x1, out);
+	else density_backward_features<false>(lds_w, gfrag, lane, x0, x1, out);
+}
 
 // Exchange a value with the partner lane (l ^ 32): one ds_bpermute.
 __device__ __forceinline__ float xchg32(float v) { return __shfl_xor(v, 32, 64); }
 __device__ __forceinline__ uint32_t xchg32u(uint32_t v) { return (uint32_t)__shfl_xor((int)v, 32, 64); }
 
+// ---- the two introspection operators for a wave's 64 samples whose features encode_to_lds has left in `fl`: network_kernel's kNetVisualizeActivation /
+// kNetInputGradient and render_body's INTRO block (EncodingVis / Normals).  The callers differ in where the operands come from, never in what is done with them.
+// network.visualize_activation(stream, layer, dim, ...): unit `dim` of forward_activations(layer) of the lane's own sample.  sh_own / sh_par, lb_own / lb_par: the SH
+// coefficients and the light operand (rgb_mlp) of the lane's own sample and of its partner's (lane ^ 32); light: the own sample's warped light direction;
+// NUM, nm: as for density_mlp_num.
+template <int NUM, bool LIGHT>
+__device__ __forceinline__ float wave_visualize_activation(uint32_t nm, const FeatLds& fl, const half8* lds_w, int lane, uint32_t layer, uint32_t dim, half8 sh_own, half8 sh_par, const half8* deep_w,
+                                                           const half8* light_w, half8 lb_own, half8 lb_par, f3 light) {
+	const int g = lane >> 5;
+	float v = 0.f;
+	if (layer == 0u) { // the hash-grid output: the slab holds level L of the own sample (see encode_to_lds)
+		const uint32_t L = dim >> 1;
+		const uint32_t w = ((L & 1u) == (uint32_t)g) ? fl.feat[L >> 1][0][lane] : fl.feat[L >> 1][1][lane ^ 32];
+		v = (float)__builtin_bit_cast(half2v, w)[dim & 1u];
+	} else if (LIGHT && layer == 2u && dim >= 32u) { // the Identity encoding of the light direction (units 32..34) and its padding ones
+		const float l = dim == 32u ? light.x : (dim == 33u ? light.y : light.z);
+		v = dim < 35u ? (float)(_Float16)l : 1.0f;
+	} else if (layer == 2u && dim >= 16u) { // an SH coefficient of the own direction: 8 g .. 8 g + 7 are here, the others in the partner lane's sh_par
+		const uint32_t cidx = dim - 16u;
+		const float mine = (float)pick8(sh_own, (int)(cidx & 7u)), theirs = xchg32((float)pick8(sh_par, (int)(cidx & 7u)));
+		v = ((cidx >> 3) == (uint32_t)g) ? mine : theirs;
+	} else {
+		#pragma unroll 1
+		for (int b = 0; b < 2; ++b) {
+			const int sel = (b != g) ? 1 : 0;
+			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
+			float val;
+			int half_of_row;
+			if (layer == 2u) { // a density-MLP output (rows 0..15 of the rgb network's input)
+				const half8 dout = density_mlp_num<NUM>(nm, lds_w, lane, x0, x1);
+				val = (float)pick8(dout, (int)((dim & 3u) + 4u * (dim >> 3))); // element of row dim: row = (e & 3) + 8 (e >> 2) + 4 half
+				half_of_row = (int)((dim >> 2) & 1u);
+			} else {
+				half8 din = x0;
+				if (layer >= 3u) din = density_mlp_num<NUM>(nm, lds_w, lane, x0, x1);
+				val = mlp_hidden_activation_num<NUM, LIGHT>(nm, lds_w, lane, x0, x1, din, sel ? sh_par : sh_own, layer, dim, deep_w, light_w, sel ? lb_par : lb_own);
+				half_of_row = tile_half(dim);
+			}
+			// the value of sample (b, j) sits in lane j + 32 * half_of_row; its sample's lane is j + 32 * b
+			if (half_of_row != b) val = xchg32(val);
+			if (g == b) v = val;
+		}
+	}
+	return v;
+}
+// network.input_gradient(stream, 3, positions, gradients): d density_raw / d warped position of the lane's own sample at `pos` -- backward of 128 e_0 through the
+// density MLP (density_backward_features), the hash grid's input gradient level by level, then the 1 / 128.  Overwrites the feature slab with dL/dfeatures.
+template <int NUM>
+__device__ __forceinline__ f3 wave_density_input_gradient(uint32_t nm, FeatLds& fl, const half8* lds_w, const half8* __restrict__ gfrag, const GridView& gv, const LevelParams* levels, int lane, f3 pos) {
+	const int g = lane >> 5;
+	uint32_t dfe[2][8];
+	#pragma unroll
+	for (int b = 0; b < 2; ++b) { // (unrolled: dfe must stay in registers)
+		const int sel = (b != g) ? 1 : 0;
+		density_backward_features_num<NUM>(nm, lds_w, gfrag, lane, load_features(fl, lane, sel, 0), load_features(fl, lane, sel, 1), dfe[b]);
+	}
+	// dL/dfeatures of sample (b, j) -> the slab, G[L][lane j + 32 b] (both lane halves of a column hold 8 of its 16 level pairs)
+	__builtin_amdgcn_wave_barrier();
+	uint32_t* G = &fl.feat[0][0][0];
+	#pragma unroll
+	for (int b = 0; b < 2; ++b)
+		#pragma unroll
+		for (int q = 0; q < 8; ++q) G[level_of_pair(q, g) * 64 + (lane & 31) + 32 * b] = dfe[b][q];
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	float res[3] = {0.f, 0.f, 0.f};
+	#pragma unroll 1
+	for (int L = 0; L < (int)kLevels; ++L) level_input_gradient(gv, levels[L], pos, G[L * 64 + lane], res);
+	__builtin_amdgcn_wave_barrier();
+	return mk3(res[0] * (1.0f / 128.0f), res[1] * (1.0f / 128.0f), res[2] * (1.0f / 128.0f));
+}
+
+// The two-block evaluation: the wave's 64 samples (features in `fl`) go through the MLPs as two 32-sample blocks; block b's samples belong to the lanes of half b,
+// its rows 0..2 sit in its lanes 0..31.  Returns the lane's own sample as packed raw fp16 pairs.
+struct NetRaw { uint32_t d, rg, b; }; // (density row 0, .), (r, g), (b, .)
+// the density MLP alone: NetRaw::d
+template <int NUM>
+__device__ __forceinline__ uint32_t wave_density(uint32_t nm, const FeatLds& fl, const half8* lds_w, int lane) {
+	const int g = lane >> 5;
+	uint32_t res_d = 0;
+	#pragma unroll 1
+	for (int b = 0; b < 2; ++b) {
+		const int sel = (b != g) ? 1 : 0;
+		const half8 dout = density_mlp_num<NUM>(nm, lds_w, lane, load_features(fl, lane, sel, 0), load_features(fl, lane, sel, 1));
+		uint32_t vd = __builtin_bit_cast(u32x4, dout)[0];
+		if (b == 1) vd = xchg32u(vd);
+		if (g == b) res_d = vd;
+	}
+	return res_d;
+}
+// (sh_own / sh_par: the SH coefficients of the lane's own sample and of its partner's; deep_w, light_w, lb: as for rgb_mlp -- both wave-uniform branches compiled
+// in -- the same for every sample)
+template <int NUM>
+__device__ __forceinline__ NetRaw wave_network(uint32_t nm, const FeatLds& fl, const half8* lds_w, int lane, half8 sh_own, half8 sh_par, const half8* deep_w, const half8* light_w, half8 lb) {
+	const int g = lane >> 5;
+	NetRaw r = {0, 0, 0};
+	#pragma unroll 1
+	for (int b = 0; b < 2; ++b) {
+		const int sel = (b != g) ? 1 : 0;
+		const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
+		const half8 dout = density_mlp_num<NUM>(nm, lds_w, lane, x0, x1);
+		const half8 rout = rgb_mlp_num<NUM, true, true>(nm, lds_w, lane, dout, sel ? sh_par : sh_own, deep_w, light_w, lb);
+		const u32x4 dd = __builtin_bit_cast(u32x4, dout), rr = __builtin_bit_cast(u32x4, rout);
+		uint32_t vd = dd[0], vrg = rr[0], vb = rr[1];
+		if (b == 1) { vd = xchg32u(vd); vrg = xchg32u(vrg); vb = xchg32u(vb); }
+		if (g == b) { r.d = vd; r.rg = vrg; r.b = vb; }
+	}
+	return r;
+}
 
 // per-workgroup LDS of the kernels that run the network on caller batches: the weights + one feature slab per wave
 template <int WAVES>

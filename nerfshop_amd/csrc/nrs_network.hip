@@ -55,22 +55,11 @@ __global__ __launch_bounds__(256) void slice_kernel(const DeviceModel m, const R
 		const f3 pdir = mk3(xchg32(wdir.x), xchg32(wdir.y), xchg32(wdir.z));
 		half8 sh_own, sh_par;
 		encode_sh4_2(g, wdir, pdir, sh_own, sh_par);
-		uint32_t res_d = 0, res_rg = 0, res_b = 0;
-		#pragma unroll 1
-		for (int b = 0; b < 2; ++b) {
-			const int sel = (b != g) ? 1 : 0;
-			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
-			const half8 dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, x0, x1);
-			// (a network trained with light directions: the frame's light direction for every pixel -- a wave-uniform branch, rgb_mlp's LIGHT)
-			const half8 rout = rgb_mlp_num<NUM, true, true>(nm, sm.ml.w, lane, dout, sel ? sh_par : sh_own, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
-			                                                m.n_extra_dims ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_operand(g, m.light01[0], m.light01[1], m.light01[2]));
-			const u32x4 dd = __builtin_bit_cast(u32x4, dout), rr = __builtin_bit_cast(u32x4, rout);
-			uint32_t vd = dd[0], vrg = rr[0], vb = rr[1];
-			if (b == 1) { vd = xchg32u(vd); vrg = xchg32u(vrg); vb = xchg32u(vb); }
-			if (g == b) { res_d = vd; res_rg = vrg; res_b = vb; }
-		}
+		// (a network trained with light directions: the frame's light direction for every pixel -- a wave-uniform branch, rgb_mlp's LIGHT)
+		const NetRaw raw = wave_network<NUM>(nm, fl, sm.ml.w, lane, sh_own, sh_par, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
+		                                     m.n_extra_dims ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_operand(g, m.light01[0], m.light01[1], m.light01[2]));
 		if (!have) continue;
-		const half2v hd = __builtin_bit_cast(half2v, res_d), hrg = __builtin_bit_cast(half2v, res_rg), hb = __builtin_bit_cast(half2v, res_b);
+		const half2v hd = __builtin_bit_cast(half2v, raw.d), hrg = __builtin_bit_cast(half2v, raw.rg), hb = __builtin_bit_cast(half2v, raw.b);
 		const float alpha = clampf_(1.f - __expf(-network_to_density((float)hd[0], m.density_activation) / 100.0f), 0.0f, 1.0f);
 		float tr = network_to_rgb((float)hrg[0], m.rgb_activation) * alpha, tg = network_to_rgb((float)hrg[1], m.rgb_activation) * alpha,
 		      tb = network_to_rgb((float)hb[0], m.rgb_activation) * alpha;
@@ -216,15 +205,7 @@ __global__ __launch_bounds__(256) void selection_rays_kernel(const DeviceModel m
 		}
 		if (!__any(have)) break;
 		encode_num<NUM>(nm, gv, m.levels, sm.ml, fl, lane, g, wpos, have);
-		uint32_t res_d = 0;
-		#pragma unroll 1
-		for (int b = 0; b < 2; ++b) {
-			const int sel = (b != g) ? 1 : 0;
-			const half8 dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, load_features(fl, lane, sel, 0), load_features(fl, lane, sel, 1));
-			uint32_t vd = __builtin_bit_cast(u32x4, dout)[0];
-			if (b == 1) vd = xchg32u(vd);
-			if (g == b) res_d = vd;
-		}
+		const uint32_t res_d = wave_density<NUM>(nm, fl, sm.ml.w, lane);
 		if (have) {
 			const float density = network_to_density((float)__builtin_bit_cast(half2v, res_d)[0], m.density_activation);
 			const float alpha = 1.f - __expf(-density * unwarp_dt(warp_dt(dt))); // (the reference reads dt back from the NerfCoordinate)
@@ -295,23 +276,22 @@ int launch_poisson_fit(const DeviceModel& m, uint32_t n_verts, uint32_t n_sh, co
 	return NRS_OK;
 }
 
-// MODE 0: inference_mixed_precision (16 channels, c3 = density raw; MODE 5: the same for a network with a third rgb hidden layer), 1: density(), 2: hash-grid features [n x 32]
+// MODE: a NetOp (nrs_internal.h).
 // 768-thread workgroups: 12 waves share one LDS copy of the weights (24 KB) next to their 12 feature slabs (48 KB), two workgroups per CU
 // = 6 waves/SIMD at <= 80 VGPRs.  (256-thread workgroups, the first shape, put 3 workgroups = 3 waves/SIMD on a CU: the weights' copy
 // per workgroup was what filled the LDS.)
 constexpr int kNetWaves = 12;
-// MODE 3: NerfNetwork::input_gradient(stream, 3, ...) -> d density_raw / d position, f32 [n x 3]; MODE 4: visualize_activation(layer, dim) -> f32 [n]
-// (layout = layer | dim << 8); both as restated in oracle/nrs_oracle.cpp -- the callers of the render path's Normals / EncodingVis modes and of
-// compute_mesh_vertex_normals (tn:4491).
-// LIGHT (modes 0 and 4): a network trained with light directions (DeviceModel::n_extra_dims = 3; rgb_mlp's LIGHT) -- every sample gets DeviceModel::light01, or, with
-// ld_light != 0, floats 7..9 of its own record (already warped: the reference's PitchedPtr<NerfCoordinate> with extra_stride).  Its MODE 0 serves the third hidden layer
+// kNetInputGradient and kNetVisualizeActivation (its `layout` = layer | dim << 8, packed by launch_network) are as restated in oracle/nrs_oracle.cpp -- the
+// callers of the render path's Normals / EncodingVis modes and of compute_mesh_vertex_normals (tn:4491).
+// LIGHT (kNetInference and kNetVisualizeActivation): a network trained with light directions (DeviceModel::n_extra_dims = 3; rgb_mlp's LIGHT) -- every sample gets DeviceModel::light01, or, with
+// ld_light != 0, floats 7..9 of its own record (already warped: the reference's PitchedPtr<NerfCoordinate> with extra_stride).  Its kNetInference serves the third hidden layer
 // too (a wave-uniform branch on DeviceModel::rgb_deep).  The instantiations without the flag are what they were before it existed.
 template <int MODE, int NUM = 0, bool LIGHT = false>
-__global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4 || LIGHT) ? 3 : 6) void network_kernel(const DeviceModel m, uint32_t n, const float* __restrict__ in, uint32_t ld_in,
+__global__ __launch_bounds__(64 * kNetWaves, (MODE == kNetInputGradient || MODE == kNetVisualizeActivation || LIGHT) ? 3 : 6) void network_kernel(const DeviceModel m, uint32_t n, const float* __restrict__ in, uint32_t ld_in,
                                                       _Float16* __restrict__ out, uint32_t ld_out, int layout, uint32_t ld_light = 0u) {
-	constexpr bool FULL = MODE == 0 || MODE == 5; // (5: the full network with a third rgb hidden layer, DeviceModel::rgb_deep -- base_3layer.json)
+	constexpr bool FULL = MODE == kNetInference || MODE == kNetInferenceDeep; // (Deep: the full network with a third rgb hidden layer, DeviceModel::rgb_deep -- base_3layer.json)
 	const half8* light_w = LIGHT ? reinterpret_cast<const half8*>(m.wfrag) : nullptr;
-	const half8* deep_w = (MODE == 5 || (LIGHT && m.rgb_deep)) ? reinterpret_cast<const half8*>(m.wfrag) : nullptr;
+	const half8* deep_w = (MODE == kNetInferenceDeep || (LIGHT && m.rgb_deep)) ? reinterpret_cast<const half8*>(m.wfrag) : nullptr;
 	__shared__ NetSmemT<kNetWaves> sm;
 	stage_model_to_lds(m, sm.ml);
 	const int lane = threadIdx.x & 63;
@@ -329,7 +309,7 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4 || LIGHT) ?
 			const float* c = in + (size_t)s * ld_in;
 			wpos = mk3(c[0], c[1], c[2]);
 			// (NerfNetworkNoDir never looks at the direction rows: a caller may leave them unset, and 0-weights do not stop a NaN)
-			if ((FULL || MODE == 4) && !m.no_dir) wdir = mk3(c[4], c[5], c[6]);
+			if ((FULL || MODE == kNetVisualizeActivation) && !m.no_dir) wdir = mk3(c[4], c[5], c[6]);
 			if (LIGHT && ld_light) wlight = mk3(c[7], c[8], c[9]);
 		}
 		// the light operands of the lane's own sample and of its partner's (lane ^ 32): block b's comes from the lanes 0..31, as for the SH coefficients
@@ -340,75 +320,23 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4 || LIGHT) ?
 		}
 		encode_to_lds<(NUM & 1) != 0>(gv, m.levels, sm.ml, fl, lane, g, wpos, have); // (four levels per round trip measured here: ray-ordered batches +-0, random ones -3.5 %: profiles/r06/ab_net_quads.txt; six waves per SIMD hide the trips)
 
-		if (MODE == 3) {
-			uint32_t dfe[2][8];
-			#pragma unroll
-			for (int b = 0; b < 2; ++b) {
-				const int sel = (b != g) ? 1 : 0;
-				density_backward_features<(NUM & 2) != 0>(sm.ml.w, reinterpret_cast<const half8*>(m.wfrag), lane, load_features(fl, lane, sel, 0), load_features(fl, lane, sel, 1), dfe[b]);
-			}
-			__builtin_amdgcn_wave_barrier();
-			uint32_t* G = &fl.feat[0][0][0];
-			#pragma unroll
-			for (int b = 0; b < 2; ++b)
-				#pragma unroll
-				for (int q = 0; q < 8; ++q) G[level_of_pair(q, g) * 64 + (lane & 31) + 32 * b] = dfe[b][q];
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-			float res[3] = {0.f, 0.f, 0.f};
-			#pragma unroll 1
-			for (int L = 0; L < (int)kLevels; ++L) level_input_gradient(gv, m.levels[L], wpos, G[L * 64 + lane], res);
-			__builtin_amdgcn_wave_barrier();
+		if (MODE == kNetInputGradient) {
+			const f3 gr = wave_density_input_gradient<NUM>((uint32_t)NUM, fl, sm.ml.w, reinterpret_cast<const half8*>(m.wfrag), gv, m.levels, lane, wpos);
 			if (have) {
 				float* o = reinterpret_cast<float*>(out) + 3 * (size_t)s;
-				o[0] = res[0] * (1.0f / 128.0f); o[1] = res[1] * (1.0f / 128.0f); o[2] = res[2] * (1.0f / 128.0f);
+				o[0] = gr.x; o[1] = gr.y; o[2] = gr.z;
 			}
 			continue;
 		}
-		if (MODE == 4) {
-			const uint32_t layer = (uint32_t)layout & 0xffu, dim = (uint32_t)layout >> 8;
-			float v = 0.f;
-			if (layer == 0u) {
-				const uint32_t L = dim >> 1;
-				const uint32_t w = ((L & 1u) == (uint32_t)g) ? fl.feat[L >> 1][0][lane] : fl.feat[L >> 1][1][lane ^ 32];
-				v = (float)__builtin_bit_cast(half2v, w)[dim & 1u];
-			} else if (LIGHT && layer == 2u && dim >= 32u) { // the Identity encoding of the light direction (units 32..34) and its padding ones
-				const float l = dim == 32u ? wlight.x : (dim == 33u ? wlight.y : wlight.z);
-				v = dim < 35u ? (float)(_Float16)l : 1.0f;
-			} else if (layer == 2u && dim >= 16u) {
-				const half8 sh_own = encode_sh4(g, wdir), sh_par = encode_sh4(g, mk3(xchg32(wdir.x), xchg32(wdir.y), xchg32(wdir.z)));
-				const uint32_t cidx = dim - 16u;
-				const float mine = (float)pick8(sh_own, (int)(cidx & 7u)), theirs = xchg32((float)pick8(sh_par, (int)(cidx & 7u)));
-				v = ((cidx >> 3) == (uint32_t)g) ? mine : theirs;
-			} else {
-				const half8 sh_own = encode_sh4(g, wdir), sh_par = encode_sh4(g, mk3(xchg32(wdir.x), xchg32(wdir.y), xchg32(wdir.z)));
-				#pragma unroll 1
-				for (int b = 0; b < 2; ++b) {
-					const int sel = (b != g) ? 1 : 0;
-					const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
-					float val;
-					int half_of_row;
-					if (layer == 2u) {
-						const half8 dout = density_mlp<(NUM & 2) != 0>(sm.ml.w, lane, x0, x1);
-						val = (float)pick8(dout, (int)((dim & 3u) + 4u * (dim >> 3)));
-						half_of_row = (int)((dim >> 2) & 1u);
-					} else {
-						half8 din = x0;
-						if (layer >= 3u) din = density_mlp<(NUM & 2) != 0>(sm.ml.w, lane, x0, x1);
-						val = mlp_hidden_activation<(NUM & 2) != 0, LIGHT>(sm.ml.w, lane, x0, x1, din, sel ? sh_par : sh_own, layer, dim, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
-						                                                   light_w, sel ? lb_par : lb_own);
-						half_of_row = tile_half(dim);
-					}
-					if (half_of_row != b) val = xchg32(val);
-					if (g == b) v = val;
-				}
-			}
+		if (MODE == kNetVisualizeActivation) {
+			const half8 sh_own = encode_sh4(g, wdir), sh_par = encode_sh4(g, mk3(xchg32(wdir.x), xchg32(wdir.y), xchg32(wdir.z)));
+			const float v = wave_visualize_activation<NUM, LIGHT>((uint32_t)NUM, fl, sm.ml.w, lane, (uint32_t)layout & 0xffu, (uint32_t)layout >> 8, sh_own, sh_par,
+			                                                    m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_w, lb_own, lb_par, wlight);
 			if (have) reinterpret_cast<float*>(out)[s] = v;
 			continue;
 		}
 
-		if (MODE == 2) {
+		if (MODE == kNetEncode) {
 			#pragma unroll 1
 			for (int b = 0; b < 2; ++b) {
 				const uint32_t sb = tile * 64 + 32 * b + j;
@@ -434,7 +362,7 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4 || LIGHT) ?
 			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
 			const half8 dout = density_mlp<(NUM & 2) != 0>(sm.ml.w, lane, x0, x1);
 			half8 rout = dout;
-			if (FULL) rout = rgb_mlp<(NUM & 2) != 0, MODE == 5 || LIGHT, LIGHT>(sm.ml.w, lane, dout, sel ? sh_par : sh_own, deep_w, light_w, sel ? lb_par : lb_own);
+			if (FULL) rout = rgb_mlp<(NUM & 2) != 0, MODE == kNetInferenceDeep || LIGHT, LIGHT>(sm.ml.w, lane, dout, sel ? sh_par : sh_own, deep_w, light_w, sel ? lb_par : lb_own);
 			const uint32_t sb = tile * 64 + 32 * b + j;
 			if (sb < n) {
 				uint32_t ldo = ld_out; // (opaque per tile: the eight 64-bit row offsets were hoisted out of the tile loop and, in the fp16-accumulator twins, spilled)
@@ -452,8 +380,15 @@ __global__ __launch_bounds__(64 * kNetWaves, (MODE == 3 || MODE == 4 || LIGHT) ?
 	}
 }
 
-int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout,
-                   int n_cus, void* stream, bool per_sample_light) {
+// one operator's kernels, by DeviceModel::numerics
+typedef void (*NetKernel)(const DeviceModel, uint32_t, const float*, uint32_t, _Float16*, uint32_t, int, uint32_t);
+template <int MODE, bool LIGHT = false>
+static NetKernel net_kernel(uint32_t numerics) {
+	static constexpr NetKernel k[4] = {network_kernel<MODE, 0, LIGHT>, network_kernel<MODE, 1, LIGHT>, network_kernel<MODE, 2, LIGHT>, network_kernel<MODE, 3, LIGHT>};
+	return k[numerics & 3u];
+}
+int launch_network(const DeviceModel& m, NetOp op, uint32_t n, const float* d_in, uint32_t ld_in, void* d_out, uint32_t ld_out, int layout,
+                   int n_cus, void* stream, bool per_sample_light, uint32_t vis_layer, uint32_t vis_dim) {
 	if (n == 0) return NRS_OK;
 	if (per_sample_light && (!m.n_extra_dims || ld_in < 10u)) { snprintf(g_launch_err, sizeof(g_launch_err), "launch_network: per-sample light directions need n_extra_dims = 3 and ld_in >= 10"); return NRS_ERR_STATE; }
 	const uint32_t ld_light = per_sample_light ? 1u : 0u;
@@ -461,50 +396,36 @@ int launch_network(const DeviceModel& m, int mode, uint32_t n, const float* d_in
 	uint32_t grid = (n_tiles + kNetWaves - 1) / kNetWaves;
 	const uint32_t cap = (uint32_t)n_cus * 2; // resident workgroups: the tiles are strided over them
 	if (grid > cap) grid = cap;
-	hipStream_t s = (hipStream_t)stream;
-	_Float16* out = (_Float16*)d_out;
-#define NRS_NET_LAUNCH(MODE, NUM) hipLaunchKernelGGL((network_kernel<MODE, NUM>), dim3(grid), dim3(64 * kNetWaves), 0, s, m, n, d_in, ld_in, out, ld_out, layout)
-#define NRS_NET_MODE(MODE)                                      \
-	switch (m.numerics & 3u) {                                  \
-		case 0: NRS_NET_LAUNCH(MODE, 0); break;                 \
-		case 1: NRS_NET_LAUNCH(MODE, 1); break;                 \
-		case 2: NRS_NET_LAUNCH(MODE, 2); break;                 \
-		default: NRS_NET_LAUNCH(MODE, 3); break;                \
+	const bool light = m.n_extra_dims != 0u; // (a light-trained network has LIGHT twins of the two operators that run the rgb MLP)
+	NetKernel k;
+	switch (op) {
+		case kNetInference:
+		case kNetInferenceDeep:
+			k = light ? net_kernel<kNetInference, true>(m.numerics) : m.rgb_deep ? net_kernel<kNetInferenceDeep>(m.numerics) : net_kernel<kNetInference>(m.numerics);
+			break;
+		case kNetVisualizeActivation:
+			k = light ? net_kernel<kNetVisualizeActivation, true>(m.numerics) : net_kernel<kNetVisualizeActivation>(m.numerics);
+			layout = (int)(vis_layer | (vis_dim << 8)); // (in the kernel parameter it has no other use for)
+			break;
+		case kNetDensity: k = net_kernel<kNetDensity>(m.numerics); break;
+		case kNetInputGradient: k = net_kernel<kNetInputGradient>(m.numerics); break;
+		default: k = net_kernel<kNetEncode>(m.numerics); break;
 	}
-#define NRS_NET_LIGHT(MODE, NUM) hipLaunchKernelGGL((network_kernel<MODE, NUM, true>), dim3(grid), dim3(64 * kNetWaves), 0, s, m, n, d_in, ld_in, out, ld_out, layout, ld_light)
-#define NRS_NET_MODE_LIGHT(MODE)                                \
-	switch (m.numerics & 3u) {                                  \
-		case 0: NRS_NET_LIGHT(MODE, 0); break;                  \
-		case 1: NRS_NET_LIGHT(MODE, 1); break;                  \
-		case 2: NRS_NET_LIGHT(MODE, 2); break;                  \
-		default: NRS_NET_LIGHT(MODE, 3); break;                 \
-	}
-	if (mode == 0 && m.n_extra_dims) { NRS_NET_MODE_LIGHT(0) }
-	else if (mode == 4 && m.n_extra_dims) { NRS_NET_MODE_LIGHT(4) }
-	else if (mode == 0 && m.rgb_deep) { NRS_NET_MODE(5) }
-	else if (mode == 0) { NRS_NET_MODE(0) }
-	else if (mode == 1) { NRS_NET_MODE(1) }
-	else if (mode == 3) { NRS_NET_MODE(3) }
-	else if (mode == 4) { NRS_NET_MODE(4) }
-	else { NRS_NET_MODE(2) }
-#undef NRS_NET_MODE_LIGHT
-#undef NRS_NET_LIGHT
-#undef NRS_NET_MODE
-#undef NRS_NET_LAUNCH
+	hipLaunchKernelGGL(k, dim3(grid), dim3(64 * kNetWaves), 0, (hipStream_t)stream, m, n, d_in, ld_in, (_Float16*)d_out, ld_out, layout, ld_light);
 	NRS_LAUNCH_CHECK("network_kernel launch");
 	return NRS_OK;
 }
 
 // ---- the network on a regular grid: Testbed::get_density_on_grid (tn:4538) / get_rgba_on_grid (tn:4588) ------------------------
-// MODE 0: raw density (row 0 of the density MLP) per grid point, -10000 where the density grid says "empty" (grid_samples_half_to_float,
-//         tn:464-481); MODE 1: premultiplied rgba for a fixed view direction (compute_nerf_density, tn:624-635).  The reference
+// MODE (a GridEvalOp) kGridDensity: raw density (row 0 of the density MLP) per grid point, -10000 where the density grid says "empty" (grid_samples_half_to_float,
+//         tn:464-481); kGridRgba: premultiplied rgba for a fixed view direction (compute_nerf_density, tn:624-635).  The reference
 //         materialises the position array and runs the network in 2^20-point batches; here a lane generates its own point.
 struct GridEvalArgs {
 	uint32_t res[3];
 	float box_mn[3], box_mx[3];  // the box the grid spans (world units)
-	float dir01[3];              // MODE 1: warp_direction(ray_dir)
-	const float* density_grid;   // MODE 0: nullable
-	float* out;                  // MODE 0: float [n]; MODE 1: float4 [n]
+	float dir01[3];              // kGridRgba: warp_direction(ray_dir)
+	const float* density_grid;   // kGridDensity: nullable
+	float* out;                  // kGridDensity: float [n]; kGridRgba: float4 [n]
 };
 template <int MODE, int NUM>
 __global__ __launch_bounds__(256) void grid_eval_kernel(const DeviceModel m, const GridEvalArgs a) {
@@ -532,25 +453,17 @@ __global__ __launch_bounds__(256) void grid_eval_kernel(const DeviceModel m, con
 			wpos = warp_position(pos, m.aabb);
 		}
 		encode_num<NUM>(nm, gv, m.levels, sm.ml, fl, lane, g, wpos, have);
-		half8 sh;
-		if (MODE == 1) sh = encode_sh4(g, wdir);
-		uint32_t res_d = 0, res_rg = 0, res_b = 0;
-		#pragma unroll 1
-		for (int b = 0; b < 2; ++b) {
-			const int sel = (b != g) ? 1 : 0;
-			const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
-			const half8 dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, x0, x1);
-			half8 rout = dout;
-			if (MODE == 1) rout = rgb_mlp_num<NUM, true, true>(nm, sm.ml.w, lane, dout, sh, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
-			                                                  m.n_extra_dims ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_operand(g, m.light01[0], m.light01[1], m.light01[2]));
-			const u32x4 dd = __builtin_bit_cast(u32x4, dout), rr = __builtin_bit_cast(u32x4, rout);
-			uint32_t vd = dd[0], vrg = rr[0], vb = rr[1]; // rows 0..2 of a block sit in lanes 0..31
-			if (b == 1) { vd = xchg32u(vd); vrg = xchg32u(vrg); vb = xchg32u(vb); }
-			if (g == b) { res_d = vd; res_rg = vrg; res_b = vb; }
+		NetRaw raw = {0, 0, 0};
+		if (MODE == kGridRgba) {
+			const half8 sh = encode_sh4(g, wdir);
+			raw = wave_network<NUM>(nm, fl, sm.ml.w, lane, sh, sh, m.rgb_deep ? reinterpret_cast<const half8*>(m.wfrag) : nullptr,
+			                        m.n_extra_dims ? reinterpret_cast<const half8*>(m.wfrag) : nullptr, light_operand(g, m.light01[0], m.light01[1], m.light01[2]));
+		} else {
+			raw.d = wave_density<NUM>(nm, fl, sm.ml.w, lane);
 		}
 		if (!have) continue;
-		const float sigma_raw = (float)__builtin_bit_cast(half2v, res_d)[0];
-		if (MODE == 0) {
+		const float sigma_raw = (float)__builtin_bit_cast(half2v, raw.d)[0];
+		if (MODE == kGridDensity) {
 			float v = sigma_raw;
 			if (a.density_grid) {
 				const f3 upos = unwarp_position(wpos, m.aabb);
@@ -559,7 +472,7 @@ __global__ __launch_bounds__(256) void grid_eval_kernel(const DeviceModel m, con
 			}
 			a.out[s] = v;
 		} else {
-			const half2v hrg = __builtin_bit_cast(half2v, res_rg), hb = __builtin_bit_cast(half2v, res_b);
+			const half2v hrg = __builtin_bit_cast(half2v, raw.rg), hb = __builtin_bit_cast(half2v, raw.b);
 			const float alpha = clampf_(1.f - __expf(-network_to_density(sigma_raw, m.density_activation) / 100.0f), 0.0f, 1.0f);
 			reinterpret_cast<float4*>(a.out)[s] = make_float4(network_to_rgb((float)hrg[0], m.rgb_activation) * alpha, network_to_rgb((float)hrg[1], m.rgb_activation) * alpha,
 			                                                   network_to_rgb((float)hb[0], m.rgb_activation) * alpha, alpha);
@@ -568,7 +481,7 @@ __global__ __launch_bounds__(256) void grid_eval_kernel(const DeviceModel m, con
 	(void)j;
 }
 
-int launch_grid_eval(const DeviceModel& m, int mode, const uint32_t res[3], const float box_mn[3], const float box_mx[3], const float dir01[3],
+int launch_grid_eval(const DeviceModel& m, GridEvalOp op, const uint32_t res[3], const float box_mn[3], const float box_mx[3], const float dir01[3],
                      const float* d_density_grid, float* d_out, int n_cus, void* stream) {
 	GridEvalArgs a{};
 	for (int k = 0; k < 3; ++k) { a.res[k] = res[k]; a.box_mn[k] = box_mn[k]; a.box_mx[k] = box_mx[k]; a.dir01[k] = dir01 ? dir01[k] : 0.5f; }
@@ -580,9 +493,9 @@ int launch_grid_eval(const DeviceModel& m, int mode, const uint32_t res[3], cons
 	uint32_t grid = (n_tiles + 3) / 4; // 256-thread workgroups: 4 waves, a tile each per trip
 	const uint32_t cap = (uint32_t)n_cus * 8; // resident workgroups: the tiles are strided over them
 	if (grid > cap) grid = cap;
-	constexpr int R = kNumRuntime;
-	if (mode == 0) { if (m.numerics) hipLaunchKernelGGL((grid_eval_kernel<0, R>), dim3(grid), dim3(256), 0, (hipStream_t)stream, m, a); else hipLaunchKernelGGL((grid_eval_kernel<0, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, m, a); }
-	else { if (m.numerics) hipLaunchKernelGGL((grid_eval_kernel<1, R>), dim3(grid), dim3(256), 0, (hipStream_t)stream, m, a); else hipLaunchKernelGGL((grid_eval_kernel<1, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, m, a); }
+	static constexpr void (*kernels[2][2])(const DeviceModel, const GridEvalArgs) = { // [op][numerics != 0]
+		{grid_eval_kernel<kGridDensity, 0>, grid_eval_kernel<kGridDensity, kNumRuntime>}, {grid_eval_kernel<kGridRgba, 0>, grid_eval_kernel<kGridRgba, kNumRuntime>}};
+	hipLaunchKernelGGL(kernels[op == kGridDensity ? 0 : 1][m.numerics ? 1 : 0], dim3(grid), dim3(256), 0, (hipStream_t)stream, m, a);
 	NRS_LAUNCH_CHECK("grid_eval_kernel launch");
 	return NRS_OK;
 }

@@ -154,31 +154,13 @@ __global__ __launch_bounds__(64 * kBwdWaves) void network_backward_kernel(const 
 		#pragma unroll 1
 		for (int b = 0; b < 2; ++b) {
 			const int sel = (b != g) ? 1 : 0;
-			// ---- forward, as density_mlp / rgb_mlp compute it (fp32 accumulators), the hidden layers kept
+			// ---- forward: the layers density_mlp / rgb_mlp are composed of (fp32 accumulators), the hidden ones kept
 			const half8 x0 = load_features(wl.fl, lane, sel, 0), x1 = load_features(wl.fl, lane, sel, 1);
 			const half8 sh = sel ? sh_par : sh_own;
 			half8 h[4], h1[4], h2[4];
-			#pragma unroll
-			for (int mb = 0; mb < 2; ++mb) {
-				floatx16 c = mfma_first(W[NRS_FRAG_D1(mb, 0) * 64 + lane], x0);
-				c = NRS_MFMA(W[NRS_FRAG_D1(mb, 1) * 64 + lane], x1, c);
-				h[2 * mb] = relu_pack(c, 0); h[2 * mb + 1] = relu_pack(c, 8);
-				NRS_STAGE_FENCE();
-			}
-			half8 d;
-			{
-				floatx16 o = mfma_first(W[NRS_FRAG_D2(0) * 64 + lane], h[0]);
-				#pragma unroll
-				for (int ks = 1; ks < 4; ++ks) o = NRS_MFMA(W[NRS_FRAG_D2(ks) * 64 + lane], h[ks], o);
-				d = pack(o, 0);
-				NRS_STAGE_FENCE();
-			}
-			#pragma unroll
-			for (int mb = 0; mb < 2; ++mb) {
-				const floatx16 c = rgb_layer0_tile<false, false>(W, lane, mb, d, sh, nullptr, half8{});
-				h1[2 * mb] = relu_pack(c, 0); h1[2 * mb + 1] = relu_pack(c, 8);
-				NRS_STAGE_FENCE();
-			}
+			density_hidden<false>(W, lane, x0, x1, h[0], h[1], h[2], h[3]);
+			const half8 d = density_output<false>(W, lane, h[0], h[1], h[2], h[3]);
+			rgb_hidden0<false, false>(W, lane, d, sh, nullptr, half8{}, h1[0], h1[1], h1[2], h1[3]);
 			h2[0] = h1[0]; h2[1] = h1[1]; h2[2] = h1[2]; h2[3] = h1[3];
 			hidden_layer_64<false>(W, W + NRS_FRAG_R2(0, 0) * 64, lane, h2[0], h2[1], h2[2], h2[3]);
 			// (the output layer's values are not needed: it has no activation)

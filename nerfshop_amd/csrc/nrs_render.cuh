@@ -688,45 +688,12 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 		if (INTRO) {
 			NRS_FRESH_ARGS(m2i, a2i);
 			const nrs_render_params& p2i = a2i.p;
-			const bool acc16 = (nm & 2u) != 0u;
 			if (p2i.render_mode == NRS_RENDER_ENCODING_VIS) {
 				// network.visualize_activation(stream, layer, dim, positions_matrix, positions_matrix): unit `dim` of forward_activations(layer)
 				const uint32_t layer = p2i.visualized_layer, dim = p2i.visualized_dimension;
-				float v = 0.f;
-				if (layer == 0u) { // the hash-grid output: the slab still holds this round's features (level L of the own sample: see encode_to_lds)
-					const uint32_t L = dim >> 1;
-					const uint32_t w = ((L & 1u) == (uint32_t)g) ? fl.feat[L >> 1][0][lane] : fl.feat[L >> 1][1][lane ^ 32];
-					v = (float)__builtin_bit_cast(half2v, w)[dim & 1u];
-				} else if (LIGHT && layer == 2u && dim >= 32u) { // the Identity encoding of the light direction: units 32..34, then its padding ones
-					v = dim < 35u ? (float)(_Float16)m2i.light01[dim - 32u] : 1.0f;
-				} else if (layer == 2u && dim >= 16u) { // an SH coefficient of the own direction: 8 g .. 8 g + 7 are here, the others in the partner lane's sh_par
-					const uint32_t cidx = dim - 16u;
-					const float mine = (float)pick8(sh_own, (int)(cidx & 7u)), theirs = xchg32((float)pick8(sh_par, (int)(cidx & 7u)));
-					v = ((cidx >> 3) == (uint32_t)g) ? mine : theirs;
-				} else {
-					#pragma unroll 1
-					for (int b = 0; b < 2; ++b) {
-						const int sel = (b != g) ? 1 : 0;
-						const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
-						float val;
-						int half_of_row;
-						if (layer == 2u) { // a density-MLP output (rows 0..15 of the rgb network's input)
-							const half8 dout = acc16 ? density_mlp<true>(sm.ml.w, lane, x0, x1) : density_mlp<false>(sm.ml.w, lane, x0, x1);
-							const int e = (int)((dim & 3u) + 4u * (dim >> 3)); // element of row dim: row = (e & 3) + 8 (e >> 2) + 4 half
-							val = (float)pick8(dout, e);
-							half_of_row = (int)((dim >> 2) & 1u);
-						} else {
-							half8 din = x0;
-							if (layer >= 3u) din = acc16 ? density_mlp<true>(sm.ml.w, lane, x0, x1) : density_mlp<false>(sm.ml.w, lane, x0, x1);
-							const half8 shb = sel ? sh_par : sh_own;
-							val = acc16 ? mlp_hidden_activation<true, LIGHT>(sm.ml.w, lane, x0, x1, din, shb, layer, dim, deep_w, light_w, lb) : mlp_hidden_activation<false, LIGHT>(sm.ml.w, lane, x0, x1, din, shb, layer, dim, deep_w, light_w, lb);
-							half_of_row = tile_half(dim);
-						}
-						// the value of sample (b, j) sits in lane j + 32 * half_of_row; its ray is lane j + 32 * b
-						if (half_of_row != b) val = xchg32(val);
-						if (g == b) v = val;
-					}
-				}
+				// (the slab still holds this round's features; the frame's light direction for every sample)
+				const f3 light = mk3(m2i.light01[0], m2i.light01[1], m2i.light01[2]);
+				const float v = wave_visualize_activation<NUM, LIGHT>(nm, fl, sm.ml.w, lane, layer, dim, sh_own, sh_par, deep_w, light_w, lb, lb, light);
 				intro_v = mk3(fmaxf(-v, 0.0f), fmaxf(v, 0.0f), 0.0f); // extract_dimension_pos_neg_kernel (tiny-cuda-nn), rows 0..2
 				// The reference hands the network INPUT to visualize_activation as its output matrix (tn:2926): the sample's NerfCoordinate is overwritten --
 				// position = the three values above, dt = 1, direction = (1, 1, 1) -- and composite_kernel_nerf reads them back as warped_pos (the colour,
@@ -736,31 +703,8 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 				wdir = mk3(1.0f, 1.0f, 1.0f);
 			} else if (p2i.render_mode == NRS_RENDER_NORMALS) {
 				// network.input_gradient(stream, 3, positions, gradients): backward of 128 e_3 (see density_backward_features), then the grid's input gradient
-				uint32_t dfe[2][8];
-				#pragma unroll
-				for (int b = 0; b < 2; ++b) { // (unrolled: dfe must stay in registers)
-					const int sel = (b != g) ? 1 : 0;
-					const half8 x0 = load_features(fl, lane, sel, 0), x1 = load_features(fl, lane, sel, 1);
-					if (acc16) density_backward_features<true>(sm.ml.w, reinterpret_cast<const half8*>(m2i.wfrag), lane, x0, x1, dfe[b]);
-					else density_backward_features<false>(sm.ml.w, reinterpret_cast<const half8*>(m2i.wfrag), lane, x0, x1, dfe[b]);
-				}
-				// dL/dfeatures of sample (b, j) -> the slab, G[L][ray lane j + 32 b] (both lane halves of a column hold 8 of its 16 level pairs)
-				__builtin_amdgcn_wave_barrier();
-				uint32_t* G = &fl.feat[0][0][0];
-				#pragma unroll
-				for (int b = 0; b < 2; ++b)
-					#pragma unroll
-					for (int q = 0; q < 8; ++q) G[level_of_pair(q, g) * 64 + (lane & 31) + 32 * b] = dfe[b][q];
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-				float res[3] = {0.f, 0.f, 0.f};
 				const GridView gvi = make_grid_view(m2i);
-				const f3 q = act ? wpos : mk3(0.f, 0.f, 0.f);
-				#pragma unroll 1
-				for (int L = 0; L < (int)kLevels; ++L) level_input_gradient(gvi, m2i.levels[L], q, G[L * 64 + lane], res);
-				intro_v = mk3(res[0] * (1.0f / 128.0f), res[1] * (1.0f / 128.0f), res[2] * (1.0f / 128.0f));
-				__builtin_amdgcn_wave_barrier();
+				intro_v = wave_density_input_gradient<NUM>(nm, fl, sm.ml.w, reinterpret_cast<const half8*>(m2i.wfrag), gvi, m2i.levels, lane, act ? wpos : mk3(0.f, 0.f, 0.f));
 			}
 		}
 		// ---- membrane correction inputs (compute_poisson_full_residuals, tn:2867-2883) + the un-deformed network pass (tn:2890-2892) ----
@@ -793,15 +737,7 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 				if (p2b.poisson_target && __any(need_old)) {
 					const GridView gvb = make_grid_view(m2b);
 					encode_num<NUM, kQuads>(nm, gvb, m2b.levels, sm.ml, fl, lane, g, wpos0, need_old);
-					uint32_t old_d = 0;
-					#pragma unroll 1
-					for (int b = 0; b < 2; ++b) {
-						const int sel = (b != g) ? 1 : 0;
-						const half8 dout = density_mlp_num<NUM>(nm, sm.ml.w, lane, load_features(fl, lane, sel, 0), load_features(fl, lane, sel, 1));
-						uint32_t vd = __builtin_bit_cast(u32x4, dout)[0];
-						if (b == 1) vd = xchg32u(vd);
-						if (g == b) old_d = vd;
-					}
+					const uint32_t old_d = wave_density<NUM>(nm, fl, sm.ml.w, lane);
 					sigma_old_raw = (float)__builtin_bit_cast(half2v, old_d)[0];
 				}
 				// step 3: the boundary colour of the samples with a residual (the only ones whose colour is mixed, tn:796-805)
