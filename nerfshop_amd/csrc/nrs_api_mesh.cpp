@@ -147,7 +147,7 @@ int build_mesh(int device, void* stream, const uint32_t res3d[3], const float aa
 	}
 	HIP_TRY(hipMemcpyAsync(d_table.get(), packed.data(), packed.size(), hipMemcpyHostToDevice, s));
 	NRS_LAUNCH(launch_mc_count(g, d_density, reinterpret_cast<const uint8_t*>(d_table.get() + table_bytes), d_code.get(), d_block_sums.get(), s));
-	NRS_LAUNCH(launch_mc_scan(n_blocks, d_block_sums.get(), d_totals.get(), s));
+	NRS_LAUNCH(launch_tile_scan(n_blocks, 2, d_block_sums.get(), d_totals.get(), nullptr, s));
 	uint32_t totals[2] = {0, 0};
 	HIP_TRY(hipMemcpyAsync(totals, d_totals.get(), sizeof(totals), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s)); // the one synchronisation: the counts size the arrays (the reference reads its counters back the same way, :747-748)

@@ -27,7 +27,7 @@ int nrs_training_samples(nrs_model* m, void* stream, uint32_t n_rays, const floa
 	if (m->n_extra_dims != 0u) return fail(NRS_ERR_UNSUPPORTED, "nrs_training_samples: n_extra_dims (0 is supported: no training samples with light directions)");
 	if (!m->have_bitfield) return fail(NRS_ERR_STATE, "nrs_training_samples: occupancy not set (nrs_model_set_density_bitfield/_grid)");
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	if (n_rays) NRS_TRY(train_workspace(m, train_ws_words(kTrainSamplesWsWords, n_rays), "nrs_training_samples: workspace allocation"));
+	if (n_rays) NRS_TRY(train_workspace(m, train_ws_words<TrainSamplesWs>(n_rays), "nrs_training_samples: workspace allocation"));
 	TrainSamplesArgs a{};
 	a.n_rays = n_rays; a.rays = d_rays; a.jitter = d_jitter; a.cone = cone_angle_constant; a.max_samples = max_samples;
 	a.coords = d_coords_out; a.ld = ld; a.numsteps = d_numsteps_out; a.ray_indices = d_ray_indices_out; a.counters = d_counters;
@@ -62,7 +62,7 @@ int nrs_ray_loss(nrs_model* m, void* stream, const nrs_ray_loss_params* p, uint3
 		if (in0 < out1 && out0 < in1) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: d_coords_out overlaps d_coords");
 	}
 	HIP_TRY(hipSetDevice(m->ctx->device));
-	if (n_rays) NRS_TRY(train_workspace(m, train_ws_words(kRayLossWsWords, n_rays), "nrs_ray_loss: workspace allocation"));
+	if (n_rays) NRS_TRY(train_workspace(m, train_ws_words<RayLossWs>(n_rays), "nrs_ray_loss: workspace allocation"));
 	RayLossArgs a{};
 	a.p = *p; a.n_rays = n_rays; a.ray_counter = d_ray_counter; a.numsteps = d_numsteps; a.n_samples = n_samples; a.coords = d_coords; a.ld_in = ld_in;
 	a.output = d_output_fp16; a.ld_out = ld_out; a.out_layout = out_layout; a.target_rgba = d_target_rgba; a.background = d_background; a.origins = d_ray_origins;

@@ -15,6 +15,7 @@
 #include "nrs_internal.h"
 #include "nrs_launch.h"
 #include "nrs_device.cuh"
+#include "nrs_scan.cuh"
 #include "nrs_svd3.h"
 
 namespace nrs {
@@ -269,70 +270,27 @@ static void launch_tet_mark(uint32_t n_tets, float cells0, const float* d_verts,
 }
 
 // ---- exclusive scan of counts[kCells] -> offsets[kCells + 1] ----------------------------------------------------------------
+// Three launches: the sum of each tile of kScanTile cells, the one-workgroup scan over those sums (launch_tile_scan, which also leaves the total in offsets[n] and
+// *d_total), and the scan inside each tile on top of its prefix.  A thread owns 16 consecutive cells, read and written as 4 x uint4.
 __global__ __launch_bounds__(256) void scan_tile_sum_kernel(const uint32_t* __restrict__ counts, uint32_t* __restrict__ tile_sums) {
-	__shared__ uint32_t part[256];
 	const uint4* src = reinterpret_cast<const uint4*>(counts + (size_t)blockIdx.x * kScanTile) + threadIdx.x * 4;
-	uint32_t s = 0;
+	uint32_t s[1] = {0u}, before[1], total[1];
 	#pragma unroll
-	for (int q = 0; q < 4; ++q) { const uint4 v = src[q]; s += v.x + v.y + v.z + v.w; }
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (int st = 128; st > 0; st >>= 1) {
-		if ((int)threadIdx.x < st) part[threadIdx.x] += part[threadIdx.x + st];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) tile_sums[blockIdx.x] = part[0];
-}
-// one block: tile_sums -> exclusive prefix in place; total -> offsets[kCells] and scratch_total
-constexpr uint32_t kMaxScanTiles = 4096; // (the cell -> tet LUT scans 2560 tiles, the fine look-up table up to kFineScanTiles = 4096)
-__global__ __launch_bounds__(1024) void scan_tile_prefix_kernel(uint32_t* __restrict__ tile_sums, uint32_t* __restrict__ offsets_last,
-                                                                 uint32_t* __restrict__ total_out, uint32_t n_tiles) {
-	__shared__ uint32_t part[1024];
-	constexpr uint32_t per = (kMaxScanTiles + 1023) / 1024;
-	uint32_t v[per], s = 0;
-	const uint32_t kScanTiles = n_tiles; // (<= kMaxScanTiles)
-	#pragma unroll
-	for (uint32_t q = 0; q < per; ++q) {
-		const uint32_t i = threadIdx.x * per + q;
-		v[q] = i < kScanTiles ? tile_sums[i] : 0u;
-		s += v[q];
-	}
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (uint32_t d = 1; d < 1024; d <<= 1) { // Hillis-Steele inclusive scan
-		const uint32_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-		__syncthreads();
-		part[threadIdx.x] += add;
-		__syncthreads();
-	}
-	uint32_t run = part[threadIdx.x] - s;
-	#pragma unroll
-	for (uint32_t q = 0; q < per; ++q) {
-		const uint32_t i = threadIdx.x * per + q;
-		if (i < kScanTiles) tile_sums[i] = run;
-		run += v[q];
-	}
-	if (threadIdx.x == 1023) { *offsets_last = part[1023]; *total_out = part[1023]; }
+	for (int q = 0; q < 4; ++q) { const uint4 v = src[q]; s[0] += v.x + v.y + v.z + v.w; }
+	block_exclusive_add<256, 1>(s, before, total);
+	if (threadIdx.x == 0) tile_sums[blockIdx.x] = total[0];
 }
 __global__ __launch_bounds__(256) void scan_write_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ tile_prefix,
                                                           uint32_t* __restrict__ offsets) {
-	__shared__ uint32_t part[256];
 	const size_t base = (size_t)blockIdx.x * kScanTile + threadIdx.x * 16;
 	const uint4* src = reinterpret_cast<const uint4*>(counts + base);
-	uint32_t c[16], s = 0;
+	uint32_t c[16], s[1] = {0u}, before[1], total[1];
 	#pragma unroll
 	for (int q = 0; q < 4; ++q) { const uint4 v = src[q]; c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w; }
 	#pragma unroll
-	for (int q = 0; q < 16; ++q) s += c[q];
-	part[threadIdx.x] = s;
-	__syncthreads();
-	for (uint32_t d = 1; d < 256; d <<= 1) {
-		const uint32_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-		__syncthreads();
-		part[threadIdx.x] += add;
-		__syncthreads();
-	}
-	uint32_t run = tile_prefix[blockIdx.x] + part[threadIdx.x] - s;
+	for (int q = 0; q < 16; ++q) s[0] += c[q];
+	block_exclusive_add<256, 1>(s, before, total);
+	uint32_t run = tile_prefix[blockIdx.x] + before[0];
 	uint4* dst = reinterpret_cast<uint4*>(offsets + base);
 	#pragma unroll
 	for (int q = 0; q < 4; ++q) {
@@ -343,6 +301,14 @@ __global__ __launch_bounds__(256) void scan_write_kernel(const uint32_t* __restr
 		o.w = run; run += c[4 * q + 3];
 		dst[q] = o;
 	}
+}
+// counts[n_tiles * kScanTile] -> offsets[n_tiles * kScanTile + 1] and *d_total
+static int launch_cell_scan(uint32_t n_tiles, const uint32_t* d_counts, uint32_t* d_tile_sums, uint32_t* d_offsets, uint32_t* d_total, hipStream_t s) {
+	hipLaunchKernelGGL(scan_tile_sum_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums);
+	const int status = launch_tile_scan(n_tiles, 1, d_tile_sums, d_offsets + (size_t)n_tiles * kScanTile, d_total, s);
+	if (status != NRS_OK) return status;
+	hipLaunchKernelGGL(scan_write_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums, d_offsets);
+	return NRS_OK;
 }
 
 // ---- per byte of the touched-cell bitfield: sort each of its 8 cells' tet lists ascending, emit the byte, track the maximum ----
@@ -478,6 +444,7 @@ __global__ __launch_bounds__(1024) void lut_sort_big_kernel(const uint32_t* __re
 			for (uint32_t ww = w0; ww < w1; ++ww) mine += (uint32_t)__popc(sh[ww]);
 			part[threadIdx.x] = mine;
 			__syncthreads();
+			// (kept as it was: on block_exclusive_add<1024, 1> this kernel went from 64 to 71 VGPRs, 8 to 7 waves / SIMD, and spilled 8 SGPRs; profiles/scan_and_walk_once.md)
 			for (uint32_t d = 1; d < 1024; d <<= 1) { // Hillis-Steele inclusive scan
 				const uint32_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
 				__syncthreads();
@@ -728,9 +695,8 @@ int launch_lut_count_scan(uint32_t n_tets, const float* d_verts, const uint32_t*
                           uint32_t* d_offsets, uint32_t* d_total, unsigned long long* d_hit_masks, float cells0, void* stream) {
 	hipStream_t s = (hipStream_t)stream;
 	launch_tet_mark<false>(n_tets, cells0, d_verts, d_tets, d_counts, nullptr, nullptr, d_hit_masks, s);
-	hipLaunchKernelGGL(scan_tile_sum_kernel, dim3(kScanTiles), dim3(256), 0, s, d_counts, d_tile_sums);
-	hipLaunchKernelGGL(scan_tile_prefix_kernel, dim3(1), dim3(1024), 0, s, d_tile_sums, d_offsets + kCells, d_total, kScanTiles);
-	hipLaunchKernelGGL(scan_write_kernel, dim3(kScanTiles), dim3(256), 0, s, d_counts, d_tile_sums, d_offsets);
+	const int status = launch_cell_scan(kScanTiles, d_counts, d_tile_sums, d_offsets, d_total, s);
+	if (status != NRS_OK) return status;
 	NRS_LAUNCH_CHECK("tet LUT count/scan launch");
 	return NRS_OK;
 }
@@ -787,12 +753,11 @@ static void launch_fine_lists(const DeviceEdit& de, uint32_t* d_counts, const ui
 int launch_fine_count_scan(const DeviceEdit& de, uint32_t n_fine_cells, uint32_t* d_counts, uint32_t* d_tile_sums, uint32_t* d_fine_off, uint32_t* d_total, void* stream) {
 	hipStream_t s = (hipStream_t)stream;
 	const uint32_t n_tiles = (n_fine_cells + kScanTile - 1) / kScanTile, n_padded = n_tiles * kScanTile;
-	if (n_tiles == 0 || n_tiles > kMaxScanTiles) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: %u fine cells", n_fine_cells); return NRS_ERR_INVALID_ARG; }
+	if (n_tiles == 0 || n_tiles > kFineScanTiles) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: %u fine cells", n_fine_cells); return NRS_ERR_INVALID_ARG; }
 	if (n_padded != n_fine_cells && hipMemsetAsync(d_counts + n_fine_cells, 0, (size_t)(n_padded - n_fine_cells) * 4, s) != hipSuccess) { snprintf(g_launch_err, sizeof(g_launch_err), "fine look-up table: memset failed"); return NRS_ERR_HIP; }
 	launch_fine_lists<false>(de, d_counts, nullptr, nullptr, nullptr, s);
-	hipLaunchKernelGGL(scan_tile_sum_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums);
-	hipLaunchKernelGGL(scan_tile_prefix_kernel, dim3(1), dim3(1024), 0, s, d_tile_sums, d_fine_off + n_padded, d_total, n_tiles);
-	hipLaunchKernelGGL(scan_write_kernel, dim3(n_tiles), dim3(256), 0, s, d_counts, d_tile_sums, d_fine_off);
+	const int status = launch_cell_scan(n_tiles, d_counts, d_tile_sums, d_fine_off, d_total, s);
+	if (status != NRS_OK) return status;
 	NRS_LAUNCH_CHECK("fine look-up table count/scan launch");
 	return NRS_OK;
 }

@@ -276,6 +276,10 @@ int launch_detile(const nrs_render_params& p, uint32_t n_ranks, size_t rank_stri
                   float* d_image, void* stream);
 const char* launch_last_error();
 
+// The middle launch of a three-launch exclusive scan (nrs_scan.hip): d_sums [n_tiles][n_values] (n_values 1 or 2), one row per tile, becomes its exclusive prefix in
+// place, in one workgroup, for any n_tiles; d_totals[n_values] = the sums of all tiles; *d_total_copy (nullable) = d_totals[0] again.
+int launch_tile_scan(uint32_t n_tiles, uint32_t n_values, uint32_t* d_sums, uint32_t* d_totals, uint32_t* d_total_copy, void* stream);
+
 // cage-move chain on the device (nrs_cage.hip)
 constexpr uint32_t kLutScanTiles = kGridVol * kCascades / 4096;
 constexpr uint32_t kFineMaxCells = 16u << 20; // fine look-up table: at most 16 M fine cells (64 MB of offsets) per edit; the subdivision is chosen to fit
@@ -317,8 +321,7 @@ struct McGrid {
 };
 // per point: d_code = vertices before it in its block | crossing flags (x, y, z) << 10 | triangles before it in its block << 16; d_block_sums [2 * n_blocks] = vertices, triangles of a block
 int launch_mc_count(const McGrid& g, const float* d_density, const uint8_t* d_n_tris /* [256] */, uint32_t* d_code, uint32_t* d_block_sums, void* stream);
-// exclusive scan of the block sums in place (one workgroup); d_totals[2] = vertices, triangles of the lattice
-int launch_mc_scan(uint32_t n_blocks, uint32_t* d_block_sums, uint32_t* d_totals, void* stream);
+// then launch_tile_scan(n_blocks, 2, d_block_sums, d_totals, ...): d_totals[2] = vertices, triangles of the lattice
 // vertices (d_verts [n_verts x 3], d_vert_src [n_verts] = point * 4 + axis) and triangles (d_indices [n_tris x 3]) in ascending point order
 int launch_mc_emit(const McGrid& g, const float* d_density, const int8_t* d_table, uint32_t row_len, const uint32_t* d_code, const uint32_t* d_block_offs,
                    float* d_verts, uint32_t* d_vert_src, uint32_t* d_indices, void* stream);

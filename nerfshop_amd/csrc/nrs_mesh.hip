@@ -1,7 +1,7 @@
 // nrs_mesh.hip -- marching cubes on a density lattice and the per-vertex passes behind it (gfx950).
 //
 //   mc_count_kernel      crossings and triangles per lattice point, numbered inside a block of kMcBlock points with wave ballots (no atomics).
-//   mc_scan_kernel       exclusive scan over the blocks' sums: one workgroup.
+//   tile_scan_kernel     (nrs_scan.hip) exclusive scan over the blocks' sums: one workgroup.
 //   mc_emit_kernel       gen_vertices + gen_faces (marching_cubes.cu:217, :313) in the numbering the two passes above fixed: ascending (point, axis) / ascending cell, table order.
 //   mc_1ring_kernel      accumulate_1ring (:267) as a gather per vertex over the cells round its lattice edge: the sequential sum, no float atomics.
 //   mesh_color_*         generate_nerf_network_inputs_from_positions (tn:608) and extract_srgb_with_activation (tn:338) either side of the network operator.
@@ -13,6 +13,7 @@
 #include "nrs_internal.h"
 #include "nrs_launch.h"
 #include "nrs_device.cuh"
+#include "nrs_scan.cuh"
 
 namespace nrs {
 
@@ -47,7 +48,6 @@ static_assert(kMcBlock == 256, "a thread stages one byte of the 256 triangle cou
 __global__ __launch_bounds__(kMcBlock) void mc_count_kernel(const McGrid g, const float* __restrict__ d, const uint8_t* __restrict__ n_tris_of, uint32_t* __restrict__ code,
                                                              uint32_t* __restrict__ block_sums) {
 	__shared__ uint8_t s_n_tris[256];
-	__shared__ uint32_t s_wave[kMcBlock / 64][2];
 	s_n_tris[threadIdx.x] = n_tris_of[threadIdx.x];
 	__syncthreads();
 	const uint32_t i = blockIdx.x * kMcBlock + threadIdx.x;
@@ -63,58 +63,14 @@ __global__ __launch_bounds__(kMcBlock) void mc_count_kernel(const McGrid g, cons
 	}
 	const unsigned long long bx = __ballot(fx), by = __ballot(fy), bz = __ballot(fz);
 	const unsigned long long t0 = __ballot(nt & 1u), t1 = __ballot(nt & 2u), t2 = __ballot(nt & 4u), t3 = __ballot(nt & 8u);
-	uint32_t v_before = lanes_below(bx) + lanes_below(by) + lanes_below(bz);
-	uint32_t t_before = lanes_below(t0) + 2u * lanes_below(t1) + 4u * lanes_below(t2) + 8u * lanes_below(t3);
-	const uint32_t wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63u) == 0u) {
-		s_wave[wave][0] = (uint32_t)(__popcll(bx) + __popcll(by) + __popcll(bz));
-		s_wave[wave][1] = (uint32_t)(__popcll(t0) + 2 * __popcll(t1) + 4 * __popcll(t2) + 8 * __popcll(t3));
-	}
-	__syncthreads();
-	uint32_t v_total = 0, t_total = 0;
-	#pragma unroll
-	for (uint32_t w = 0; w < kMcBlock / 64; ++w) {
-		if (w < wave) { v_before += s_wave[w][0]; t_before += s_wave[w][1]; }
-		v_total += s_wave[w][0];
-		t_total += s_wave[w][1];
-	}
+	const uint32_t in_wave[2] = {(uint32_t)(__popcll(bx) + __popcll(by) + __popcll(bz)), (uint32_t)(__popcll(t0) + 2 * __popcll(t1) + 4 * __popcll(t2) + 8 * __popcll(t3))};
+	uint32_t before[2], total[2]; // vertices, triangles
+	block_combine_waves<kMcBlock, 2>(in_wave, before, total);
+	const uint32_t v_before = before[0] + lanes_below(bx) + lanes_below(by) + lanes_below(bz);
+	const uint32_t t_before = before[1] + lanes_below(t0) + 2u * lanes_below(t1) + 4u * lanes_below(t2) + 8u * lanes_below(t3);
 	// v_before <= 3 * 255 (10 bits), t_before <= 10 * 255 (12 bits)
 	if (i < g.n) code[i] = v_before | ((uint32_t)fx << 10) | ((uint32_t)fy << 11) | ((uint32_t)fz << 12) | (t_before << 16);
-	if (threadIdx.x == 0) { block_sums[2 * blockIdx.x] = v_total; block_sums[2 * blockIdx.x + 1] = t_total; }
-}
-
-// One workgroup of 1024 threads: thread t owns a contiguous run of blocks, sums it, the 1024 sums are scanned across the workgroup, and the run is rewritten as running
-// prefixes.  (2 x 4 bytes per 256 lattice points: 1 MiB at 512^3, L2-resident.)
-constexpr uint32_t kMcScanThreads = 1024;
-__global__ __launch_bounds__(kMcScanThreads) void mc_scan_kernel(uint32_t n_blocks, uint32_t* __restrict__ sums, uint32_t* __restrict__ totals) {
-	__shared__ uint32_t s_wave[kMcScanThreads / 64][2];
-	const uint32_t per = (n_blocks + kMcScanThreads - 1) / kMcScanThreads;
-	const uint32_t first = min(threadIdx.x * per, n_blocks), last = min(first + per, n_blocks);
-	uint32_t v = 0, t = 0;
-	for (uint32_t b = first; b < last; ++b) { v += sums[2 * b]; t += sums[2 * b + 1]; }
-	uint32_t vi = v, ti = t; // inclusive scan inside the wave
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	#pragma unroll
-	for (uint32_t s = 1; s < 64; s <<= 1) {
-		const uint32_t vu = __shfl_up(vi, s), tu = __shfl_up(ti, s);
-		if (lane >= s) { vi += vu; ti += tu; }
-	}
-	if (lane == 63u) { s_wave[wave][0] = vi; s_wave[wave][1] = ti; }
-	__syncthreads();
-	uint32_t v_run = vi - v, t_run = ti - t, v_all = 0, t_all = 0;
-	for (uint32_t w = 0; w < kMcScanThreads / 64; ++w) {
-		if (w < wave) { v_run += s_wave[w][0]; t_run += s_wave[w][1]; }
-		v_all += s_wave[w][0];
-		t_all += s_wave[w][1];
-	}
-	for (uint32_t b = first; b < last; ++b) {
-		const uint32_t bv = sums[2 * b], bt = sums[2 * b + 1];
-		sums[2 * b] = v_run;
-		sums[2 * b + 1] = t_run;
-		v_run += bv;
-		t_run += bt;
-	}
-	if (threadIdx.x == 0) { totals[0] = v_all; totals[1] = t_all; }
+	if (threadIdx.x == 0) { block_sums[2 * blockIdx.x] = total[0]; block_sums[2 * blockIdx.x + 1] = total[1]; }
 }
 
 // number of the vertex on the lattice edge that leaves point j along `axis` (the caller knows it is crossed)
@@ -255,11 +211,6 @@ static uint32_t mc_blocks(uint32_t n) { return (n + kMcBlock - 1) / kMcBlock; }
 int launch_mc_count(const McGrid& g, const float* d_density, const uint8_t* d_n_tris, uint32_t* d_code, uint32_t* d_block_sums, void* stream) {
 	hipLaunchKernelGGL(mc_count_kernel, dim3(mc_blocks(g.n)), dim3(kMcBlock), 0, (hipStream_t)stream, g, d_density, d_n_tris, d_code, d_block_sums);
 	NRS_LAUNCH_CHECK("mc_count_kernel launch");
-	return NRS_OK;
-}
-int launch_mc_scan(uint32_t n_blocks, uint32_t* d_block_sums, uint32_t* d_totals, void* stream) {
-	hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kMcScanThreads), 0, (hipStream_t)stream, n_blocks, d_block_sums, d_totals);
-	NRS_LAUNCH_CHECK("mc_scan_kernel launch");
 	return NRS_OK;
 }
 int launch_mc_emit(const McGrid& g, const float* d_density, const int8_t* d_table, uint32_t row_len, const uint32_t* d_code, const uint32_t* d_block_offs,

@@ -1,19 +1,44 @@
 // nrs_train.h -- what nrs_api_train.cpp and nrs_train.hip share: the argument blocks and launchers of the training-ray path (include/nrs.h, "training rays").
 // Not part of the public ABI.
 #pragma once
+#include <hip/hip_runtime.h>
 #include "nrs_internal.h"
 
 namespace nrs {
 
-// Per-ray workspace, in 32-bit words, structure of arrays over n_rays (the model owns it: nrs_model::d_train_ws).
-//   generator: count | base | slot, then one word: the end of the last emitted ray
-//   ray loss:  M | cbase | C[3] | g[3] | mean loss / n_rays
-// Behind the per-ray arrays: the generator's `end` word, then the scan's tile sums, 2 per 1024 rays, and its 2 totals.
-constexpr uint32_t kTrainSamplesWsWords = 3;
-constexpr uint32_t kRayLossWsWords = 9;
-inline uint32_t train_scan_tiles(uint32_t n_rays) { return (n_rays + 1023u) / 1024u; }
-inline size_t train_ws_words(uint32_t per_ray, uint32_t n_rays) { return (size_t)per_ray * n_rays + 1 + 2 * (size_t)train_scan_tiles(n_rays) + 2; }
 constexpr uint32_t kTrainMaxRays = 1u << 21; // 2^21 rays x NERF_STEPS = 2^31 samples: every sum of counts fits 32 bits
+constexpr uint32_t kTrainScanTile = 1024;    // rays per tile of the scan over the per-ray counts
+inline uint32_t train_scan_tiles(uint32_t n_rays) { return (n_rays + kTrainScanTile - 1u) / kTrainScanTile; }
+// what the scan keeps behind a view's per-ray arrays: two sums per tile, then the two totals
+inline size_t train_scan_words(uint32_t n_rays) { return 2 * (size_t)train_scan_tiles(n_rays) + 2; }
+
+// The per-ray workspace (the model owns it: nrs_model::d_train_ws) as each of its two users sees it: 32-bit words, arrays of n_rays, laid out in the order of the
+// members, the scan's words last.  A view is built from (ws, n_rays) wherever it is needed.
+struct TrainSamplesWs { // the generator
+	uint32_t *count, *base, *slot; // [n_rays] each: samples of the ray, samples in front of it, rays with samples in front of it
+	uint32_t* end;                 // one word: where the last emitted ray ends
+	uint32_t* tiles;               // [train_scan_words]
+	__host__ __device__ TrainSamplesWs(uint32_t* ws, uint32_t n) : count(ws), base(count + n), slot(base + n), end(slot + n), tiles(end + 1) {}
+};
+struct RayLossWs { // the loss
+	uint32_t *M, *cbase;   // [n_rays] each: samples consumed, compact samples in front of the ray
+	float *C[3], *g[3];    // [n_rays] each: the composited colour and dLoss/dC
+	float* loss;           // [n_rays]: mean loss / n_rays
+	uint32_t* tiles;       // [train_scan_words]
+	__host__ __device__ RayLossWs(uint32_t* ws, uint32_t n) : M(ws), cbase(M + n) {
+		float* f = reinterpret_cast<float*>(cbase + n);
+		for (int k = 0; k < 3; ++k, f += n) C[k] = f;
+		for (int k = 0; k < 3; ++k, f += n) g[k] = f;
+		loss = f;
+		tiles = reinterpret_cast<uint32_t*>(loss + n);
+	}
+};
+// the words a view spans
+template <class View>
+inline size_t train_ws_words(uint32_t n_rays) {
+	uint32_t* const ws = nullptr;
+	return (size_t)(View(ws, n_rays).tiles - ws) + train_scan_words(n_rays);
+}
 
 struct TrainSamplesArgs {
 	uint32_t n_rays;
@@ -26,7 +51,7 @@ struct TrainSamplesArgs {
 	uint32_t* numsteps;      // [n_rays][2]
 	uint32_t* ray_indices;   // [n_rays]
 	uint32_t* counters;      // [2]
-	uint32_t* ws;            // train_ws_words(kTrainSamplesWsWords, n_rays) words (NULL when n_rays == 0)
+	uint32_t* ws;            // TrainSamplesWs: train_ws_words<TrainSamplesWs>(n_rays) words (NULL when n_rays == 0)
 };
 
 struct RayLossArgs {
@@ -50,7 +75,7 @@ struct RayLossArgs {
 	int dl_layout;
 	float* loss;                 // nullable
 	uint32_t* counter_out;
-	uint32_t* ws;                // train_ws_words(kRayLossWsWords, n_rays) words (NULL when n_rays == 0)
+	uint32_t* ws;                // RayLossWs: train_ws_words<RayLossWs>(n_rays) words (NULL when n_rays == 0)
 };
 
 int launch_training_samples(const DeviceModel& m, const TrainSamplesArgs& a, void* stream);

@@ -1,7 +1,7 @@
 // nrs_train.hip -- the training-ray path (gfx950): rays -> network inputs, and network outputs -> ray loss + dL/doutput, compacted.
 //
 //   train_count_kernel     generate_training_samples_nerf's first walk (tn:1188-1213): samples per ray.
-//   train_tile_*_kernel    exclusive scan of the per-ray counts in input order: tile sums, mc_scan_kernel (nrs_mesh.hip) over them, the scan inside each tile.  It stands where the
+//   train_tile_*_kernel    exclusive scan of the per-ray counts in input order: tile sums, tile_scan_kernel (nrs_scan.hip) over them, the scan inside each tile.  It stands where the
 //                          reference has atomicAdd (tn:1218, :1225, :1834), so the layout does not depend on arrival order.
 //   train_write_kernel     the second walk (tn:1232-1246) into the slots the scan fixed; train_fill_kernel zeroes the records behind the last emitted ray.
 //   ray_loss_forward_kernel   compute_loss_kernel_train_nerf's first loop, the target and loss_and_gradient (tn:1745-1828, :1847): M, C, g, loss per ray.
@@ -14,6 +14,7 @@
 #include "nrs_internal.h"
 #include "nrs_launch.h"
 #include "nrs_device.cuh"
+#include "nrs_scan.cuh"
 #include "nrs_train.h"
 
 namespace nrs {
@@ -73,73 +74,60 @@ __global__ __launch_bounds__(kTrainBlock) void train_count_kernel(const DeviceMo
 	const uint32_t i = blockIdx.x * kTrainBlock + threadIdx.x;
 	if (i >= a.n_rays) return;
 	const TrainRay r = train_ray(m, a, i);
-	a.ws[i] = r.ok ? train_march<false>(m, r, a.cone, kTrainSteps, nullptr, 0) : 0u;
+	TrainSamplesWs(a.ws, a.n_rays).count[i] = r.ok ? train_march<false>(m, r, a.cone, kTrainSteps, nullptr, 0) : 0u;
 }
 
-// The exclusive scan of the per-ray counts, in three launches as the mesh path does it: sums per tile of kScanTile rays (coalesced, any number of workgroups), the
-// one-workgroup scan of the tile sums (mc_scan_kernel itself: 2 x 4 bytes per 1024 rays), and the scan inside each tile on top of its offset.
+// The exclusive scan of the per-ray counts, in three launches as the mesh path does it: sums per tile of kTrainScanTile rays (coalesced, any number of workgroups), the
+// one-workgroup scan of the tile sums (launch_tile_scan: 2 x 4 bytes per 1024 rays), and the scan inside each tile on top of its offset.
 // Two sums per ray: its count and whether it has one.  count / base / slot: three arrays of n words; rays at or past *live (NULL: all n) count as empty.
 // GEN (the generator): slot = the rays with samples before this one -- its place among the emitted rays, because a ray with samples that is dropped puts every later
 // one past max_samples too (bases only grow) -- out[0] = emitted rays, out[1] = the sum of all counts, *end = where the last emitted ray ends.
 // Otherwise (the loss): out[0] = the sum of all counts.
-constexpr uint32_t kScanTile = 1024, kScanThreads = 256, kScanPer = kScanTile / kScanThreads;
+constexpr uint32_t kScanThreads = 256, kScanPer = kTrainScanTile / kScanThreads;
+// a thread's kScanPer consecutive rays of tile blockIdx.x: their counts (0 at or past n) and the two sums over them
+struct TileCounts { uint32_t first, c[kScanPer], sum[2]; };
+__device__ __forceinline__ TileCounts load_tile_counts(uint32_t n, const uint32_t* __restrict__ live, const uint32_t* __restrict__ count) {
+	TileCounts t;
+	if (live) n = min(n, *live);
+	t.first = blockIdx.x * kTrainScanTile + threadIdx.x * kScanPer;
+	t.sum[0] = t.sum[1] = 0u;
+	#pragma unroll
+	for (uint32_t k = 0; k < kScanPer; ++k) { t.c[k] = t.first + k < n ? count[t.first + k] : 0u; t.sum[0] += t.c[k]; t.sum[1] += t.c[k] ? 1u : 0u; }
+	return t;
+}
 // tiles: [n_tiles][2] sums, then [2] totals
 __global__ __launch_bounds__(kScanThreads) void train_tile_sums_kernel(uint32_t n, const uint32_t* __restrict__ live, const uint32_t* __restrict__ count,
                                                                         uint32_t* __restrict__ tiles, uint32_t* __restrict__ zero0, uint32_t* __restrict__ zero1) {
-	__shared__ uint32_t s_wave[kScanThreads / 64][2];
 	if (blockIdx.x == 0 && threadIdx.x == 0) { if (zero0) *zero0 = 0u; if (zero1) *zero1 = 0u; } // what train_tile_scan_kernel<true> takes maxima into
-	if (live) n = min(n, *live);
-	const uint32_t first = blockIdx.x * kScanTile + threadIdx.x * kScanPer;
-	uint32_t v = 0, t = 0;
-	#pragma unroll
-	for (uint32_t k = 0; k < kScanPer; ++k) if (first + k < n) { const uint32_t c = count[first + k]; v += c; t += c ? 1u : 0u; }
-	#pragma unroll
-	for (uint32_t d = 32; d; d >>= 1) { v += (uint32_t)__shfl_xor((int)v, (int)d); t += (uint32_t)__shfl_xor((int)t, (int)d); }
-	if ((threadIdx.x & 63u) == 0u) { s_wave[threadIdx.x >> 6][0] = v; s_wave[threadIdx.x >> 6][1] = t; }
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t vs = 0, ts = 0;
-		for (uint32_t w = 0; w < kScanThreads / 64; ++w) { vs += s_wave[w][0]; ts += s_wave[w][1]; }
-		tiles[2 * blockIdx.x] = vs;
-		tiles[2 * blockIdx.x + 1] = ts;
-	}
+	const TileCounts t = load_tile_counts(n, live, count);
+	uint32_t before[2], total[2];
+	block_exclusive_add<kScanThreads, 2>(t.sum, before, total);
+	if (threadIdx.x == 0) { tiles[2 * blockIdx.x] = total[0]; tiles[2 * blockIdx.x + 1] = total[1]; }
 }
 template <bool GEN>
 __global__ __launch_bounds__(kScanThreads) void train_tile_scan_kernel(uint32_t n, const uint32_t* __restrict__ live, const uint32_t* __restrict__ count,
                                                                         const uint32_t* __restrict__ tiles, const uint32_t* __restrict__ totals,
                                                                         uint32_t* __restrict__ base, uint32_t* __restrict__ slot, uint32_t max_samples,
                                                                         uint32_t* __restrict__ out, uint32_t* __restrict__ end) {
-	__shared__ uint32_t s_wave[kScanThreads / 64][2];
 	__shared__ uint32_t s_emitted, s_end;
 	if (threadIdx.x == 0) { s_emitted = 0; s_end = 0; }
 	if (live) n = min(n, *live);
-	const uint32_t first = blockIdx.x * kScanTile + threadIdx.x * kScanPer;
-	uint32_t c[kScanPer], v = 0, t = 0;
-	#pragma unroll
-	for (uint32_t k = 0; k < kScanPer; ++k) { c[k] = first + k < n ? count[first + k] : 0u; v += c[k]; t += c[k] ? 1u : 0u; }
-	uint32_t vi = v, ti = t; // inclusive scan inside the wave
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) {
-		const uint32_t vu = (uint32_t)__shfl_up((int)vi, d), tu = (uint32_t)__shfl_up((int)ti, d);
-		if (lane >= d) { vi += vu; ti += tu; }
-	}
-	if (lane == 63u) { s_wave[wave][0] = vi; s_wave[wave][1] = ti; }
-	__syncthreads();
-	uint32_t v_run = tiles[2 * blockIdx.x] + vi - v, t_run = tiles[2 * blockIdx.x + 1] + ti - t; // (tiles: exclusive after the one-workgroup scan)
-	for (uint32_t w = 0; w < kScanThreads / 64; ++w) if (w < wave) { v_run += s_wave[w][0]; t_run += s_wave[w][1]; }
+	const TileCounts t = load_tile_counts(n, nullptr, count);
+	uint32_t before[2], total[2];
+	block_exclusive_add<kScanThreads, 2>(t.sum, before, total); // (its barrier also orders s_emitted = 0 in front of the maxima below)
+	uint32_t v_run = tiles[2 * blockIdx.x] + before[0], t_run = tiles[2 * blockIdx.x + 1] + before[1]; // (tiles: exclusive after the one-workgroup scan)
 	uint32_t emitted_to = 0, my_end = 0;
 	#pragma unroll
 	for (uint32_t k = 0; k < kScanPer; ++k) {
-		if (first + k < n) {
-			base[first + k] = v_run;
+		if (t.first + k < n) {
+			base[t.first + k] = v_run;
 			if (GEN) {
-				slot[first + k] = t_run;
-				if (c[k] && v_run <= max_samples && c[k] <= max_samples - v_run) { emitted_to = t_run + 1u; my_end = v_run + c[k]; }
+				slot[t.first + k] = t_run;
+				if (t.c[k] && v_run <= max_samples && t.c[k] <= max_samples - v_run) { emitted_to = t_run + 1u; my_end = v_run + t.c[k]; }
 			}
 		}
-		v_run += c[k];
-		t_run += c[k] ? 1u : 0u;
+		v_run += t.c[k];
+		t_run += t.c[k] ? 1u : 0u;
 	}
 	if (GEN) { // the emitted rays are the first of the rays with samples: their number is the last one's slot + 1.  Integer maxima: the result does not depend on the order
 		if (emitted_to) { atomicMax(&s_emitted, emitted_to); atomicMax(&s_end, my_end); }
@@ -150,7 +138,7 @@ __global__ __launch_bounds__(kScanThreads) void train_tile_scan_kernel(uint32_t 
 		}
 	} else if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = totals[0];
 }
-// tiles: 2 * train_scan_tiles(n) + 2 words of workspace
+// tiles: train_scan_words(n) words of workspace
 template <bool GEN>
 static int launch_train_scan(uint32_t n, const uint32_t* live, const uint32_t* count, uint32_t* tiles, uint32_t* base, uint32_t* slot, uint32_t max_samples, uint32_t* out,
                              uint32_t* end, hipStream_t st) {
@@ -158,7 +146,7 @@ static int launch_train_scan(uint32_t n, const uint32_t* live, const uint32_t* c
 	uint32_t* totals = tiles + 2 * (size_t)n_tiles;
 	hipLaunchKernelGGL(train_tile_sums_kernel, dim3(n_tiles), dim3(kScanThreads), 0, st, n, live, count, tiles, GEN ? out : nullptr, GEN ? end : nullptr);
 	NRS_LAUNCH_CHECK("train_tile_sums_kernel launch");
-	const int status = launch_mc_scan(n_tiles, tiles, totals, st);
+	const int status = launch_tile_scan(n_tiles, 2, tiles, totals, nullptr, st);
 	if (status != NRS_OK) return status;
 	hipLaunchKernelGGL(train_tile_scan_kernel<GEN>, dim3(n_tiles), dim3(kScanThreads), 0, st, n, live, count, (const uint32_t*)tiles, (const uint32_t*)totals, base, slot, max_samples,
 	                   out, end);
@@ -169,9 +157,10 @@ static int launch_train_scan(uint32_t n, const uint32_t* live, const uint32_t* c
 __global__ __launch_bounds__(kTrainBlock) void train_write_kernel(const DeviceModel m, const TrainSamplesArgs a) {
 	const uint32_t i = blockIdx.x * kTrainBlock + threadIdx.x;
 	if (i >= a.n_rays) return;
-	const uint32_t j = a.ws[i], base = a.ws[a.n_rays + i];
+	const TrainSamplesWs ws(a.ws, a.n_rays);
+	const uint32_t j = ws.count[i], base = ws.base[i];
 	if (j == 0u || base > a.max_samples || j > a.max_samples - base) return; // tn:1214-1221
-	const uint32_t s = a.ws[2 * a.n_rays + i];
+	const uint32_t s = ws.slot[i];
 	a.ray_indices[s] = i;
 	a.numsteps[2 * s] = j;
 	a.numsteps[2 * s + 1] = base;
@@ -192,10 +181,11 @@ int launch_training_samples(const DeviceModel& m, const TrainSamplesArgs& a, voi
 	uint32_t* end = nullptr;
 	if (a.n_rays) {
 		const uint32_t blocks = (a.n_rays + kTrainBlock - 1) / kTrainBlock;
-		end = a.ws + (size_t)kTrainSamplesWsWords * a.n_rays;
+		const TrainSamplesWs ws(a.ws, a.n_rays);
+		end = ws.end;
 		hipLaunchKernelGGL(train_count_kernel, dim3(blocks), dim3(kTrainBlock), 0, st, m, a);
 		NRS_LAUNCH_CHECK("train_count_kernel launch");
-		const int status = launch_train_scan<true>(a.n_rays, nullptr, a.ws, end + 1, a.ws + a.n_rays, a.ws + 2 * (size_t)a.n_rays, a.max_samples, a.counters, end, st);
+		const int status = launch_train_scan<true>(a.n_rays, nullptr, ws.count, ws.tiles, ws.base, ws.slot, a.max_samples, a.counters, end, st);
 		if (status != NRS_OK) return status;
 		hipLaunchKernelGGL(train_write_kernel, dim3(blocks), dim3(kTrainBlock), 0, st, m, a);
 		NRS_LAUNCH_CHECK("train_write_kernel launch");
@@ -283,8 +273,6 @@ __device__ __forceinline__ uint32_t live_rays(const RayLossArgs& a) { return a.r
 
 // The ray's target, the background behind a ray that was not stopped, loss_and_gradient, and the ray's row of the workspace (tn:1789-1828, :1847-1858)
 __device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uint32_t M, uint32_t n, f3 C, float T) {
-	uint32_t* ws_m = a.ws;
-	float* ws_f = reinterpret_cast<float*>(a.ws) + 2 * (size_t)a.n_rays; // C[3] | g[3] | loss, n_rays apart
 	// tn:1789-1828
 	const nrs_ray_loss_params& p = a.p;
 	const float* bgp = a.background ? a.background + 3 * (size_t)i : p.background;
@@ -309,48 +297,30 @@ __device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uin
 	loss_and_gradient(p.loss_type, target.x, C.x, lx, gx);
 	loss_and_gradient(p.loss_type, target.y, C.y, ly, gy);
 	loss_and_gradient(p.loss_type, target.z, C.z, lz, gz);
-	const size_t R = a.n_rays;
-	ws_m[i] = M;
-	ws_f[i] = C.x; ws_f[R + i] = C.y; ws_f[2 * R + i] = C.z;
-	ws_f[3 * R + i] = gx; ws_f[4 * R + i] = gy; ws_f[5 * R + i] = gz;
-	ws_f[6 * R + i] = sum3(lx, ly, lz) / 3.0f / (float)a.n_rays;
+	const RayLossWs ws(a.ws, a.n_rays);
+	ws.M[i] = M;
+	ws.C[0][i] = C.x; ws.C[1][i] = C.y; ws.C[2][i] = C.z;
+	ws.g[0][i] = gx; ws.g[1][i] = gy; ws.g[2][i] = gz;
+	ws.loss[i] = sum3(lx, ly, lz) / 3.0f / (float)a.n_rays;
 }
 
 // ---- one lane per sample -------------------------------------------------------------------------------------------------------------------------------------
 // A wave owns 64 consecutive rays (lane k holds ray k's count and base) and walks them in packets: consecutive rays whose counts fit into 64 lanes, one lane per
 // sample, so that the loads of outputs and records are contiguous over the wave; a ray of more than 64 samples goes alone, in chunks of 64, and carries (T, C) from
-// chunk to chunk in wave-uniform registers.  T in front of a sample is a segmented exclusive product scan of 1 - alpha; C three segmented sums.  The early stop is a
-// predicate per lane (T in front of it < EPS), balloted: the first set bit of a segment is the ray's M, and every lane at or behind it contributes exactly nothing.
+// chunk to chunk in wave-uniform registers.  T in front of a sample is a segmented exclusive product scan of 1 - alpha; C three segmented sums.
+//
+// walk_samples is that walk, for both passes over the samples: the forward pass reads a ray's C out of it, the gradient pass the C in front of every sample, and
+// dL/doutput needs their difference -- what lies behind the sample -- to be exact (0 behind the last consumed sample of a stopped ray).  It is, because both values are
+// this one function's: the same lanes scanned in the same order.  The passes differ only in the weight they give a sample (the forward pass stops a ray) and in what
+// they do with a chunk's scans.
 constexpr uint32_t kWaveBlock = 256;
 __device__ __forceinline__ uint32_t shfl_u(uint32_t v, uint32_t lane) { return (uint32_t)__shfl((int)v, (int)lane); }
+__device__ __forceinline__ f3 shfl3(f3 v, uint32_t lane) { return mk3(__shfl(v.x, (int)lane), __shfl(v.y, (int)lane), __shfl(v.z, (int)lane)); }
 // inclusive scans over the lanes st..lane of a segment (lane >= st)
-__device__ __forceinline__ float seg_scan_mul(float x, uint32_t lane, uint32_t st) {
-	#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) { const float v = __shfl_up(x, d); if (lane >= st + d) x *= v; }
-	return x;
-}
-__device__ __forceinline__ float seg_scan_add(float x, uint32_t lane, uint32_t st) {
-	#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) { const float v = __shfl_up(x, d); if (lane >= st + d) x += v; }
-	return x;
-}
+__device__ __forceinline__ float seg_scan_mul(float x, uint32_t lane, uint32_t st) { return wave_segmented_scan(x, lane, st, [](float a, float b) { return a * b; }); }
+__device__ __forceinline__ float seg_scan_add(float x, uint32_t lane, uint32_t st) { return wave_segmented_scan(x, lane, st, [](float a, float b) { return a + b; }); }
 __device__ __forceinline__ unsigned long long lane_range(uint32_t first, uint32_t last) { // bits first..last
 	return ((2ull << last) - 1ull) & ~((1ull << first) - 1ull);
-}
-// A packet of the wave's walk: rays c..e (long: ray c alone), `tot` samples
-struct Packet { uint32_t e, tot; bool lng; };
-__device__ __forceinline__ Packet next_packet(uint32_t c, uint32_t lane, uint32_t n, uint32_t P, uint32_t E) {
-	Packet k;
-	const uint32_t Nc = shfl_u(n, c), Ec = shfl_u(E, c);
-	k.lng = Nc > 64u;
-	k.e = c;
-	k.tot = Nc;
-	if (!k.lng) {
-		const unsigned long long fit = __ballot(lane >= c && P - Ec <= 64u); // P grows with the lane: a run that starts at c
-		k.e = c + (uint32_t)__popcll(fit) - 1u;
-		k.tot = shfl_u(P, k.e) - Ec;
-	}
-	return k;
 }
 // the ray of the packet that sample lane `lane` belongs to: the first k in c..e with P_k - Ec > lane (every lane takes the same six steps)
 __device__ __forceinline__ uint32_t packet_ray(uint32_t c, uint32_t e, uint32_t lane, uint32_t P, uint32_t Ec) {
@@ -363,14 +333,106 @@ __device__ __forceinline__ uint32_t packet_ray(uint32_t c, uint32_t e, uint32_t 
 	}
 	return min(lo, e);
 }
-__device__ __forceinline__ uint32_t wave_prefix(uint32_t n, uint32_t lane) { // inclusive
-	#pragma unroll
-	for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = (uint32_t)__shfl_up((int)n, d); if (lane >= d) n += v; }
-	return n;
+
+// What the walk shows its body.
+struct Walk {
+	uint32_t lane, n, P, E; // as a ray of the wave: its samples, the inclusive and the exclusive sum of n over the lanes
+	// the packet (wave-uniform): rays c..e with tot samples, the first of them sample Ec of the wave; lng: ray c alone, and this is its chunk ch of `lanes` samples
+	uint32_t c, e, tot, Ec, ch, lanes;
+	bool lng;
+	float Tin; f3 Cin;      // (T, C) of the chunks in front of this one
+	// as a sample of the chunk: sample j of ray r (a lane of the wave), whose samples start at lane st of the chunk; record si; valid: there is such a sample
+	uint32_t r, st, j; bool valid; size_t si;
+	Sample q;               // (not valid: one that adds nothing)
+	float x, Tb, T, w;      // the product of 1 - alpha over the ray's samples of this chunk up to this one; T in front of the sample and behind it; its weight
+	f3 y, C2;               // the sums of w * rgb over the same lanes; C up to and including this sample
+};
+// the packet that starts at ray k.c: the rays from c on whose counts fit into 64 lanes together, or ray c alone when it is longer
+__device__ __forceinline__ void next_packet(Walk& k) {
+	// (tot and Ec come out of shuffles: the same in every lane, which the compiler has to be told to keep them in scalar registers)
+	k.Ec = (uint32_t)__builtin_amdgcn_readfirstlane((int)shfl_u(k.E, k.c));
+	uint32_t tot = shfl_u(k.n, k.c);
+	k.lng = tot > 64u;
+	k.e = k.c;
+	if (!k.lng) {
+		const unsigned long long fit = __ballot(k.lane >= k.c && k.P - k.Ec <= 64u); // P grows with the lane: a run that starts at c
+		k.e = k.c + (uint32_t)__popcll(fit) - 1u;
+		tot = shfl_u(k.P, k.e) - k.Ec;
+	}
+	k.tot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tot);
+}
+// body.weight(k): the sample's weight, given k.Tb.  body.chunk(k): the chunk's scans are complete; returns how many of the chunk's lanes the ray consumed (fewer than
+// k.lanes ends a long ray there).  body.long_ray(k): a long ray is done, (k.Tin, k.Cin) are its T and C.
+template <class Body>
+__device__ __forceinline__ void walk_samples(const DeviceModel& m, const RayLossArgs& a, uint32_t n, uint32_t base, Body& body) {
+	Walk k;
+	const uint32_t lane = k.lane = threadIdx.x & 63u;
+	k.n = n; k.P = wave_inclusive_add(n, lane); k.E = k.P - n;
+	for (k.c = 0; k.c < 64u; k.c = k.e + 1u) {
+		next_packet(k);
+		k.Tin = 1.f; k.Cin = mk3(0, 0, 0);
+		const uint32_t chunks = (k.tot + 63u) / 64u;
+		for (k.ch = 0; k.ch < chunks; ++k.ch) {
+			k.lanes = min(64u, k.tot - k.ch * 64u);
+			k.r = k.c; k.st = 0; k.j = k.ch * 64u + lane;
+			if (!k.lng) {
+				k.r = packet_ray(k.c, k.e, lane, k.P, k.Ec);
+				k.st = shfl_u(k.E, k.r) - k.Ec;
+				k.j = lane - k.st;
+			}
+			k.valid = k.lng ? k.j < k.tot : lane < k.tot;
+			k.si = (size_t)shfl_u(base, k.r) + k.j;
+			k.q.alpha = 0.f; k.q.rest = 1.f; k.q.dt = 0.f; k.q.rgb = mk3(0, 0, 0); k.q.raw.v[0] = k.q.raw.v[1] = k.q.raw.v[2] = k.q.raw.v[3] = 0.f;
+			if (k.valid) k.q = load_sample(m, a, k.si);
+			k.x = seg_scan_mul(k.q.rest, lane, k.st);
+			const float up = wave_lane_before(k.x);
+			k.Tb = (lane == k.st ? 1.f : up) * k.Tin;
+			k.T = k.x * k.Tin;
+			k.w = body.weight(k);
+			k.y = mk3(seg_scan_add(k.w * k.q.rgb.x, lane, k.st), seg_scan_add(k.w * k.q.rgb.y, lane, k.st), seg_scan_add(k.w * k.q.rgb.z, lane, k.st));
+			k.C2 = k.Cin + k.y;
+			const uint32_t used = body.chunk(k);
+			if (k.lng) { // what the next chunk starts from, or the ray ends with
+				if (used) { k.Cin = shfl3(k.C2, used - 1u); k.Tin = __shfl(k.T, (int)used - 1); }
+				if (used < k.lanes) break;
+			}
+		}
+		if (k.lng) body.long_ray(k);
+	}
 }
 
+// The forward pass: a ray's M, C and T.  The early stop is a predicate per lane (T in front of it < EPS), balloted: the first set bit of a segment is the ray's M, and
+// every lane at or behind it contributes exactly nothing.
+struct ForwardBody {
+	f3 C; float T; uint32_t M; // of the lane's ray
+	unsigned long long bad;    // the chunk's lanes with T in front of them below EPS
+	__device__ __forceinline__ float weight(const Walk& k) {
+		bad = __ballot(k.valid && k.Tb < kLossEps);
+		const bool active = k.valid && !(bad & lane_range(k.st, k.lane));
+		return active ? k.q.alpha * k.Tb : 0.f;
+	}
+	// A ray's sums are read at the lane of its last consumed sample, not at the end of its segment: see walk_samples.
+	__device__ __forceinline__ uint32_t chunk(const Walk& k) {
+		if (k.lng) {
+			const uint32_t used = bad ? (uint32_t)__builtin_ctzll(bad) : k.lanes;
+			if (k.lane == k.c) M = k.ch * 64u + used; // (of the last chunk the walk comes to)
+			return used;
+		}
+		const bool mine = k.lane >= k.c && k.lane <= k.e && k.n > 0u;
+		const uint32_t first = mine ? k.E - k.Ec : 0u, last = mine ? first + k.n - 1u : 0u;
+		const unsigned long long stop = bad & lane_range(first, last);
+		const uint32_t Mr = stop ? (uint32_t)__builtin_ctzll(stop) - first : k.n; // >= 1 for a ray with samples: T in front of its first sample is 1
+		const f3 p = shfl3(k.y, mine ? first + Mr - 1u : 0u);
+		const float px = __shfl(k.x, (int)last);
+		if (mine) { M = Mr; C = p; T = px; }
+		return k.lanes;
+	}
+	__device__ __forceinline__ void long_ray(const Walk& k) {
+		if (k.lane == k.c) { C = k.Cin; T = k.Tin; }
+	}
+};
+
 __global__ __launch_bounds__(kWaveBlock) void ray_loss_forward_kernel(const DeviceModel m, const RayLossArgs a) {
-	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t i = blockIdx.x * kWaveBlock + threadIdx.x;
 	const uint32_t live = live_rays(a);
 	uint32_t n = 0, base = 0;
@@ -379,154 +441,77 @@ __global__ __launch_bounds__(kWaveBlock) void ray_loss_forward_kernel(const Devi
 		base = a.numsteps[2 * i + 1];
 		if (base > a.n_samples || n > a.n_samples - base || n > kTrainSteps) n = 0u; // not inside the buffers, or longer than a ray can be: no samples
 	}
-	const uint32_t P = wave_prefix(n, lane), E = P - n;
-	f3 C = mk3(0, 0, 0);
-	float T = 1.f;
-	uint32_t M = 0;
-	for (uint32_t c = 0; c < 64u;) {
-		const Packet k = next_packet(c, lane, n, P, E);
-		const uint32_t Ec = shfl_u(E, c);
-		const uint32_t chunks = (k.tot + 63u) / 64u;
-		float Tin = 1.f;
-		f3 Cin = mk3(0, 0, 0);
-		uint32_t Mlong = k.tot;
-		for (uint32_t ch = 0; ch < chunks; ++ch) {
-			uint32_t r = c, st = 0, j = ch * 64u + lane;
-			if (!k.lng) {
-				r = packet_ray(c, k.e, lane, P, Ec);
-				st = shfl_u(E, r) - Ec;
-				j = lane - st;
-			}
-			const bool valid = k.lng ? j < k.tot : lane < k.tot;
-			const uint32_t sbase = shfl_u(base, r);
-			float alpha = 0.f, rest = 1.f;
-			f3 rgb = mk3(0, 0, 0);
-			if (valid) { const Sample q = load_sample(m, a, (size_t)sbase + j); alpha = q.alpha; rest = q.rest; rgb = q.rgb; }
-			const float x = seg_scan_mul(rest, lane, st);
-			float Tb = __shfl_up(x, 1);
-			Tb = (lane == st ? 1.f : Tb) * Tin;
-			const unsigned long long bad = __ballot(valid && Tb < kLossEps);
-			const bool active = valid && !(bad & lane_range(st, lane));
-			const float w = active ? alpha * Tb : 0.f;
-			const float y0 = seg_scan_add(w * rgb.x, lane, st), y1 = seg_scan_add(w * rgb.y, lane, st), y2 = seg_scan_add(w * rgb.z, lane, st);
-			// A ray's sums are read at the lane of its last consumed sample, not at the end of its segment: the scan's value there is formed from the same lanes in the
-			// same order as the gradient pass forms C2 at that sample, so C - C2 is exactly what lies behind the sample (0 behind the last one of a stopped ray).
-			if (k.lng) {
-				if (bad) {
-					const uint32_t fb = (uint32_t)__builtin_ctzll(bad);
-					Mlong = ch * 64u + fb;
-					if (fb) Cin = Cin + mk3(__shfl(y0, (int)fb - 1), __shfl(y1, (int)fb - 1), __shfl(y2, (int)fb - 1));
-					break;
-				}
-				const int lv = (int)min(63u, k.tot - 1u - ch * 64u);
-				Cin = Cin + mk3(__shfl(y0, lv), __shfl(y1, lv), __shfl(y2, lv));
-				Tin *= __shfl(x, lv);
-			} else {
-				const bool mine = lane >= c && lane <= k.e && n > 0u;
-				const uint32_t first = mine ? E - Ec : 0u, last = mine ? first + n - 1u : 0u;
-				const unsigned long long stop = bad & lane_range(first, last);
-				const uint32_t Mr = stop ? (uint32_t)__builtin_ctzll(stop) - first : n; // >= 1 for a ray with samples: T in front of its first sample is 1
-				const int src = mine ? (int)(first + Mr - 1u) : 0;
-				const float p0 = __shfl(y0, src), p1 = __shfl(y1, src), p2 = __shfl(y2, src), px = __shfl(x, (int)last);
-				if (mine) {
-					M = Mr;
-					C = mk3(p0, p1, p2);
-					T = px;
-				}
-			}
-		}
-		if (k.lng && lane == c) { C = Cin; T = Tin; M = Mlong; }
-		c = k.e + 1u;
-	}
+	ForwardBody f{mk3(0, 0, 0), 1.f, 0u, 0ull};
+	walk_samples(m, a, n, base, f);
 	if (i >= a.n_rays) return;
 	if (i >= live) {
-		a.ws[i] = 0u;
+		RayLossWs(a.ws, a.n_rays).M[i] = 0u;
 		if (a.loss) a.loss[i] = 0.f;
 		return;
 	}
-	finish_ray(a, i, M, n, C, T);
+	finish_ray(a, i, f.M, n, f.C, f.T);
 }
 
+// The gradient pass: the M' samples of every ray that fit the compact buffer, replayed (tn:1835) -- each sample's record copied to its compact place, its dL/doutput
+// from what lies in front of it and behind it.
+struct GradientBody {
+	const DeviceModel& m;
+	const RayLossArgs& a;
+	uint32_t i, cbase; // the lane's ray, its compact base
+	f3 C, g;           // and what the forward pass left of it
+	float s, l2reg, l1reg;
+	__device__ __forceinline__ float weight(const Walk& k) { return k.q.alpha * k.Tb; }
+	__device__ __forceinline__ uint32_t chunk(const Walk& k) {
+		const nrs_ray_loss_params& p = a.p;
+		const uint32_t scbase = shfl_u(cbase, k.r);
+		const f3 Cr = shfl3(C, k.r), gr = shfl3(g, k.r);
+		if (k.valid) {
+			const Sample& q = k.q;
+			const size_t so = (size_t)scbase + k.j;
+			const float* cin = a.coords + k.si * a.ld_in;
+			float* cout = a.coords_out + so * a.ld_in;
+			for (uint32_t f = 0; f < a.ld_in; ++f) cout[f] = cin[f];
+			const f3 suffix = Cr - k.C2;
+			const f3 dr = k.w * gr;
+			float dl[4];
+			dl[0] = s * (dr.x * network_to_rgb_derivative(q.raw.v[0], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[0]));
+			dl[1] = s * (dr.y * network_to_rgb_derivative(q.raw.v[1], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[1]));
+			dl[2] = s * (dr.z * network_to_rgb_derivative(q.raw.v[2], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[2]));
+			const float by_mlp = network_to_density_derivative(q.raw.v[3], m.density_activation) * (q.dt * dot3(gr, k.T * q.rgb - suffix));
+			float near_term = 0.0f;
+			if (p.near_distance > 0.f && q.raw.v[3] > -10.0f) {
+				const size_t ray = (size_t)(i - k.lane) + k.r;
+				const f3 dv = unwarp_position(mk3(cin[0], cin[1], cin[2]), m.aabb) - mk3(a.origins[3 * ray], a.origins[3 * ray + 1], a.origins[3 * ray + 2]);
+				if (sqrtf(dot3(dv, dv)) < p.near_distance) near_term = 1e-4f;
+			}
+			dl[3] = s * by_mlp + (q.raw.v[3] < 0.0f ? -l1reg : 0.0f) + near_term;
+			store_dl(reinterpret_cast<__half*>(a.dl), a.ld_dl, a.dl_layout, so, dl);
+		}
+		return k.lanes;
+	}
+	__device__ __forceinline__ void long_ray(const Walk&) {}
+};
+
 __global__ __launch_bounds__(kWaveBlock) void ray_loss_gradient_kernel(const DeviceModel m, const RayLossArgs a) {
-	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t i = blockIdx.x * kWaveBlock + threadIdx.x;
-	const size_t R = a.n_rays;
-	const float* ws_f = reinterpret_cast<const float*>(a.ws) + 2 * R;
+	const RayLossWs ws(a.ws, a.n_rays);
 	const nrs_ray_loss_params& p = a.p;
-	uint32_t n = 0, base = 0, cbase = 0; // n: the samples to replay, M' (tn:1835)
-	f3 C = mk3(0, 0, 0), g = mk3(0, 0, 0);
+	GradientBody b{m, a, i, 0u, mk3(0, 0, 0), mk3(0, 0, 0), p.loss_scale / (float)a.n_rays, m.rgb_activation == NRS_ACT_EXPONENTIAL ? 1e-4f : 0.0f, p.density_l1_reg ? 1e-4f : 0.0f};
+	uint32_t n = 0, base = 0; // n: the samples to replay, M' (tn:1835)
 	if (i < live_rays(a)) {
-		const uint32_t M = a.ws[i], cap = p.max_samples_compacted;
-		cbase = a.ws[R + i];
-		n = min(cap - min(cap, cbase), M);
+		const uint32_t M = ws.M[i], cap = p.max_samples_compacted;
+		b.cbase = ws.cbase[i];
+		n = min(cap - min(cap, b.cbase), M);
 		a.numsteps_out[2 * i] = n;
-		a.numsteps_out[2 * i + 1] = cbase;
-		if (a.loss) a.loss[i] = n ? ws_f[6 * R + i] : 0.f;
+		a.numsteps_out[2 * i + 1] = b.cbase;
+		if (a.loss) a.loss[i] = n ? ws.loss[i] : 0.f;
 		if (n) {
 			base = a.numsteps[2 * i + 1];
-			C = mk3(ws_f[i], ws_f[R + i], ws_f[2 * R + i]);
-			g = mk3(ws_f[3 * R + i], ws_f[4 * R + i], ws_f[5 * R + i]);
+			b.C = mk3(ws.C[0][i], ws.C[1][i], ws.C[2][i]);
+			b.g = mk3(ws.g[0][i], ws.g[1][i], ws.g[2][i]);
 		}
 	}
-	const uint32_t P = wave_prefix(n, lane), E = P - n;
-	const float s = p.loss_scale / (float)a.n_rays;
-	const float l2reg = m.rgb_activation == NRS_ACT_EXPONENTIAL ? 1e-4f : 0.0f, l1reg = p.density_l1_reg ? 1e-4f : 0.0f;
-	const bool use_near = p.near_distance > 0.f;
-	for (uint32_t c = 0; c < 64u;) {
-		const Packet k = next_packet(c, lane, n, P, E);
-		const uint32_t Ec = shfl_u(E, c);
-		const uint32_t chunks = (k.tot + 63u) / 64u;
-		float Tin = 1.f;
-		f3 Cin = mk3(0, 0, 0);
-		for (uint32_t ch = 0; ch < chunks; ++ch) {
-			uint32_t r = c, st = 0, j = ch * 64u + lane;
-			if (!k.lng) {
-				r = packet_ray(c, k.e, lane, P, Ec);
-				st = shfl_u(E, r) - Ec;
-				j = lane - st;
-			}
-			const bool valid = k.lng ? j < k.tot : lane < k.tot;
-			const uint32_t sbase = shfl_u(base, r), scbase = shfl_u(cbase, r);
-			const f3 Cr = mk3(__shfl(C.x, (int)r), __shfl(C.y, (int)r), __shfl(C.z, (int)r)), gr = mk3(__shfl(g.x, (int)r), __shfl(g.y, (int)r), __shfl(g.z, (int)r));
-			Sample q;
-			q.alpha = 0.f; q.rest = 1.f; q.dt = 0.f; q.rgb = mk3(0, 0, 0); q.raw.v[0] = q.raw.v[1] = q.raw.v[2] = q.raw.v[3] = 0.f;
-			const size_t si = (size_t)sbase + j, so = (size_t)scbase + j;
-			const float* cin = a.coords + si * a.ld_in;
-			if (valid) {
-				q = load_sample(m, a, si);
-				float* cout = a.coords_out + so * a.ld_in;
-				for (uint32_t f = 0; f < a.ld_in; ++f) cout[f] = cin[f];
-			}
-			const float x = seg_scan_mul(q.rest, lane, st);
-			float Tb = __shfl_up(x, 1);
-			Tb = (lane == st ? 1.f : Tb) * Tin;
-			const float T = x * Tin; // after the sample
-			const float w = q.alpha * Tb;
-			const f3 C2 = Cin + mk3(seg_scan_add(w * q.rgb.x, lane, st), seg_scan_add(w * q.rgb.y, lane, st), seg_scan_add(w * q.rgb.z, lane, st));
-			if (valid) {
-				const f3 suffix = Cr - C2;
-				const f3 dr = w * gr;
-				float dl[4];
-				dl[0] = s * (dr.x * network_to_rgb_derivative(q.raw.v[0], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[0]));
-				dl[1] = s * (dr.y * network_to_rgb_derivative(q.raw.v[1], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[1]));
-				dl[2] = s * (dr.z * network_to_rgb_derivative(q.raw.v[2], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[2]));
-				const float by_mlp = network_to_density_derivative(q.raw.v[3], m.density_activation) * (q.dt * dot3(gr, T * q.rgb - suffix));
-				float near_term = 0.0f;
-				if (use_near && q.raw.v[3] > -10.0f) {
-					const size_t ray = (size_t)(i - lane) + r;
-					const f3 dv = unwarp_position(mk3(cin[0], cin[1], cin[2]), m.aabb) - mk3(a.origins[3 * ray], a.origins[3 * ray + 1], a.origins[3 * ray + 2]);
-					if (sqrtf(dot3(dv, dv)) < p.near_distance) near_term = 1e-4f;
-				}
-				dl[3] = s * by_mlp + (q.raw.v[3] < 0.0f ? -l1reg : 0.0f) + near_term;
-				store_dl(reinterpret_cast<__half*>(a.dl), a.ld_dl, a.dl_layout, so, dl);
-			}
-			if (k.lng) { // what the next chunk starts from
-				Cin = mk3(__shfl(C2.x, 63), __shfl(C2.y, 63), __shfl(C2.z, 63));
-				Tin = __shfl(T, 63);
-			}
-		}
-		c = k.e + 1u;
-	}
+	walk_samples(m, a, n, base, b);
 }
 
 // compact indices [min(*total, cap), cap): a zero record and dL rows 0..3 zero
@@ -545,7 +530,8 @@ int launch_ray_loss(const DeviceModel& m, const RayLossArgs& a, void* stream) {
 		const uint32_t blocks = (a.n_rays + kWaveBlock - 1) / kWaveBlock;
 		hipLaunchKernelGGL(ray_loss_forward_kernel, dim3(blocks), dim3(kWaveBlock), 0, st, m, a);
 		NRS_LAUNCH_CHECK("ray_loss_forward_kernel launch");
-		const int status = launch_train_scan<false>(a.n_rays, a.ray_counter, a.ws, a.ws + (size_t)kRayLossWsWords * a.n_rays, a.ws + a.n_rays, nullptr, 0u, a.counter_out, nullptr, st);
+		const RayLossWs ws(a.ws, a.n_rays);
+		const int status = launch_train_scan<false>(a.n_rays, a.ray_counter, ws.M, ws.tiles, ws.cbase, nullptr, 0u, a.counter_out, nullptr, st);
 		if (status != NRS_OK) return status;
 		hipLaunchKernelGGL(ray_loss_gradient_kernel, dim3(blocks), dim3(kWaveBlock), 0, st, m, a);
 		NRS_LAUNCH_CHECK("ray_loss_gradient_kernel launch");

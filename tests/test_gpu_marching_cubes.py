@@ -84,6 +84,20 @@ def test_random_lattice(rig, table):
         assert on_lattice_boundary(V[a], res) and on_lattice_boundary(V[b], res), (a, b)
 
 
+def test_more_blocks_than_scan_threads(rig, table):
+    """8 x 8 x 4100 points are 1025 blocks of 256: each thread of the one-workgroup scan over the blocks' sums owns a run of two.  Three slabs of U(-1, 1), in the
+    first blocks, in the middle and in the last ones, in a field that is below the threshold everywhere else."""
+    res = (8, 8, 4100)
+    rng = np.random.default_rng(4100)
+    d = np.full((res[2], res[1] * res[0]), -0.6, F32)
+    for z in (3, 2040, 4090):
+        d[z:z + 3] = rng.uniform(-1, 1, (3, res[1] * res[0])).astype(F32)
+    mesh, V, *_ = assert_equals_restatement(rig, table, d.reshape(-1), res, 0.1)
+    assert mesh.n_verts > 600 and mesh.n_tris > 900
+    z = V[:mesh.n_verts, 2] * res[2]
+    assert ((z > 2) & (z < 7)).any() and ((z > 2039) & (z < 2044)).any() and ((z > 4089) & (z < 4094)).any()
+
+
 def lattice_points(res, box=UNIT):
     z, y, x = np.meshgrid(*(np.arange(r, dtype=np.float64) for r in res[::-1]), indexing="ij")
     scale = (np.array(box[1]) - np.array(box[0])) / np.array(res)

@@ -199,6 +199,29 @@ def test_counter_cap_and_determinism(ctx):
     assert first[4] == again[4] == live_total
 
 
+def test_loss_across_scan_tiles(ctx):
+    """1079 rays: the scan of M takes two tiles of 1024 rays.  Whole; then with 1050 live rays and a compact buffer 37 samples short, which clips the last 37 rays,
+    either side of the tile boundary; that run twice, bit for bit."""
+    b, expect = ref.constructed_batch(3, repeats=13)
+    c = ref.closed_form(b)
+    assert b["numsteps"].shape[0] == 1079 and b["out"].shape[0] >= 27062 and c.counter == 14920
+    assert (c.f.M.numpy() == expect).all() and not bool(c.f.in_band.any()) and not bool(c.f.near_threshold.any())
+    judge("two tiles", b, run(ctx, b), True)
+    b["live"] = 1050
+    live_total = ref.closed_form(b).counter
+    assert live_total == 14736
+    b["p"]["cap"] = live_total - 37
+    c = ref.closed_form(b)
+    clipped = np.nonzero((c.numsteps_out[:1050, 0] < c.f.M[:1050]).numpy())[0]
+    assert len(clipped) == 37 and clipped.min() < 1024 <= clipped.max() and c.counter == live_total   # (rays 1013..1049: either side of the tile boundary)
+    first = run(ctx, b, live=1050)
+    judge("two tiles, clipped", b, first, True)
+    again = run(ctx, b, live=1050)
+    for x, y in zip(first[:4], again[:4]):
+        assert x.tobytes() == y.tobytes()
+    assert first[4] == again[4] == live_total
+
+
 def test_no_rays_and_refusals(ctx):
     from nerfshop_amd import _abi, runtime
     net = network(ctx)
@@ -296,6 +319,55 @@ def test_training_samples_drops_clips_and_repeats(generated):
     bad[2, 3:] *= 1e-20
     c = net.training_samples(None, torch.from_numpy(bad).to(DEV), None, 0.0, 4096)[3].cpu().numpy()
     assert c[1] == got_counts[3] and c[0] == (1 if got_counts[3] else 0)
+
+
+@pytest.fixture(scope="module")
+def generated_100(generated):
+    """the fixture's 100 rays through the generator once: per-ray counts and records"""
+    net, rays, jitter, walk, counts, stable = generated
+    coords, numsteps, ray_indices, counters = (x.cpu().numpy() for x in net.training_samples(None, torch.from_numpy(rays).to(DEV), torch.from_numpy(jitter).to(DEV), 0.0,
+                                                                                              1 << 16))
+    emitted = int(counters[0])
+    assert int(counters[1]) <= 1 << 16 and emitted == (counts > 0).sum() > 30
+    got_counts = np.zeros(100, np.int64)
+    got_counts[ray_indices[:emitted]] = numsteps[:emitted, 0]
+    records = [np.zeros((0, 7), np.float32)] * 100
+    for k in range(emitted):
+        records[ray_indices[k]] = coords[numsteps[k, 1]:numsteps[k, 1] + numsteps[k, 0]]
+    return got_counts, records
+
+
+@pytest.mark.parametrize("n,cut", [(1023, False), (1024, False), (1025, False), (2600, False), (2600, True)])
+def test_training_samples_across_scan_tiles(generated, generated_100, n, cut):
+    """The 100 rays repeated to n: one tile of 1024 rays less one ray, exactly one tile, one ray into the second, and three tiles; cut: max_samples drops a ray of the
+    second tile and every ray behind it.  The layout is layout_from_counts of the 100-ray call's counts, a ray's records are those of the 100-ray call, byte for
+    byte, the tail is zero, and two calls agree."""
+    net, rays, jitter = generated[:3]
+    counts100, records = generated_100
+    which = np.arange(n) % 100
+    counts = counts100[which]
+    max_samples = int(counts.sum()) + 11
+    if cut:
+        bases = np.cumsum(counts) - counts
+        k = 1500 + int(np.nonzero(counts[1500:])[0][0])
+        max_samples = int(bases[k] + counts[k]) - 1   # ray k is the first that does not fit
+        assert 1024 <= k < 2048
+    d_rays, d_jitter = torch.from_numpy(rays[which]).to(DEV), torch.from_numpy(jitter[which]).to(DEV)
+    runs = [[x.cpu().numpy() for x in net.training_samples(None, d_rays, d_jitter, 0.0, max_samples)] for _ in range(2)]
+    for x, y in zip(*runs):
+        assert x.tobytes() == y.tobytes()
+    coords, numsteps, ray_indices, counters = runs[0]
+    want_numsteps, want_idx, want_counters, _ = ref.layout_from_counts(counts, max_samples)
+    emitted = int(counters[0])
+    assert tuple(int(v) for v in counters) == want_counters and (emitted < (counts > 0).sum()) == cut
+    if cut:
+        assert want_idx[-1] < k and ((counts[want_idx[-1] + 1:k] == 0).all())
+    assert (numsteps[:emitted] == want_numsteps).all() and (ray_indices[:emitted] == want_idx).all()
+    assert (numsteps[emitted:] == 0).all() and (ray_indices[emitted:] == 0).all()
+    want_coords = np.zeros_like(coords)
+    end = int(want_numsteps[-1].sum())
+    want_coords[:end] = np.concatenate([records[i % 100] for i in want_idx])   # (bases are the running sum: the emitted rays' records lie back to back)
+    assert coords.tobytes() == want_coords.tobytes(), "records of ray i are those of ray i % 100; zero behind the last emitted ray"
 
 
 # ---- torch -------------------------------------------------------------------------------------------------------------------------------------------------------

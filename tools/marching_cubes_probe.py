@@ -4,7 +4,7 @@
 nrs_mesh_from_density synchronises the stream, so a call is timed on the host's clock around it (after `--warmup` untimed calls, `--reps` times, median and 10th..90th
 percentile); nrs_density_on_grid is asynchronous and is timed with a stream synchronisation either side.  The passes inside nrs_mesh_from_density (count, scan, emit,
 1-ring) are not separated here: that takes a kernel trace (rocprofv3 --kernel-trace --stats -- python tools/marching_cubes_probe.py --reps 1), whose per-kernel rows
-carry the names mc_count_kernel, mc_scan_kernel, mc_emit_kernel, mc_1ring_kernel, mesh_color_inputs_kernel, mesh_colors_kernel.  Beside every time: the bytes the
+carry the names mc_count_kernel, tile_scan_kernel<2>, mc_emit_kernel, mc_1ring_kernel, mesh_color_inputs_kernel, mesh_colors_kernel.  Beside every time: the bytes the
 step must move (lattice read once per pass that reads it, per-point codes written once and read once, the mesh written once) and their floor at 8 TB/s.
 --json adds one machine-readable line.  Needs a GPU: there is nothing to fall back to.
 
