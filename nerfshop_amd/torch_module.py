@@ -151,11 +151,9 @@ class NerfNetworkModule(torch.nn.Module):
         self._resident = p16
         key = (coords.shape[0], numsteps.shape[0], int(params.max_samples_compacted), coords.shape[1])
         if self._ray_bufs is None or self._ray_bufs[0] != key:
-            dev, cap = coords.device, int(params.max_samples_compacted)
+            dev = coords.device
             self._ray_bufs = (key, torch.empty((coords.shape[0], 16), dtype=torch.float16, device=dev),
-                              (torch.empty_like(numsteps), torch.empty(cap, coords.shape[1], dtype=torch.float32, device=dev),
-                               torch.zeros((cap, 16), dtype=torch.float16, device=dev), torch.empty(numsteps.shape[0], dtype=torch.float32, device=dev),
-                               torch.empty(1, dtype=torch.int32, device=dev)),
+                              net.ray_loss_buffers(numsteps.shape[0], params.max_samples_compacted, coords.shape[1], device=dev),
                               torch.empty(self.params.numel(), dtype=torch.float32, device=dev))
         _, out16, bufs, grad = self._ray_bufs
         net.inference_strided(None, coords, out16)

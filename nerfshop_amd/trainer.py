@@ -16,13 +16,11 @@ Everything in `step` is enqueued on the current stream and nothing is read back:
 configs/nerf/base.json's -- Ema(0.95) over ExponentialDecay(20000, 10000, 0.33) over Adam(1e-2, 0.9, 0.99, 1e-15, l2_reg 1e-6) -- and writes the network's parameters
 in place (runtime.Optimizer bound to the network), so no set_params call and no gradient memset sits between two steps.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _abi, runtime
-from ._abi import NrsError, check
+from ._abi import NrsError
 from .torch_module import LOSS_SCALE, initial_params
 
 
@@ -55,9 +53,7 @@ class Trainer:
         self._loss_bufs = None
         self._grid_update = _abi.GridUpdate()
         self._grid_update.max_cascade, self._grid_update.ema_step = int(max_cascade), 0
-        st, inc = C.c_uint64(), C.c_uint64()
-        self.lib.nrs_rng_seed(int(seed), C.byref(st), C.byref(inc))
-        self._grid_update.rng_state, self._grid_update.rng_inc = st.value, inc.value
+        self._grid_update.rng_state, self._grid_update.rng_inc = runtime.rng_seed(seed)
         self.density_grid_decay = float(density_grid_decay)
         self._grid_step = 0  # the training step of the last update_density_grid
         if density_grid is not None:
@@ -81,7 +77,7 @@ class Trainer:
             u.n_uniform_samples, u.n_nonuniform_samples = cells // 4, cells // 4
         u.reset_grid = 0
         u.decay = self.density_grid_decay ** (k / 16.0)
-        check(self.lib.nrs_model_update_density_grid(self.network.h, (C.c_void_p * 1)(), 0, C.byref(u), runtime._stream_handle(stream)))
+        self.network.update_density_grid(u, stream=stream)
         self._grid_step = self.training_step
 
     def step(self, rays, target_rgba, jitter=None, background=None):
@@ -98,10 +94,7 @@ class Trainer:
         target = target_rgba.index_select(0, slots)
         bg = None if background is None else background.index_select(0, slots)
         if self._loss_bufs is None or self._loss_bufs[0].shape[0] != n_rays:
-            dev = rays.device
-            self._loss_bufs = (torch.empty((n_rays, 2), dtype=torch.int32, device=dev), torch.empty((self.max_samples, 7), dtype=torch.float32, device=dev),
-                               torch.zeros((self.max_samples, 16), dtype=torch.float16, device=dev), torch.empty(n_rays, dtype=torch.float32, device=dev),
-                               torch.empty(1, dtype=torch.int32, device=dev))
+            self._loss_bufs = net.ray_loss_buffers(n_rays, self.max_samples, device=rays.device)
         _, coords_out, dl, loss, _ = net.ray_loss(None, self.loss_params, numsteps, coords, self._out16, target, background=bg, ray_counter=counters[:1],
                                                   out=self._loss_bufs)
         net.backward(None, coords_out, dl, self.grad, None, accumulate=True)
