@@ -312,7 +312,8 @@ __device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uin
 // walk_samples is that walk, for both passes over the samples: the forward pass reads a ray's C out of it, the gradient pass the C in front of every sample, and
 // dL/doutput needs their difference -- what lies behind the sample -- to be exact (0 behind the last consumed sample of a stopped ray).  It is, because both values are
 // this one function's: the same lanes scanned in the same order.  The passes differ only in the weight they give a sample (the forward pass stops a ray) and in what
-// they do with a chunk's scans.
+// they do with a chunk's scans.  The gradient pass takes that difference only at the ray's last sample of a chunk and sums the samples between from the far end
+// (GradientBody::chunk): C - C2 at every sample carries the rounding of C into a difference that is a thousandth of it late in a ray.
 constexpr uint32_t kWaveBlock = 256;
 __device__ __forceinline__ uint32_t shfl_u(uint32_t v, uint32_t lane) { return (uint32_t)__shfl((int)v, (int)lane); }
 __device__ __forceinline__ f3 shfl3(f3 v, uint32_t lane) { return mk3(__shfl(v.x, (int)lane), __shfl(v.y, (int)lane), __shfl(v.z, (int)lane)); }
@@ -465,13 +466,27 @@ struct GradientBody {
 		const nrs_ray_loss_params& p = a.p;
 		const uint32_t scbase = shfl_u(cbase, k.r);
 		const f3 Cr = shfl3(C, k.r), gr = shfl3(g, k.r);
+		// What lies behind a sample: the weighted colours of the ray's later samples in this chunk, summed from the ray's end towards the sample, plus what lies behind
+		// the chunk's last sample of the ray (C - C2 there: 0 behind the last consumed sample of a stopped ray, both being walk_samples' values).  C - C2 at the sample
+		// itself is the same number with the rounding of C on it -- half a float32 step of C, which late in a ray that is about to stop (T rgb and what lies behind it
+		// both near 1e-3 of C) is hundreds of float32 steps of the difference the density gradient is made of.
+		const uint32_t en = k.lng ? k.lanes - 1u : k.st + shfl_u(k.n, k.r) - 1u; // the last lane of the ray's samples in this chunk
+		f3 later = k.w * k.q.rgb; // (a lane without a sample has weight 0)
+		#pragma unroll
+		for (uint32_t d = 1; d < 64; d <<= 1) {
+			const f3 v = mk3(__shfl_down(later.x, d), __shfl_down(later.y, d), __shfl_down(later.z, d));
+			if (k.lane + d <= en) later = later + v;
+		}
+		const f3 next = mk3(__shfl_down(later.x, 1), __shfl_down(later.y, 1), __shfl_down(later.z, 1));
+		const f3 C2end = shfl3(k.C2, en & 63u);
 		if (k.valid) {
 			const Sample& q = k.q;
 			const size_t so = (size_t)scbase + k.j;
 			const float* cin = a.coords + k.si * a.ld_in;
 			float* cout = a.coords_out + so * a.ld_in;
 			for (uint32_t f = 0; f < a.ld_in; ++f) cout[f] = cin[f];
-			const f3 suffix = Cr - k.C2;
+			const f3 behind = Cr - C2end;
+			const f3 suffix = k.lane < en ? next + behind : behind;
 			const f3 dr = k.w * gr;
 			float dl[4];
 			dl[0] = s * (dr.x * network_to_rgb_derivative(q.raw.v[0], m.rgb_activation) + fmaxf(0.0f, l2reg * q.raw.v[0]));

@@ -12,6 +12,8 @@ composite_loss   float64, dL/doutput from autograd of s * sum over rays and chan
 closed_form      the reference's formula (T after the sample, suffix = C - C2), float64
 closed_form32    the same in float32: the reference's own arithmetic
 march            the generator's walk in numpy float32 on the oracle's exported scalars
+large_scene_walk that walk in a box of side 4 or 16 through block_bitfield on large_scene_rays (with and without the cone): the generator's large-box cases
+big_box_batch    random_batch at a cone's steps (dt of 1..128 minimum steps) in such a box, with the near-distance term
 
 All three loss twins run the rays side by side and the samples of a ray one after the other, so a ray's sums are formed in the reference's order.
 """
@@ -375,9 +377,10 @@ def ray_tmin(mn, mx, o, d):
     return max(f(tmin), f(0))
 
 
-def march(orc_lib, bitfield, aabb, rays, jitter, cone, tmin_nudge_ulps=0, max_steps=1024):
+def march(orc_lib, bitfield, aabb, rays, jitter, cone, tmin_nudge_ulps=0, max_steps=1024, mips_out=None):
     """The generator's walk per ray, float32: returns a list of [count, 7] float32 records (warped position, warped dt, warped direction).
-    tmin_nudge_ulps moves the entry distance by that many float32 steps (how stable a ray's count is against the last bit of its start)."""
+    tmin_nudge_ulps moves the entry distance by that many float32 steps (how stable a ray's count is against the last bit of its start).
+    mips_out: a list that receives, per ray, the cascade of every sample (int array [count])."""
     f = np.float32
     bits = np.ascontiguousarray(bitfield, np.uint8)
     mn, mx = np.asarray(aabb[0], f), np.asarray(aabb[1], f)
@@ -393,7 +396,7 @@ def march(orc_lib, bitfield, aabb, rays, jitter, cone, tmin_nudge_ulps=0, max_st
         jit = f(jitter[i]) if jitter is not None else f(0)
         t = f(tmin + f(f(orc_lib.orc_calc_dt(C.c_float(tmin), C.c_float(cone))) * jit))
         wdir = (d + f(1)) * f(0.5)
-        rec = []
+        rec, mips = [], []
         guard = 0
         while len(rec) < max_steps and guard < 200000:
             guard += 1
@@ -407,10 +410,13 @@ def march(orc_lib, bitfield, aabb, rays, jitter, cone, tmin_nudge_ulps=0, max_st
             if bits[cell // 8 + (grid_vol * mip) // 8] & (1 << (cell % 8)):
                 wpos = (pos - mn) / (mx - mn)
                 rec.append(np.concatenate([wpos.astype(f), [f(orc_lib.orc_warp_dt(C.c_float(dt)))], wdir.astype(f)]).astype(f))
+                mips.append(mip)
                 t = f(t + dt)
             else:
                 t = f(orc_lib.orc_advance_to_next_voxel(C.c_float(t), C.c_float(cone), pp, d.ctypes.data, 128 >> mip))
         records.append(np.asarray(rec, f).reshape(-1, 7))
+        if mips_out is not None:
+            mips_out.append(np.asarray(mips, np.int64))
     return records
 
 
@@ -422,6 +428,84 @@ def layout_from_counts(counts, max_samples):
     emit = (counts > 0) & (bases + counts <= max_samples)
     idx = np.nonzero(emit)[0]
     return np.stack([counts[idx], bases[idx]], 1), idx, (int(emit.sum()), int(counts.sum())), bases
+
+
+# ---- the generator in large boxes -----------------------------------------------------------------------------------------------------------------------------
+GRID_VOLUME, GRID_CASCADES = 128 ** 3, 5
+LARGE_SCENE_CASES = [(4, 0.0), (4, 1.0 / 256.0), (16, 0.0), (16, 1.0 / 256.0)]  # (aabb_scale, cone_angle_constant)
+
+
+def scene_aabb(scale):
+    """the box of side `scale` around 0.5 (float32-exact for every power of two)"""
+    return ((0.5 - 0.5 * scale,) * 3, (0.5 + 0.5 * scale,) * 3)
+
+
+def block_bitfield(seed, share=0.3):
+    """An occupancy in which, in each of the five cascades, every block of 4 x 4 x 4 cells (64 consecutive cells in Morton order: 8 bytes) is occupied with
+    probability `share`: empty space and occupied space alternate in every cascade, so both branches of the walk run everywhere."""
+    blocks = np.random.default_rng(seed).random(GRID_CASCADES * GRID_VOLUME // 64) < share
+    return np.repeat(np.where(blocks, 255, 0).astype(np.uint8), 8)
+
+
+def large_scene_rays(scale, seed):
+    """52 float32 unit rays and a jitter each for a box of side `scale`: 16 from a sphere outside the box, 16 from inside the box (0.5 +- 0.45 scale: mostly outside
+    the unit cube, entry distance 0), 16 from inside the unit cube, all aimed at a point within 0.5 +- 0.3 min(scale / 2, 3); then (1, 0, 0) from outside and
+    (0, -1, 0) from inside (infinite components of 1 / d), a ray that misses the box, and one that starts exactly on the face x = 0.5 - scale / 2.
+    Returns (rays [52, 6], jitter [52], index of the missing ray)."""
+    rng = np.random.default_rng(seed)
+    f = np.float32
+    o = rng.normal(size=(16, 3))
+    o = 0.5 + 1.2 * np.sqrt(3.0) * scale / 2 * o / np.linalg.norm(o, axis=1, keepdims=True)
+    o = np.concatenate([o, rng.uniform(0.5 - 0.45 * scale, 0.5 + 0.45 * scale, (16, 3)), rng.uniform(0.0, 1.0, (16, 3))]).astype(f)
+    reach = 0.3 * min(scale / 2, 3)
+    d = rng.uniform(0.5 - reach, 0.5 + reach, (48, 3)).astype(f) - o
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(f)
+    lo = 0.5 - scale / 2
+    edge = np.array([[lo - 1.0, 0.5 + 0.21 * scale, 0.5 - 0.13 * scale, 1.0, 0.0, 0.0],
+                     [0.5 - 0.17 * scale, 0.5 + 0.4 * scale, 0.5 + 0.11 * scale, 0.0, -1.0, 0.0],
+                     [lo - 1.0, 0.5 + 0.45 * scale, 0.5, 0.6, 0.8, 0.0],   # (leaves the box's y range before it reaches its x range)
+                     [lo, 0.5 + 0.1 * scale, 0.5 - 0.3 * scale, 0.6, 0.0, 0.8]], f)
+    rays = np.concatenate([np.concatenate([o, d], 1), edge]).astype(f)
+    return rays, rng.random(len(rays)).astype(f), 50
+
+
+class LargeSceneWalk:
+    pass
+
+
+def large_scene_walk(orc_lib, scale, cone, seed=None):
+    """The twin's walk of large_scene_rays through block_bitfield in the box of side `scale`, at the three entry distances: rays, jitter, bitfield, the records and
+    cascades of the walk as it stands, its counts, which rays are stable, which start at distance 0, and the samples per cascade."""
+    w = LargeSceneWalk()
+    seed = 500 + scale if seed is None else seed
+    w.scale, w.cone, w.aabb = scale, cone, scene_aabb(scale)
+    w.rays, w.jitter, w.missing = large_scene_rays(scale, seed)
+    w.bitfield = block_bitfield(seed + 1)
+    w.mips = []
+    with np.errstate(over="ignore", invalid="ignore"):  # (the missing ray: FLT_MAX moved up two steps, and a position at infinity)
+        walks = {k: march(orc_lib, w.bitfield, w.aabb, w.rays, w.jitter, cone, tmin_nudge_ulps=k, mips_out=w.mips if k == 0 else None) for k in (-2, 0, 2)}
+    counts = {k: np.array([len(r) for r in v]) for k, v in walks.items()}
+    w.walk, w.counts = walks[0], counts[0]
+    w.stable = (counts[-2] == counts[0]) & (counts[0] == counts[2])
+    mn, mx = np.asarray(w.aabb[0], np.float32), np.asarray(w.aabb[1], np.float32)
+    w.tmin = np.array([ray_tmin(mn, mx, r[:3], r[3:]) for r in w.rays])
+    w.per_cascade = np.bincount(np.concatenate(w.mips), minlength=GRID_CASCADES)
+    w.max_warped_dt = max((float(r[:, 3].max()) for r in w.walk if len(r)), default=0.0)
+    return w
+
+
+def assert_large_scene_coverage(walks):
+    """What the four cases must exercise, from the twin alone: {(scale, cone): LargeSceneWalk}.  Conditions on the inputs."""
+    for (scale, cone), w in walks.items():
+        assert w.stable.mean() >= 0.98, (scale, cone, float(w.stable.mean()))
+        assert w.counts[w.missing] == 0 and w.tmin[w.missing] > 1e38, "the missing ray misses"
+        assert int((w.tmin == 0).sum()) >= 10, "cameras inside the box: entry distance 0"
+        assert (w.counts > 0).sum() >= 30
+    for scale, top in ((16, 4), (4, 3)):
+        w = walks[scale, 1.0 / 256.0]
+        assert (w.per_cascade[:top + 1] > 0).all(), (scale, w.per_cascade)
+    assert walks[16, 1.0 / 256.0].max_warped_dt > 1.0, "steps beyond 16 minimum steps: a warped dt above 1"
+    assert int((walks[16, 0.0].counts == 1024).sum()) >= 1, "a ray that ends on the 1024-sample limit"
 
 
 # ---- batches ------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -462,33 +546,53 @@ def _common(rng, numsteps, n, ld, per_ray_bg, with_origins):
 
 
 def random_batch(seed, n_rays=200, max_count=130, ld=7, gaps=True, per_ray_bg=True, rgb_act_kind=ACT_LOGISTIC, den_act_kind=ACT_EXPONENTIAL, cap=None,
-                 density_mean=3.0, density_max=9.0, with_origins=False, **params):
-    """rays of 0..max_count samples; densities spread so that some rays stop early (exponential activation) and most do not"""
+                 density_mean=3.0, density_max=9.0, with_origins=False, dt_steps=(1.0, 4.0), aabb=AABB_UNIT, **params):
+    """rays of 0..max_count samples; densities spread so that some rays stop early (exponential activation) and most do not.
+    dt_steps: the range of a sample's dt in minimum steps -- uniform up to 4, log-uniform when the upper bound exceeds 4 (a cone's steps: up to 128), and then every
+    raw density is lowered by ln(dt / MIN_STEP) before it is rounded to fp16, so that the optical depth of a sample (exponential activation) keeps the spread it has
+    at short steps.  aabb: the box the batch names; origins are drawn uniform inside it (positions are warped: uniform in every box).
+    The defaults give the batches this function always gave, bit for bit (tests/test_ray_loss_host.py pins one)."""
     rng = np.random.default_rng(seed)
     counts = rng.integers(0, max_count + 1, n_rays)
     numsteps, n = _layout(rng, counts, gaps)
     coords, target, bg, origins = _common(rng, numsteps, n, ld, per_ray_bg, with_origins)
-    coords[:, 3] = [warp_dt_of(MIN_STEP * s) for s in rng.uniform(1.0, 4.0, n)]
+    wide = dt_steps[1] > 4.0
+    steps = np.exp(rng.uniform(np.log(dt_steps[0]), np.log(dt_steps[1]), n)) if wide else rng.uniform(dt_steps[0], dt_steps[1], n)
+    coords[:, 3] = [warp_dt_of(MIN_STEP * s) for s in steps]
+    if origins is not None and aabb is not AABB_UNIT:
+        mn, mx = np.asarray(aabb[0], np.float32), np.asarray(aabb[1], np.float32)
+        origins = (mn + origins * (mx - mn)).astype(np.float32)
     out = np.zeros((n, 4))
     out[:, :3] = _half(rng.normal(0.0, 1.5, (n, 3)))
     ray_mean = np.zeros(n)
     for r in range(n_rays):
         ray_mean[numsteps[r, 1]:numsteps[r, 1] + numsteps[r, 0]] = rng.normal(density_mean, 1.5)
-    out[:, 3] = _half(np.clip(ray_mean + rng.normal(0.0, 1.0, n), -9.0, density_max))
+    raw = np.clip(ray_mean + rng.normal(0.0, 1.0, n), -9.0, density_max)
+    if wide:
+        raw = raw - np.log(unwarp_dt(coords[:, 3].astype(np.float64)) / MIN_STEP)
+    out[:, 3] = _half(raw)
     total = int(counts.sum())
-    return dict(out=out, coords=coords, numsteps=numsteps, target=target, background=bg, origins=origins, rgb_act=rgb_act_kind, den_act=den_act_kind, aabb=AABB_UNIT,
+    return dict(out=out, coords=coords, numsteps=numsteps, target=target, background=bg, origins=origins, rgb_act=rgb_act_kind, den_act=den_act_kind, aabb=aabb,
                 p=_params(total + 7 if cap is None else cap, **params))
 
 
-def constructed_batch(seed, ld=7, cap_slack=9, repeats=6, **params):
+def big_box_batch(scale, seed=None, **kw):
+    """random_batch at a cone's steps in a box of side `scale`: dt of 1..128 minimum steps, Huber loss, the density regulariser, and the near-distance term at 3 / 8 of
+    the box's side (6.0 at scale 16, 1.5 at scale 4) from per-ray origins inside the box."""
+    return random_batch(310 + scale if seed is None else seed, dt_steps=(1.0, 128.0), aabb=scene_aabb(scale), loss_type=HUBER, l1=True, near_distance=0.375 * scale,
+                        with_origins=True, **kw)
+
+
+def constructed_batch(seed, ld=7, cap_slack=9, repeats=6, dt_steps=4.0, **params):
     """CONSTRUCTED_COUNTS (`repeats` times over, each time with other stops) with decisive stops: a ray either keeps its optical depth at 4.5 or below, or has one sample with sigma dt > 30 -- at sample 0, mid-chunk, either
     side of lane 31|32, the last lane of a chunk, the first of the next, the last sample but one (M == N - 1) or the last (M == N, the background term).
-    Logistic colours, exponential density.  Returns (batch, expected M per ray)."""
+    Logistic colours, exponential density; every sample's dt is dt_steps minimum steps, and the densities derive from it (a stop has sigma dt > 30 from 4 steps on).
+    Returns (batch, expected M per ray)."""
     rng = np.random.default_rng(seed)
     counts = np.asarray(CONSTRUCTED_COUNTS * repeats, np.int64)
     numsteps, n = _layout(rng, counts, True)
     coords, target, bg, origins = _common(rng, numsteps, n, ld, True, False)
-    coords[:, 3] = warp_dt_of(MIN_STEP * 4.0)
+    coords[:, 3] = warp_dt_of(MIN_STEP * dt_steps)
     dt = float(unwarp_dt(np.float64(coords[0, 3])))
     out = np.zeros((n, 4))
     out[:, :3] = _half(rng.normal(0.0, 1.5, (n, 3)))

@@ -3,7 +3,9 @@ surface exists and refuses bad arguments before it touches a device, and the gen
 
 Which of these guard the library: test_surface_exists, test_struct_size_matches_the_library and test_bad_arguments_are_refused_without_a_device fail without the
 feature.  The others (autograd against closed form, the hand-computed ray, the accuracy unit, the generator's stability) pin the TWIN that the GPU tests compare
-the library with, not the library: they pass on any tree that holds tests/ray_loss_ref.py."""
+the library with, not the library: they pass on any tree that holds tests/ray_loss_ref.py.  So do the tests of the large-scene inputs: the default batches are bit for bit what they
+were before random_batch took dt_steps and aabb, the two big-box batches meet the conditions the GPU comparison needs, and the generator's four large-box cases
+reach every cascade, the 1024-sample limit and an entry distance of 0."""
 import ctypes as C
 
 import numpy as np
@@ -142,6 +144,68 @@ def test_the_accuracy_unit():
         err = ref.error_units(ref.to_fp16_values(c32.dl.numpy()[used]), c.dl.numpy()[used], c.A.numpy()[used])
         print(f"{name}: closed_form32 against closed_form, worst error per row {err.max(0)} units of 2^-23 A over {int(used.sum())} samples")
         assert np.isfinite(err).all()
+
+
+def _batch_hash(b):
+    import hashlib
+    m = hashlib.sha256()
+    for k in ("out", "coords", "numsteps", "target", "background", "origins"):
+        m.update(k.encode())
+        m.update(b"none" if b[k] is None else np.ascontiguousarray(b[k]).tobytes())
+    m.update(repr((b["rgb_act"], b["den_act"], b["aabb"], sorted(b["p"].items()))).encode())
+    return m.hexdigest()
+
+
+def test_default_batches_are_what_they_were():
+    """random_batch and constructed_batch took dt_steps and aabb after these hashes were taken (of test_activations' batch 74, test_every_loss_and_colour_path's
+    batch 140 and the constructed batch): their defaults give the same bytes."""
+    assert _batch_hash(ref.random_batch(74, rgb_act_kind=1, den_act_kind=0, l1=True, near_distance=0.7, with_origins=True, loss_type=ref.HUBER)) == \
+        "8d36b56a06d18f057850bef3b4d3353a3c6b3b6c02a2168b85a2c6e77e434eb4"
+    assert _batch_hash(ref.random_batch(140)) == "b0a095b130f5136bb0ee32caa994f98f833f84ae9b4bfcfaa4ab766745afa928"
+    assert _batch_hash(ref.constructed_batch(3)[0]) == "f19bea9e51c71d06f1803d5edf313c3e1149da5e502dd8c370a234674feaa3d5"
+
+
+@pytest.mark.parametrize("scale", [16, 4])
+def test_big_box_batches_are_what_the_gpu_tests_need(scale):
+    """The two batches of tests/test_gpu_ray_loss.py::test_long_steps_in_a_big_box, judged with the twins alone: conditions on the INPUTS, so that the GPU comparison
+    covers what it is for -- steps up to 128 minimum steps (warped dt up to 8.47), rays that stop early and rays that do not, samples on both sides of the near
+    distance and none so close to it that float32 could not decide, the float32 twin consuming what the float64 twin consumes, and gradients that an fp16 holds."""
+    b = ref.big_box_batch(scale)
+    assert b["aabb"] == ref.scene_aabb(scale) and b["p"]["near_distance"] == {16: 6.0, 4: 1.5}[scale]
+    c, c32 = ref.closed_form(b), ref.closed_form32(b)
+    f = c.f
+    wdt = b["coords"][:, 3]
+    assert wdt.max() > 8.0 and wdt.min() < 0.1
+    left_out = float(f.near_threshold.numpy().mean())
+    has = (f.N > 0).numpy()
+    stopped = float(((f.M < f.N).numpy() & has).sum() / has.sum())
+    used = (c.src >= 0).numpy()
+    src, ray_of = c.src.numpy()[used], c.ray_of.numpy()[used]
+    mn, mx = (np.asarray(v, np.float64) for v in b["aabb"])
+    dist = np.linalg.norm(mn + b["coords"][src, :3].astype(np.float64) * (mx - mn) - b["origins"][ray_of].astype(np.float64), axis=1)
+    near = float(np.float32(b["p"]["near_distance"]))
+    within, closest = float((dist < near).mean()), float(np.abs(dist / near - 1.0).min())
+    normal = float((np.abs(c.dl.numpy()[used]) >= 2.0 ** -14).mean())
+    print(f"big box, scale {scale}: left out {left_out:.3f}, stopped early {stopped:.3f}, within the near distance {within:.3f} (closest {closest:.1e} relative), "
+          f"fp16-normal {normal:.3f}, warped dt max {wdt.max():.2f}, raw density min {b['out'][:, 3].min():.2f}")
+    assert left_out <= 0.01
+    assert 0.1 <= stopped <= 0.6
+    assert 0.05 <= within <= 0.5
+    assert closest > 1e-6
+    assert torch.equal(c32.f.M, f.M)
+    assert normal >= 0.3
+
+
+def test_large_scene_rays_cover_what_they_are_for(built):
+    """The generator's four large-box cases (tests/test_gpu_training_large_scenes.py) through the twin alone: every cascade the cone reaches, steps beyond 16
+    minimum steps, a ray on the 1024-sample limit, cameras inside the box, stable counts."""
+    from oracle import oracle as orc
+    lib = orc.load()
+    walks = {case: ref.large_scene_walk(lib, *case) for case in ref.LARGE_SCENE_CASES}
+    for (scale, cone), w in walks.items():
+        print(f"scale {scale} cone {cone:.5f}: {len(w.rays)} rays, {int((w.counts > 0).sum())} with samples, {int(w.counts.sum())} samples, per cascade {w.per_cascade.tolist()}, "
+              f"stable {w.stable.mean():.3f}, entry distance 0: {int((w.tmin == 0).sum())}, on the limit {int((w.counts == 1024).sum())}, warped dt max {w.max_warped_dt:.2f}")
+    ref.assert_large_scene_coverage(walks)
 
 
 @pytest.fixture(scope="module")
