@@ -990,8 +990,8 @@ size_t   nrs_optimizer_n_params(const nrs_optimizer* opt, size_t* n_matrix);
 /* What stands in front of nrs_training_samples: the first half of generate_training_samples_nerf (src/testbed_nerf.cu:1087-1186: image and pixel selection, the camera
  * of the pixel's time, lens distortion), the look-ups compute_loss_kernel_train_nerf repeats for a ray's target and background (:1777-1806), the loader's image
  * conversion (from_rgba32, common_device.cuh:513-540; from_fullp, src/nerf_loader.cu:62) and mark_untrained_density_grid (:353-400).  Callers detect these entry
- * points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  Not here: the error-map CDFs (cdf_img, cdf_x_cond_y: the `cdf == nullptr`
- * branches are the ones built), explicit per-pixel rays (rays_in), the trainable per-pixel distortion map, the envmap and exposure, light directions (a dataset serves
+ * points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  The error-map CDFs (cdf_img, cdf_x_cond_y) are
+ * nrs_dataset_rays_ex's, further down: nrs_dataset_rays is the `cdf == nullptr` branches.  Not here: explicit per-pixel rays (rays_in), the trainable per-pixel distortion map, the envmap and exposure, light directions (a dataset serves
  * n_extra_dims == 0 models), sharpening and the sharpness map, EXR, the adaptive rays_per_batch of train_nerf (it reads counters back), decoding image files (the
  * Python package does that).
  *
@@ -1065,6 +1065,81 @@ int  nrs_dataset_rays(nrs_dataset* ds, void* stream, const nrs_dataset_rays_para
                       float* d_background, uint32_t* d_pixels);
 int  nrs_dataset_mark_untrained(nrs_model* model, nrs_dataset* ds, int clear_visible_voxels, void* stream);
 void nrs_rng_advance(uint64_t* state, uint64_t inc, uint64_t delta);
+
+/* ---- the training error map: accumulate, CDFs, rays sampled in proportion to it ---------------------------------------------------------------------- */
+/* The error map of train_nerf (src/testbed_nerf.cu:3724-3831): every ray's loss is deposited into a small per-image map (:1861-1886), the map is turned into three
+ * CDFs (construct_cdf_2d :2620, construct_cdf_1d :2650, the host loop :3811-3822), and the next steps' images and pixels are drawn from them (image_idx :1052,
+ * sample_cdf_2d :983).  All of it is state of an nrs_dataset and runs on the device with nothing read back; all of it is new surface, detected by symbol
+ * (nrs_dataset_rays_ex); nrs_dataset_rays and nrs_ray_loss are what they were.  Not here: the sharpness map and include_sharpness_in_error (:1872-1881).
+ *
+ * THREE DEVIATIONS, all deliberate:
+ *  1. The cells are unsigned 64-bit fixed point, not floats: no float atomic on the training path, and two calls give the same bits.  A deposit v (float32) is
+ *     skipped unless v > 0 (that also drops NaN); otherwise it adds (uint64)(min(v, 1024.f) * 4294967296.f) -- the product is exact, the conversion truncates, the
+ *     add is one no-return 64-bit integer atomic.  Integer sums do not depend on the order of arrival, so the map, the CDFs and every ray drawn from them are
+ *     reproducible.  2^21 deposits of the clamp value fit without a wrap.  The float map the reference keeps is (float)cell * 2^-32, formed where it is read.
+ *  2. The deposit is e = (loss[slot] * n_rays) / pdf with loss[slot] the per-slot mean nrs_ray_loss wrote.  The reference divides each channel's loss by the pdf and
+ *     then averages (:1848, :1856): a few float32 roundings apart.  The map steers sampling; it is part of no gradient (nor is the pdf, in the reference: :1850-1854).
+ *  3. The map's resolution lies in [2, min(image resolution, 1024)] on each axis.  At resolution 1 the reference's own deposit writes cell x + 1 outside the map; with
+ *     the map no finer than the image, the reference's clamp of the cell index by the IMAGE resolution (:1866) never acts: the position is already clamped to
+ *     res - (1 + 1e-4), so the cell is at most res - 2.  (The kernel clamps the cell into [0, res - 2] for the sake of a NaN in d_xy; for every other input that is
+ *     the same cell.)
+ *
+ * nrs_dataset_error_map_reset: (re)allocates and zeroes n_images x res_y x res_x cells (:3724-3728), asynchronous on `stream` (a reallocation waits for the device).
+ *   Valid CDFs carry their own resolution (cdf_resolution beside resolution) and survive.
+ * nrs_error_map_resolution (host only): one axis of the reference's choice, (int)(sqrtf(sqrtf((float)((steps_between * rays_per_batch) / n_images))) * 3.5f) with the
+ *   product in 32-bit unsigned arithmetic, clamped into [2, min(image_resolution, 1024)]; 0 when n_images == 0 or image_resolution < 2 (no map is possible).
+ * nrs_dataset_error_map_set: the map from res_y x res_x x n_images floats of the host, each quantised by the deposit rule (what it skips is 0).  Synchronous.
+ * nrs_dataset_error_map_get: `what` to the host, synchronous; *count (may be NULL) receives the number of elements, h_out may be NULL to ask for the count alone.
+ *   NRS_ERROR_MAP_FLOAT: (float)cell * 2^-32 [n_images][res_y][res_x] f32;  NRS_ERROR_MAP_CELLS: the cells, uint64;  NRS_ERROR_MAP_CDF_X_COND_Y [n_images][res_y][res_x],
+ *   _CDF_Y [n_images][res_y], _CDF_IMG [n_images], _PMF_IMG [n_images]: f32, at the CDFs' resolution.  For tests, checkpoints and display.
+ * nrs_dataset_error_map_accumulate: one thread per ray slot s < min(*d_ray_counter, n_rays).  i = d_ray_indices[s] (nrs_training_samples), img = d_pixels[2 i],
+ *   xy = d_xy[2 i ..], p = d_pdf ? d_pdf[i] : 1, e = (d_loss[s] * (float)n_rays) / p, then :1862-1886: pos = clamp(xy * res - 0.5, 0, res - (1 + 1e-4f)), truncated to
+ *   the cell, the fraction is the weight, four bilinear products (1 - wx) * (1 - wy) * e ... evaluated left to right, each deposited by rule 1.  d_loss_weighted (NULL,
+ *   or it may alias d_loss) receives d_loss[s] / p: the loss the reference reports (:1848).  A slot whose loss is 0 deposits nothing (the early return at :1838).
+ *   A slot whose ray index is not below n_rays or whose image is not below n_images is skipped.
+ * nrs_dataset_error_map_build_cdfs: per (image, row) the running sum of data[x] + 1e-10f in ascending x, the row's total into cdf_y, then
+ *   (1.0f - 0.01f) * c * (1.0f / total) + 0.01f * (float)(x + 1) / (float)width;  the same over a picture's rows (no 1e-10f), the total into cdf_img;  over the images
+ *   with MIN_PMF = 0.1f: pmf_img = (1.0f - 0.1f) * total * norm + 0.1f / n_images, cdf_img likewise with (float)(i + 1) / n_images.  IEEE division, no contraction,
+ *   products and sums in the written order; THE SERIAL ASSOCIATION OF EACH RUNNING SUM IS PART OF THE DEFINITION.  Records the CDFs' resolution and marks them valid.
+ * nrs_error_map_cdfs_host (host only): the same expressions on the host, data = the float map; outputs sized as nrs_dataset_error_map_get lays them out.
+ *
+ * nrs_dataset_rays_ex: nrs_dataset_rays with two switches and two more outputs, d_xy [n x 2] f32 (xy after snapping: what the accumulate needs) and d_pdf [n] f32 =
+ *   img_pdf * xy_pdf (either may be NULL).  With both switches off every output it shares with nrs_dataset_rays has that call's bits and the pdf is exactly 1.  The
+ *   generator's draw order is the same under every switch -- no draw is added -- so jitter, background and motion-blur time keep their bits.
+ *   binary_search (common.h:187-210): the first index whose entry is not < val, capped at length - 1.
+ *   sample_images_by_error (image_idx, :1052-1064): img = binary_search(ld_random_val(i + n_rays_total, 0xdeadbeef), cdf_img, n_images), img_pdf = (cdf_img[img] - prev)
+ *     * n_images.
+ *   sample_pixels_by_error (sample_cdf_2d, :983-1012, on draws 0 and 1): x < 0.5f is the uniform half, x /= 0.5f and xy_pdf stays 1.  Otherwise x = (x - 0.5f) /
+ *     (1.0f - 0.5f); the row comes from cdf_y and y = (y - prev) / pmf_y; the column from that row of cdf_x_cond_y and x = (x - prev) / pmf_x; xy_pdf = pmf_x * pmf_y *
+ *     (res_x * res_y); xy = ((float)col + x) / res_x, ((float)row + y) / res_y.  xy_pdf is the density of the CDF half ALONE, not the mixture's (pdf_2d, :1014): that
+ *     is what the reference divides by, and it is kept.  Then snap_to_pixel_centers and everything behind it as in nrs_dataset_rays.
+ *
+ * Refused before any HIP call, NRS_ERR_INVALID_ARG: NULL handles, a wrong struct_size, NULL inputs or outputs that are required, a resolution outside
+ *   [2, min(image resolution, 1024)], an unknown `what`, n_rays > 2^21.  NRS_ERR_STATE: accumulate, get (map or cells), build_cdfs without a map; get of a CDF and
+ *   nrs_dataset_rays_ex with a switch on without valid CDFs; nrs_dataset_rays_ex while an image or a camera has never been set. */
+typedef enum nrs_error_map_what {
+	NRS_ERROR_MAP_FLOAT = 0, NRS_ERROR_MAP_CDF_X_COND_Y = 1, NRS_ERROR_MAP_CDF_Y = 2, NRS_ERROR_MAP_CDF_IMG = 3, NRS_ERROR_MAP_PMF_IMG = 4, NRS_ERROR_MAP_CELLS = 5
+} nrs_error_map_what;
+#define NRS_ERROR_MAP_MAX_RESOLUTION 1024u
+typedef struct nrs_dataset_rays_ex_params {
+	uint32_t struct_size;          /* refused unless == sizeof(nrs_dataset_rays_ex_params) */
+	uint32_t n_rays_total;
+	uint64_t rng_state, rng_inc;
+	uint32_t snap_to_pixel_centers;
+	uint32_t random_bg_color;
+	uint32_t sample_images_by_error;   /* sample_image_proportional_to_error */
+	uint32_t sample_pixels_by_error;   /* sample_focal_plane_proportional_to_error */
+} nrs_dataset_rays_ex_params;
+int      nrs_dataset_error_map_reset(nrs_dataset* ds, uint32_t res_x, uint32_t res_y, void* stream);
+uint32_t nrs_error_map_resolution(uint32_t steps_between, uint32_t rays_per_batch, uint32_t n_images, uint32_t image_resolution);
+int      nrs_dataset_error_map_set(nrs_dataset* ds, uint32_t res_x, uint32_t res_y, const float* h_data_f32);
+int      nrs_dataset_error_map_get(nrs_dataset* ds, int what, void* h_out, size_t* count);
+int      nrs_dataset_error_map_accumulate(nrs_dataset* ds, void* stream, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices, const float* d_loss,
+                                          const float* d_xy, const uint32_t* d_pixels, const float* d_pdf, float* d_loss_weighted);
+int      nrs_dataset_error_map_build_cdfs(nrs_dataset* ds, void* stream);
+int      nrs_error_map_cdfs_host(uint32_t n_images, uint32_t res_y, uint32_t res_x, const float* data, float* cdf_x_cond_y, float* cdf_y, float* cdf_img, float* pmf_img);
+int      nrs_dataset_rays_ex(nrs_dataset* ds, void* stream, const nrs_dataset_rays_ex_params* params, uint32_t n_rays, float* d_rays, float* d_jitter, float* d_target_rgba,
+                             float* d_background, uint32_t* d_pixels, float* d_xy, float* d_pdf);
 
 #ifdef __cplusplus
 }

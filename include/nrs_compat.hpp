@@ -204,6 +204,27 @@ public:
 	void mark_untrained(NerfNetwork& network, bool clear_visible_voxels, void* stream) {
 		check(nrs_dataset_mark_untrained(network.get(), m_ds, clear_visible_voxels ? 1 : 0, stream), "nrs_dataset_mark_untrained");
 	}
+	// the training error map (m_nerf.training.error_map): its cells, the CDFs built from them, and rays drawn in proportion to them -- rays() with two switches and
+	// two more outputs, d_xy [n x 2] (what error_map_accumulate reads) and d_pdf [n]
+	void error_map_reset(uint32_t res_x, uint32_t res_y, void* stream) { check(nrs_dataset_error_map_reset(m_ds, res_x, res_y, stream), "nrs_dataset_error_map_reset"); }
+	void error_map_set(uint32_t res_x, uint32_t res_y, const float* h_data) { check(nrs_dataset_error_map_set(m_ds, res_x, res_y, h_data), "nrs_dataset_error_map_set"); }
+	size_t error_map_get(nrs_error_map_what what, void* h_out) { // h_out == nullptr: the number of elements alone
+		size_t count = 0;
+		check(nrs_dataset_error_map_get(m_ds, what, h_out, &count), "nrs_dataset_error_map_get");
+		return count;
+	}
+	void error_map_accumulate(void* stream, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices, const float* d_loss, const float* d_xy,
+	                          const uint32_t* d_pixels, const float* d_pdf = nullptr, float* d_loss_weighted = nullptr) {
+		check(nrs_dataset_error_map_accumulate(m_ds, stream, n_rays, d_ray_counter, d_ray_indices, d_loss, d_xy, d_pixels, d_pdf, d_loss_weighted), "nrs_dataset_error_map_accumulate");
+	}
+	void error_map_build_cdfs(void* stream) { check(nrs_dataset_error_map_build_cdfs(m_ds, stream), "nrs_dataset_error_map_build_cdfs"); }
+	void rays_by_error(void* stream, uint32_t n_rays, uint32_t n_rays_total, uint64_t rng_state, uint64_t rng_inc, bool sample_images, bool sample_pixels, float* d_rays,
+	                   float* d_jitter, float* d_target_rgba, float* d_background, uint32_t* d_pixels, float* d_xy, float* d_pdf, bool snap_to_pixel_centers = true,
+	                   bool random_bg_color = true) {
+		const nrs_dataset_rays_ex_params p{(uint32_t)sizeof(nrs_dataset_rays_ex_params), n_rays_total, rng_state, rng_inc, snap_to_pixel_centers ? 1u : 0u, random_bg_color ? 1u : 0u,
+		                                   sample_images ? 1u : 0u, sample_pixels ? 1u : 0u};
+		check(nrs_dataset_rays_ex(m_ds, stream, &p, n_rays, d_rays, d_jitter, d_target_rgba, d_background, d_pixels, d_xy, d_pdf), "nrs_dataset_rays_ex");
+	}
 	nrs_dataset* get() const { return m_ds; }
 
 private:

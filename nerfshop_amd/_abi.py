@@ -222,6 +222,21 @@ class DatasetRaysParams(C.Structure):
         self.struct_size = C.sizeof(DatasetRaysParams)
 
 
+class DatasetRaysExParams(C.Structure):
+    """nrs_dataset_rays_ex_params; struct_size is filled in on construction."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays_total", C.c_uint32), ("rng_state", C.c_uint64), ("rng_inc", C.c_uint64), ("snap_to_pixel_centers", C.c_uint32),
+                ("random_bg_color", C.c_uint32), ("sample_images_by_error", C.c_uint32), ("sample_pixels_by_error", C.c_uint32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(DatasetRaysExParams)
+
+
+# nrs_error_map_what
+ERROR_MAP_FLOAT, ERROR_MAP_CDF_X_COND_Y, ERROR_MAP_CDF_Y, ERROR_MAP_CDF_IMG, ERROR_MAP_PMF_IMG, ERROR_MAP_CELLS = 0, 1, 2, 3, 4, 5
+ERROR_MAP_MAX_RESOLUTION = 1024  # NRS_ERROR_MAP_MAX_RESOLUTION
+
+
 IMAGE_RGBA8_SRGB, IMAGE_RGBA32F_LINEAR, IMAGE_RGBA16F_LINEAR = 0, 1, 2  # nrs_image_format
 IMAGE_WHITE_TRANSPARENT, IMAGE_BLACK_TRANSPARENT = 1, 2  # NRS_IMAGE_WHITE_TRANSPARENT / _BLACK_TRANSPARENT
 RNG_STEP_DELTA = 1 << 32  # NRS_RNG_STEP_DELTA
@@ -264,6 +279,8 @@ EXPORTS = [
     "nrs_optimizer_step", "nrs_optimizer_get_state", "nrs_optimizer_set_state", "nrs_optimizer_export_fp16", "nrs_optimizer_step_count", "nrs_optimizer_set_step_count",
     "nrs_optimizer_n_params",
     "nrs_dataset_create", "nrs_dataset_destroy", "nrs_dataset_set_image", "nrs_dataset_set_camera", "nrs_dataset_get_image", "nrs_dataset_rays", "nrs_dataset_mark_untrained", "nrs_rng_advance",
+    "nrs_dataset_error_map_reset", "nrs_error_map_resolution", "nrs_dataset_error_map_set", "nrs_dataset_error_map_get", "nrs_dataset_error_map_accumulate",
+    "nrs_dataset_error_map_build_cdfs", "nrs_error_map_cdfs_host", "nrs_dataset_rays_ex",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -383,6 +400,16 @@ def load():
         lib.nrs_dataset_mark_untrained.argtypes = [P, P, I, P]
         lib.nrs_rng_advance.argtypes = [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64]
         lib.nrs_rng_advance.restype = None
+    if hasattr(lib, "nrs_dataset_rays_ex"):  # the training error map (detected by symbol)
+        lib.nrs_dataset_error_map_reset.argtypes = [P, U32, U32, P]
+        lib.nrs_error_map_resolution.argtypes = [U32, U32, U32, U32]
+        lib.nrs_error_map_resolution.restype = U32
+        lib.nrs_dataset_error_map_set.argtypes = [P, U32, U32, P]
+        lib.nrs_dataset_error_map_get.argtypes = [P, I, P, C.POINTER(C.c_size_t)]
+        lib.nrs_dataset_error_map_accumulate.argtypes = [P, P, U32, P, P, P, P, P, P, P]
+        lib.nrs_dataset_error_map_build_cdfs.argtypes = [P, P]
+        lib.nrs_error_map_cdfs_host.argtypes = [U32, U32, U32, P, P, P, P, P]
+        lib.nrs_dataset_rays_ex.argtypes = [P, P, C.POINTER(DatasetRaysExParams), U32, P, P, P, P, P, P, P]
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

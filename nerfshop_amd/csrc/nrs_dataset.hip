@@ -2,6 +2,9 @@
 //
 //   dataset_convert_*       the loader's image conversion: from_rgba32<__half> (common_device.cuh:513-540), from_fullp (src/nerf_loader.cu:62).
 //   dataset_rays_kernel     generate_training_samples_nerf up to the ray (tn:1087-1186) and the target / background look-ups of the loss kernel (tn:1777-1806).
+//   dataset_rays_kernel<true>    the same with the image drawn from cdf_img (tn:1052-1064) and the pixel from cdf_y / cdf_x_cond_y (tn:983-1012): nrs_dataset_rays_ex.
+//   error_map_accumulate_kernel  the loss kernel's deposits into the error map (tn:1861-1886), in 64-bit fixed point.
+//   error_map_cdf_kernel         construct_cdf_2d (tn:2620), construct_cdf_1d (tn:2650) and train_nerf's host loop over the images (tn:3811-3822).
 //   mark_untrained_kernel   mark_untrained_density_grid (tn:353-400).
 #include <hip/hip_runtime.h>
 #include "nrs_dataset.h"
@@ -83,16 +86,57 @@ __device__ __forceinline__ void dataset_ray(C c, uint32_t W, uint32_t H, float u
 	d = {d.x / n, d.y / n, d.z / n};
 }
 
+// binary_search (common.h:187-210): the first index whose entry is not < val, capped at length - 1 (length >= 1)
+__device__ __forceinline__ uint32_t cdf_search(float val, const float* __restrict__ data, uint32_t length) {
+	uint32_t first = 0, count = length;
+	while (count > 0) {
+		const uint32_t step = count / 2, it = first + step;
+		if (data[it] < val) { first = it + 1; count -= step + 1; }
+		else count = step;
+	}
+	return min(first, length - 1);
+}
+
+// EX = false is nrs_dataset_rays: the `cdf == nullptr` branches of the reference and nothing else.  EX = true is its twin for nrs_dataset_rays_ex: the image from
+// cdf_img (image_idx, tn:1052-1064), the pixel from cdf_y and cdf_x_cond_y (sample_cdf_2d, tn:983-1012), each behind its switch, and the two outputs xy and pdf.  The
+// generator's draws are the same five in the same order in both.
+template <bool EX>
 __global__ __launch_bounds__(256) void dataset_rays_kernel(const DatasetRaysArgs a) {
 	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= a.n_rays) return;
-	const uint32_t img = (((i + a.n_rays_total) * a.n_images) / a.n_rays) % a.n_images; // image_idx, tn:1072: 32-bit, the product wraps
+	uint32_t img = (((i + a.n_rays_total) * a.n_images) / a.n_rays) % a.n_images; // image_idx, tn:1072: 32-bit, the product wraps
+	float img_pdf = 1.0f, xy_pdf = 1.0f;
+	if (EX && a.by_images) {
+		img = cdf_search(ld_random_val(i + a.n_rays_total, 0xdeadbeefu), a.cdf_img, a.n_images);
+		const float prev = img > 0 ? a.cdf_img[img - 1] : 0.0f;
+		img_pdf = (a.cdf_img[img] - prev) * (float)a.n_images;
+	}
 	Pcg32 rng{a.rng_state, a.rng_inc};
 	// N_MAX_RANDOM_SAMPLES_PER_RAY.  The plain per-lane skip loop: composing it from a wave-uniform skip and a per-lane step out of a table built once per workgroup,
 	// as grid_refresh_kernel does, was measured and lost (profiles/dataset_rays.md): a thread lives for one ray here, so the table and its barrier are never paid back.
 	rng.advance((uint64_t)(i * 8u));
 	const float W = (float)a.width, H = (float)a.height;
 	float u = rng.next_float(), v = rng.next_float(); // draws 0, 1
+	if (EX && a.by_pixels) { // sample_cdf_2d: UNIFORM_SAMPLING_FRACTION = 0.5 of the rays stay uniform, and xy_pdf is the density of the OTHER half alone (as in the reference)
+		if (u < 0.5f) {
+			u /= 0.5f;
+		} else {
+			u = (u - 0.5f) / (1.0f - 0.5f);
+			const float* cy = a.cdf_y + (size_t)img * a.cdf_res_y;
+			const uint32_t row = cdf_search(v, cy, a.cdf_res_y);
+			float prev = row > 0 ? cy[row - 1] : 0.0f;
+			const float pmf_y = cy[row] - prev;
+			v = (v - prev) / pmf_y;
+			const float* cx = a.cdf_x_cond_y + ((size_t)img * a.cdf_res_y + row) * a.cdf_res_x;
+			const uint32_t col = cdf_search(u, cx, a.cdf_res_x);
+			prev = col > 0 ? cx[col - 1] : 0.0f;
+			const float pmf_x = cx[col] - prev;
+			u = (u - prev) / pmf_x;
+			xy_pdf = pmf_x * pmf_y * (float)(int)(a.cdf_res_x * a.cdf_res_y);
+			u = ((float)col + u) / (float)(int)a.cdf_res_x;
+			v = ((float)row + v) / (float)(int)a.cdf_res_y;
+		}
+	}
 	if (a.snap) { // tn:1047
 		u = ((float)max(min((int)(u * W), (int)a.width - 1), 0) + 0.5f) / W;
 		v = ((float)max(min((int)(v * H), (int)a.height - 1), 0) + 0.5f) / H;
@@ -122,11 +166,125 @@ __global__ __launch_bounds__(256) void dataset_rays_kernel(const DatasetRaysArgs
 		b[0] = mb; b[1] = jitter; b[2] = bg2;
 	}
 	if (a.pixels) reinterpret_cast<uint2*>(a.pixels)[i] = make_uint2(img, pixel);
+	if (EX) {
+		if (a.xy) reinterpret_cast<float2*>(a.xy)[i] = make_float2(u, v);
+		if (a.pdf) a.pdf[i] = img_pdf * xy_pdf;
+	}
 }
 int launch_dataset_rays(const DatasetRaysArgs& a, void* stream) {
 	if (a.n_rays == 0) return NRS_OK;
-	hipLaunchKernelGGL(dataset_rays_kernel, dim3((a.n_rays + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+	hipLaunchKernelGGL(dataset_rays_kernel<false>, dim3((a.n_rays + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
 	NRS_LAUNCH_CHECK("dataset_rays_kernel launch");
+	return NRS_OK;
+}
+int launch_dataset_rays_ex(const DatasetRaysArgs& a, void* stream) {
+	if (a.n_rays == 0) return NRS_OK;
+	hipLaunchKernelGGL(dataset_rays_kernel<true>, dim3((a.n_rays + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+	NRS_LAUNCH_CHECK("dataset_rays_kernel<ex> launch");
+	return NRS_OK;
+}
+
+// ---- the error map: deposits (tn:1861-1886) -----------------------------------------------------------------------------------------------------------
+// One deposit (include/nrs.h, deviation 1): skipped unless v > 0 (NaN too), clamped to 1024, scaled by 2^32 (exact), truncated; the add returns nothing.
+__device__ __forceinline__ uint64_t error_map_quantise(float v) { return v > 0.0f ? (uint64_t)(fminf(v, 1024.0f) * 4294967296.0f) : 0ull; }
+__device__ __forceinline__ void error_map_deposit(uint64_t* cell, float v) {
+	const uint64_t q = error_map_quantise(v);
+	if (q) (void)__hip_atomic_fetch_add(cell, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__global__ __launch_bounds__(256) void error_map_accumulate_kernel(const ErrorMapAccumulateArgs a) {
+	const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+	if (s >= min(*a.ray_counter, a.n_rays)) return;
+	const uint32_t i = a.ray_indices[s];
+	if (i >= a.n_rays) return;
+	const float loss = a.loss[s];
+	const float p = a.pdf ? a.pdf[i] : 1.0f;
+	if (a.loss_weighted) a.loss_weighted[s] = loss / p; // tn:1848 (may be a.loss itself: this thread's own slot, read above)
+	const uint32_t img = a.pixels[2 * (size_t)i];
+	if (img >= a.n_images) return;
+	const float e = (loss * (float)a.n_rays) / p; // loss_output is mean_loss / n_rays, tn:1858
+	const float2 xy = reinterpret_cast<const float2*>(a.xy)[i];
+	const float rx = (float)(int)a.res_x, ry = (float)(int)a.res_y;
+	const float px = fminf(fmaxf(xy.x * rx - 0.5f, 0.0f), rx - (1.0f + 1e-4f)), py = fminf(fmaxf(xy.y * ry - 0.5f, 0.0f), ry - (1.0f + 1e-4f));
+	const int ix = (int)px, iy = (int)py;
+	const float wx = px - (float)ix, wy = py - (float)iy;
+	// res >= 2 and the clamp of pos put the cell into [0, res - 2] already; the clamp below acts for a NaN in xy alone (include/nrs.h, deviation 3)
+	const uint32_t cx = (uint32_t)max(min(ix, (int)a.res_x - 2), 0), cy = (uint32_t)max(min(iy, (int)a.res_y - 2), 0);
+	uint64_t* c = a.cells + ((size_t)img * a.res_y + cy) * a.res_x + cx;
+	error_map_deposit(c, (1 - wx) * (1 - wy) * e);
+	error_map_deposit(c + 1, wx * (1 - wy) * e);
+	error_map_deposit(c + a.res_x, (1 - wx) * wy * e);
+	error_map_deposit(c + a.res_x + 1, wx * wy * e);
+}
+int launch_error_map_accumulate(const ErrorMapAccumulateArgs& a, void* stream) {
+	if (a.n_rays == 0) return NRS_OK;
+	hipLaunchKernelGGL(error_map_accumulate_kernel, dim3((a.n_rays + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+	NRS_LAUNCH_CHECK("error_map_accumulate_kernel launch");
+	return NRS_OK;
+}
+
+// ---- the error map: CDFs (construct_cdf_2d tn:2620, construct_cdf_1d tn:2650, the host loop of train_nerf tn:3811-3822) ------------------------------------
+// One running sum per row, and the serial association of that sum is the definition -- so the chain is one lane's; what is parallel is everything around it.  The rows
+// of all three stages are contiguous (row r starts at r * width), so a wave takes 64 consecutive rows, one per lane, and walks them in tiles of 16 columns: the 64
+// lanes load the tile with 16 lanes to a row's segment (64 or 128 contiguous bytes each), every lane then walks ITS row's 16 entries out of LDS (17 words to a row:
+// no bank is hit twice) and leaves the running sums there, and the 64 lanes store the tile as they loaded it.  The chain never waits for global memory.  With the
+// totals known the block normalises its rows in one coalesced pass.
+//   MODE 0: src = the cells [n_images * res_y rows][res_x]; the entry is (float)cell * 2^-32 + 1e-10f; total_out = cdf_y (unnormalised)
+//   MODE 1: src = cdf = cdf_y [n_images rows][res_y], in place; total_out = the pictures' totals
+//   MODE 2: src = the pictures' totals [1 row][n_images]; MIN_PMF = 0.1 in place of MIN_PDF = 0.01, and pmf_out
+constexpr uint32_t kCdfTile = 16;
+template <int MODE>
+__global__ __launch_bounds__(64) void error_map_cdf_kernel(uint32_t n_rows, uint32_t width, const void* src, float* cdf, float* total_out, float* pmf_out) {
+	__shared__ float tile[64][kCdfTile + 1];
+	__shared__ float norm[64];
+	const uint32_t lane = threadIdx.x, row0 = blockIdx.x * 64u, rows = min(64u, n_rows - row0);
+	float cum = 0.0f;
+	for (uint32_t c0 = 0; c0 < width; c0 += kCdfTile) {
+		const uint32_t cw = min(kCdfTile, width - c0);
+		#pragma unroll
+		for (uint32_t k = 0; k < kCdfTile; ++k) {
+			const uint32_t e = k * 64u + lane, r = e / kCdfTile, x = e % kCdfTile;
+			if (r < rows && x < cw) {
+				const size_t at = (size_t)(row0 + r) * width + c0 + x;
+				tile[r][x] = MODE == 0 ? (float)((const uint64_t*)src)[at] * 0x1p-32f + 1e-10f : ((const float*)src)[at];
+			}
+		}
+		__syncthreads();
+		if (lane < rows)
+			for (uint32_t x = 0; x < cw; ++x) {
+				cum += tile[lane][x];
+				tile[lane][x] = cum;
+			}
+		__syncthreads();
+		#pragma unroll
+		for (uint32_t k = 0; k < kCdfTile; ++k) {
+			const uint32_t e = k * 64u + lane, r = e / kCdfTile, x = e % kCdfTile;
+			if (r < rows && x < cw) cdf[(size_t)(row0 + r) * width + c0 + x] = tile[r][x];
+		}
+		__syncthreads();
+	}
+	if (lane < rows) {
+		if (MODE != 2) total_out[row0 + lane] = cum;
+		norm[lane] = 1.0f / cum; // __frcp_rn
+	}
+	__syncthreads();
+	constexpr float kMin = MODE == 2 ? 0.1f : 0.01f; // MIN_PMF : MIN_PDF
+	for (uint32_t e = lane; e < rows * width; e += 64u) { // (rows * width <= 64 * 1024, or one row of n_images)
+		const uint32_t r = e / width, x = e % width;
+		const size_t at = (size_t)row0 * width + e;
+		cdf[at] = (1.0f - kMin) * cdf[at] * norm[r] + kMin * (float)(x + 1) / (float)width;
+		if (MODE == 2) pmf_out[at] = (1.0f - kMin) * ((const float*)src)[at] * norm[r] + kMin / (float)width;
+	}
+}
+int launch_error_map_cdfs(uint32_t n_images, uint32_t res_y, uint32_t res_x, const uint64_t* d_cells, float* d_cdf_x_cond_y, float* d_cdf_y, float* d_img_total,
+                          float* d_cdf_img, float* d_pmf_img, void* stream) {
+	hipStream_t s = (hipStream_t)stream;
+	const uint32_t n_rows = n_images * res_y;
+	hipLaunchKernelGGL(error_map_cdf_kernel<0>, dim3((n_rows + 63) / 64), dim3(64), 0, s, n_rows, res_x, (const void*)d_cells, d_cdf_x_cond_y, d_cdf_y, (float*)nullptr);
+	NRS_LAUNCH_CHECK("error_map_cdf_kernel<0> launch");
+	hipLaunchKernelGGL(error_map_cdf_kernel<1>, dim3((n_images + 63) / 64), dim3(64), 0, s, n_images, res_y, (const void*)d_cdf_y, d_cdf_y, d_img_total, (float*)nullptr);
+	NRS_LAUNCH_CHECK("error_map_cdf_kernel<1> launch");
+	hipLaunchKernelGGL(error_map_cdf_kernel<2>, dim3(1), dim3(64), 0, s, 1u, n_images, (const void*)d_img_total, d_cdf_img, (float*)nullptr, d_pmf_img);
+	NRS_LAUNCH_CHECK("error_map_cdf_kernel<2> launch");
 	return NRS_OK;
 }
 

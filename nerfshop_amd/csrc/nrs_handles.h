@@ -221,6 +221,12 @@ struct nrs_dataset {
 	std::vector<uint8_t> image_set, camera_set;
 	uint32_t n_images_set = 0, n_cameras_set = 0;
 	bool cameras_dirty = false;
+	// the training error map (include/nrs.h, "the training error map"): 64-bit fixed-point cells, and the CDFs of the last build with their own resolution
+	nrs::DeviceBuffer<uint64_t> d_error_map;   // [n_images][map_res_y][map_res_x]
+	uint32_t map_res_x = 0, map_res_y = 0;     // 0: no map yet
+	nrs::DeviceBuffer<float> d_cdf_x_cond_y, d_cdf_y, d_cdf_img, d_pmf_img, d_img_total; // d_img_total: the pictures' unnormalised totals (construct_cdf_1d's cdf_img)
+	uint32_t cdf_res_x = 0, cdf_res_y = 0;
+	bool cdf_valid = false;
 };
 
 // The optimiser's state (nrs_api_optimizer.cpp, nrs_optimizer.hip): every array in the blob's order, n elements.

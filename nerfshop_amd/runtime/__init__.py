@@ -15,7 +15,7 @@ One module per subsystem of the library (the nrs_api_*.cpp it fronts); this file
 from .._abi import NrsError, RenderParams, RenderStats, check
 from ._base import _require_cuda, _stream_handle
 from .context import Context
-from .dataset import Dataset
+from .dataset import Dataset, error_map_cdfs_host, error_map_resolution
 from .edits import AffineDuplication, CageDeformation
 from .mesh import Mesh, mesh_from_density
 from .network import DEFAULT_CELL_CACHE_BYTES, NerfNetwork, rng_advance, rng_seed

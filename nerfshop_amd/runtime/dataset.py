@@ -9,6 +9,24 @@ from .._abi import NrsError, check
 from ._base import Handle, _device, _ptr, _stream_handle
 
 
+def error_map_resolution(steps_between, rays_per_batch, n_images, image_resolution):
+    """nrs_error_map_resolution: one axis of the error map's resolution as train_nerf picks it, clamped into [2, min(image_resolution, 1024)].  Host only."""
+    return int(_abi.load().nrs_error_map_resolution(int(steps_between) & 0xffffffff, int(rays_per_batch) & 0xffffffff, int(n_images), int(image_resolution)))
+
+
+def error_map_cdfs_host(data):
+    """nrs_error_map_cdfs_host: (cdf_x_cond_y [n, res_y, res_x], cdf_y [n, res_y], cdf_img [n], pmf_img [n]) from a float32 error map [n, res_y, res_x], with the
+    expressions and the order of Dataset.error_map_build_cdfs.  Host only."""
+    a = np.ascontiguousarray(data, dtype=np.float32)
+    if a.ndim != 3:
+        raise NrsError("error_map_cdfs_host: data must be [n_images, res_y, res_x]")
+    n, res_y, res_x = a.shape
+    cx, cy = np.zeros((n, res_y, res_x), np.float32), np.zeros((n, res_y), np.float32)
+    ci, pi = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    check(_abi.load().nrs_error_map_cdfs_host(n, res_y, res_x, a.ctypes.data, cx.ctypes.data, cy.ctypes.data, ci.ctypes.data, pi.ctypes.data))
+    return cx, cy, ci, pi
+
+
 class Dataset(Handle):
     """Posed images on the device (nrs_dataset_*): n_images images of one resolution as fp16 RGBA, linear and premultiplied (NerfDataset::images_data), and one camera
     record per image.  rays() is the first half of generate_training_samples_nerf: the pixels a training step looks at, their rays and the colours they should have."""
@@ -51,14 +69,16 @@ class Dataset(Handle):
             raise NrsError("Dataset.set_camera: camera must be a TrainingCamera")
         check(self.lib.nrs_dataset_set_camera(self.h, int(index), C.byref(camera)))
 
-    def rays(self, n_rays, n_rays_total, rng, snap=True, random_bg=True, stream=None, want_pixels=True):
+    def rays(self, n_rays, n_rays_total, rng, snap=True, random_bg=True, stream=None, want_pixels=True, by_error=None):
         """The rays of one training step (nrs_dataset_rays).  rng = (state, inc) of the step's generator (nrs_rng_seed / nrs_rng_advance); n_rays_total: the rays of
         the steps before.  snap and random_bg default to the reference's Testbed initialisers, snap_to_pixel_centers = true and random_bg_color = true
         (include/neural-graphics-primitives/testbed.h:584 and :581).  Returns CUDA tensors (rays [n, 6] f32, jitter [n] f32, target_rgba [n, 4] f32,
-        background [n, 3] f32 sRGB-encoded or None without random_bg, pixels [n, 2] int32 (image, x + y * width) or None)."""
+        background [n, 3] f32 sRGB-encoded or None without random_bg, pixels [n, 2] int32 (image, x + y * width) or None).
+        by_error=(images, pixels) goes through nrs_dataset_rays_ex instead -- images drawn from cdf_img, pixels from cdf_y / cdf_x_cond_y, each behind its switch;
+        (False, False) draws what the plain call draws -- and returns two more tensors: xy [n, 2] f32 (after snapping) and pdf [n] f32."""
         n = int(n_rays)
         dev = _device(self.ctx)
-        p = _abi.DatasetRaysParams()
+        p = _abi.DatasetRaysParams() if by_error is None else _abi.DatasetRaysExParams()
         p.n_rays_total, p.rng_state, p.rng_inc = int(n_rays_total) & 0xffffffff, int(rng[0]), int(rng[1])
         p.snap_to_pixel_centers, p.random_bg_color = int(bool(snap)), int(bool(random_bg))
         rays = torch.empty((n, 6), dtype=torch.float32, device=dev)
@@ -66,9 +86,60 @@ class Dataset(Handle):
         target = torch.empty((n, 4), dtype=torch.float32, device=dev)
         background = torch.empty((n, 3), dtype=torch.float32, device=dev) if random_bg else None
         pixels = torch.empty((n, 2), dtype=torch.int32, device=dev) if want_pixels else None
-        check(self.lib.nrs_dataset_rays(self.h, _stream_handle(stream), C.byref(p), n, rays.data_ptr(), jitter.data_ptr(), target.data_ptr(),
-                                        _ptr(background), _ptr(pixels)))
-        return rays, jitter, target, background, pixels
+        if by_error is None:
+            check(self.lib.nrs_dataset_rays(self.h, _stream_handle(stream), C.byref(p), n, rays.data_ptr(), jitter.data_ptr(), target.data_ptr(),
+                                            _ptr(background), _ptr(pixels)))
+            return rays, jitter, target, background, pixels
+        p.sample_images_by_error, p.sample_pixels_by_error = int(bool(by_error[0])), int(bool(by_error[1]))
+        xy = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        pdf = torch.empty(n, dtype=torch.float32, device=dev)
+        check(self.lib.nrs_dataset_rays_ex(self.h, _stream_handle(stream), C.byref(p), n, rays.data_ptr(), jitter.data_ptr(), target.data_ptr(),
+                                           _ptr(background), _ptr(pixels), xy.data_ptr(), pdf.data_ptr()))
+        return rays, jitter, target, background, pixels, xy, pdf
+
+    # ---- the training error map (include/nrs.h): cells in 64-bit fixed point, three CDFs, rays(by_error=...) ------------------------------------------------------
+    def error_map_resolution(self, steps_between, rays_per_batch):
+        """(res_x, res_y) the reference picks for this many steps of this many rays (nrs_error_map_resolution), clamped into what error_map_reset accepts."""
+        return tuple(int(self.lib.nrs_error_map_resolution(int(steps_between), int(rays_per_batch), self.n_images, r)) for r in (self.width, self.height))
+
+    def error_map_reset(self, res_x, res_y, stream=None):
+        """(Re)allocate and zero the map, n_images x res_y x res_x cells.  Valid CDFs survive."""
+        check(self.lib.nrs_dataset_error_map_reset(self.h, int(res_x), int(res_y), _stream_handle(stream)))
+
+    def error_map_set(self, data):
+        """The map from a float32 array [n_images, res_y, res_x], each entry quantised as a deposit is.  Synchronous."""
+        a = np.ascontiguousarray(data, dtype=np.float32)
+        if a.ndim != 3 or a.shape[0] != self.n_images:
+            raise NrsError("Dataset.error_map_set: data must be [n_images, res_y, res_x]")
+        check(self.lib.nrs_dataset_error_map_set(self.h, a.shape[2], a.shape[1], a.ctypes.data))
+
+    def error_map_get(self, what=_abi.ERROR_MAP_FLOAT):
+        """The map (_abi.ERROR_MAP_FLOAT: float32, ERROR_MAP_CELLS: the uint64 cells) or one of the CDFs (ERROR_MAP_CDF_X_COND_Y / _CDF_Y / _CDF_IMG / _PMF_IMG) as a
+        flat host array; synchronous.  The map is [n_images, res_y, res_x] at the map's resolution, the CDFs at theirs."""
+        count = C.c_size_t(0)
+        check(self.lib.nrs_dataset_error_map_get(self.h, int(what), None, C.byref(count)))
+        out = np.empty(count.value, dtype=np.uint64 if what == _abi.ERROR_MAP_CELLS else np.float32)
+        check(self.lib.nrs_dataset_error_map_get(self.h, int(what), out.ctypes.data, None))
+        return out
+
+    def error_map_accumulate(self, n_rays, ray_counter, ray_indices, loss, xy, pixels, pdf=None, loss_weighted=None, stream=None):
+        """Deposit the losses of one step (nrs_dataset_error_map_accumulate): ray_counter [>= 1] and ray_indices [n] int32 from training_samples, loss [n] f32 by slot
+        from ray_loss, xy [n, 2] f32 / pixels [n, 2] int32 / pdf [n] f32 or None by ray from rays(by_error=...).  loss_weighted: None, or a [n] f32 tensor (loss itself
+        is allowed) that receives loss / pdf.  CUDA tensors; nothing waits for the device."""
+        n = int(n_rays)
+        for t, dtype, numel, name in ((ray_counter, torch.int32, 1, "ray_counter"), (ray_indices, torch.int32, n, "ray_indices"), (loss, torch.float32, n, "loss"),
+                                      (xy, torch.float32, 2 * n, "xy"), (pixels, torch.int32, 2 * n, "pixels"), (pdf, torch.float32, n, "pdf"),
+                                      (loss_weighted, torch.float32, n, "loss_weighted")):
+            if t is None and name in ("pdf", "loss_weighted"):
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < numel:
+                raise NrsError(f"Dataset.error_map_accumulate: {name} must be a contiguous CUDA tensor of {dtype} with at least {numel} elements")
+        check(self.lib.nrs_dataset_error_map_accumulate(self.h, _stream_handle(stream), n, ray_counter.data_ptr(), ray_indices.data_ptr(), loss.data_ptr(),
+                                                        xy.data_ptr(), pixels.data_ptr(), _ptr(pdf), _ptr(loss_weighted)))
+
+    def error_map_build_cdfs(self, stream=None):
+        """cdf_x_cond_y, cdf_y, cdf_img and pmf_img from the map, on the device (nrs_dataset_error_map_build_cdfs); they take the map's resolution and become valid."""
+        check(self.lib.nrs_dataset_error_map_build_cdfs(self.h, _stream_handle(stream)))
 
     def mark_untrained(self, network, clear_visible=True, stream=None):
         """mark_untrained_density_grid on the network's density grid: cells no camera sees become -1 (and stay so through every later grid update), seen cells 0 where

@@ -24,6 +24,24 @@ from ._abi import NrsError
 from .torch_module import LOSS_SCALE, initial_params
 
 
+class ErrorMapSchedule:
+    """train_nerf's error map for Trainer.step_dataset / fit, with the reference's cadence (src/testbed_nerf.cu:3724-3830): every step's ray losses are deposited
+    into the dataset's error map; after steps_between steps (128, the reference's n_steps_between_error_map_updates) the map becomes CDFs and steps_between
+    becomes (uint32)(steps_between * growth) (1.5); the step after a build starts a fresh map.  sample_images / sample_pixels
+    (sample_image_proportional_to_error / sample_focal_plane_proportional_to_error, both off in the reference's Testbed) draw the next steps' images / pixels
+    from those CDFs once a build has happened.  The object carries the state: steps_between (current), steps_since (the last build), builds, build_steps (the
+    trainer's training_step after each build), resolution (of the current map); keep_last=True also keeps clones of each step's (ray_counter, ray_indices, loss) as
+    last_loss beside last_rays = (xy, pixels, pdf), for inspection."""
+
+    def __init__(self, steps_between=128, growth=1.5, sample_images=False, sample_pixels=False, keep_last=False):
+        if int(steps_between) < 1 or not float(growth) >= 1.0:
+            raise NrsError("ErrorMapSchedule: steps_between must be at least 1 and growth at least 1")
+        self.steps_between, self.growth = int(steps_between), float(growth)
+        self.sample_images, self.sample_pixels, self.keep_last = bool(sample_images), bool(sample_pixels), bool(keep_last)
+        self.steps_since, self.builds, self.build_steps = 0, 0, []
+        self.resolution, self.last_rays, self.last_loss = None, None, None
+
+
 class Trainer:
     """A NerfNetwork without cell records, an Optimizer bound to it, one persistent gradient buffer (zero between steps: the optimiser clears what it reads) and
     base.json's learning-rate schedule.
@@ -83,6 +101,10 @@ class Trainer:
     def step(self, rays, target_rgba, jitter=None, background=None):
         """One training step on rays [n, 6] f32 with the colours they should have, target_rgba [n, 4] f32 (linear, premultiplied); jitter [n] in [0, 1) or None,
         background [n, 3] (sRGB-encoded) or None for loss_params.background.  Returns the mean loss as a 0-d CUDA tensor.  Nothing waits for the device."""
+        return self._step(rays, target_rgba, jitter, background, None)
+
+    def _step(self, rays, target_rgba, jitter, background, after_loss):
+        """step(); after_loss(ray_counter, ray_indices, loss), if given, runs between the ray loss and the backward pass and may rewrite the per-slot losses in place."""
         net = self.network
         n_rays = int(rays.shape[0])
         if tuple(target_rgba.shape) != (n_rays, 4):
@@ -97,32 +119,63 @@ class Trainer:
             self._loss_bufs = net.ray_loss_buffers(n_rays, self.max_samples, device=rays.device)
         _, coords_out, dl, loss, _ = net.ray_loss(None, self.loss_params, numsteps, coords, self._out16, target, background=bg, ray_counter=counters[:1],
                                                   out=self._loss_bufs)
+        if after_loss is not None:
+            after_loss(counters[:1], ray_indices, loss)
         net.backward(None, coords_out, dl, self.grad, None, accumulate=True)
         self.optimizer.step(self.grad, loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate(), zero_grad=True)
         self.training_step += 1
         return loss.sum()
 
-    def step_dataset(self, dataset, n_rays=4096, snap=True, random_bg=True):
+    def step_dataset(self, dataset, n_rays=4096, snap=True, random_bg=True, error_map=None):
         """One training step on n_rays pixels of a runtime.Dataset: dataset.rays (image and pixel selection, the pixel's camera, lens distortion; the target colour and
         the random background the loss composites behind it) -> step().  The generator is the trainer's m_rng (the one update_density_grid draws from), advanced once per
         step by NRS_RNG_STEP_DELTA as the reference advances it (src/testbed_nerf.cu:4435); n_rays_total counts the rays of the steps before.  snap and random_bg
-        default to the reference's Testbed initialisers (include/neural-graphics-primitives/testbed.h:584 and :581).  Like step, nothing waits for the device."""
+        default to the reference's Testbed initialisers (include/neural-graphics-primitives/testbed.h:584 and :581).  Like step, nothing waits for the device.
+        error_map: an ErrorMapSchedule runs train_nerf's error map around the step (src/testbed_nerf.cu:3724-3831): the map is reset, at the resolution recomputed
+        from the schedule, when no step has passed since the last build; the rays are drawn from the CDFs once there are valid ones and the schedule asks for it; every
+        ray's loss is deposited after the ray loss (the returned loss is then the sum of loss / pdf, the loss the reference reports); and once steps_between steps have
+        passed the CDFs are rebuilt and steps_between grows.  All on the device; with both sampling switches off the step computes what it computes without a schedule."""
         u = self._grid_update
-        rays, jitter, target, background, _ = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg, want_pixels=False)
-        loss = self.step(rays, target, jitter=jitter, background=background)
+        if error_map is None:
+            rays, jitter, target, background, _ = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg, want_pixels=False)
+            loss = self.step(rays, target, jitter=jitter, background=background)
+        else:
+            em = error_map
+            if em.steps_since == 0:
+                em.resolution = dataset.error_map_resolution(em.steps_between, n_rays)
+                dataset.error_map_reset(*em.resolution)
+            by_error = (em.sample_images and em.builds > 0, em.sample_pixels and em.builds > 0)  # (the reference hands the CDFs over only once is_cdf_valid)
+            rays, jitter, target, background, pixels, xy, pdf = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg,
+                                                                             by_error=by_error)
+            em.last_rays = (xy, pixels, pdf)
+
+            def accumulate(ray_counter, ray_indices, loss):
+                em.last_loss = (ray_counter.clone(), ray_indices.clone(), loss.clone()) if em.keep_last else None
+                dataset.error_map_accumulate(n_rays, ray_counter, ray_indices, loss, xy, pixels, pdf=pdf, loss_weighted=loss)
+            loss = self._step(rays, target, jitter, background, accumulate)
+            em.steps_since += 1
+            if em.steps_since >= em.steps_between:
+                dataset.error_map_build_cdfs()
+                em.builds += 1
+                em.build_steps.append(self.training_step)
+                em.steps_since = 0
+                em.steps_between = int(np.float32(em.steps_between) * np.float32(em.growth)) & 0xffffffff
         self.n_rays_total = (self.n_rays_total + int(n_rays)) & 0xffffffff
         u.rng_state = runtime.rng_advance(u.rng_state, u.rng_inc)
         return loss
 
-    def fit(self, dataset, n_steps, n_rays=4096, grid_every=16, snap=True, random_bg=True):
+    def fit(self, dataset, n_steps, n_rays=4096, grid_every=16, snap=True, random_bg=True, error_map=None):
         """Train on a runtime.Dataset for n_steps steps.  At training step 0 the cells no camera sees are marked untrained (mark_untrained_density_grid with
         clear_visible_voxels, src/testbed_nerf.cu:3452-3465) in front of the first grid update; the grid is updated every grid_every steps (the reference's cadence: 16).
-        Returns the losses, 0-d CUDA tensors."""
+        error_map: None, or an ErrorMapSchedule (step_dataset).  Returns the losses, 0-d CUDA tensors."""
         losses = []
         for _ in range(int(n_steps)):
             if self.training_step == 0:
                 dataset.mark_untrained(self.network, clear_visible=True)
             if self.training_step % int(grid_every) == 0:
                 self.update_density_grid()
-            losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg))
+            if error_map is None:
+                losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg))
+            else:
+                losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg, error_map=error_map))
         return losses
