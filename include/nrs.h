@@ -1141,6 +1141,72 @@ int      nrs_error_map_cdfs_host(uint32_t n_images, uint32_t res_y, uint32_t res
 int      nrs_dataset_rays_ex(nrs_dataset* ds, void* stream, const nrs_dataset_rays_ex_params* params, uint32_t n_rays, float* d_rays, float* d_jitter, float* d_target_rgba,
                              float* d_background, uint32_t* d_pixels, float* d_xy, float* d_pdf);
 
+/* ---- image metrics: PSNR and SSIM of a rendered view against a held-out image, on the device --------------------------------------------------------- */
+/* What scripts/run.py --test_transforms prints (:215-302; linear_to_srgb / srgb_to_linear scripts/common.py:139-145, luminance and SSIM :186-207, compute_error_img
+ * :227-247, compute_error :264-269), as one stencil-and-reduce kernel over the accumulate buffer and the reference image where it lies.  New surface, detected by
+ * symbol (nrs_image_metrics).  Not here: MAE, MAPE, SMAPE, MRSE, FLIP, per-frame fovs of a test file, EXR references.
+ *
+ * THE DEFINITION.  I: the rendered image, f32x4 per pixel, linear, rows top to bottom (the accumulate buffer after its folds); only rgb is read.  Rf: the reference,
+ * NRS_IMAGE_RGBA16F_LINEAR (a dataset image as nrs_dataset stores it: linear, premultiplied) or NRS_IMAGE_RGBA32F_LINEAR of the same meaning.  Per pixel, float32,
+ * IEEE division, no contraction, products and sums in the written order; powf is the platform's (the device library's, glibc's in the host twin):
+ *  1. the reference.  color_space == NRS_COLOR_SRGB (NeRF's blend in sRGB space, run.py:264-270), with a = Rf.w:  c = a != 0 ? Rf.rgb / a : 0;
+ *     c = linear_to_srgb(c) * a + (1.0f - a) * background_color.rgb;  ref = srgb_to_linear(c).  Any other colour space: ref = Rf.rgb.  (run.py sets the background
+ *     (0, 0, 0, 1).)  linear_to_srgb(l) = l > 0.0031308f ? 1.055f * powf(l, 0.41666667f) - 0.055f : 12.92f * l  and  srgb_to_linear(s) = s > 0.04045f ?
+ *     powf((s + 0.055f) / 1.055f, 2.4f) : s / 12.92f -- run.py's curves, NOT nrs_tonemap's (`<`, 0.41666).
+ *  2. A = clip(linear_to_srgb(I.rgb)) and R = clip(linear_to_srgb(ref)) with clip(x) = x < 0 ? 0 : (x > 1 ? 1 : x); then a non-finite A (a NaN: the clip passes it)
+ *     counts as 0 (compute_error_img :228-229).
+ *  3. squared error: e_c = (A_c - R_c) * (A_c - R_c) for c = r, g, b; a non-finite e_c (a NaN in the reference) counts as 0 (compute_error :266).
+ *  4. SSIM.  La = (0.2126f * powf(A.r, g) + 0.7152f * powf(A.g, g)) + 0.0722f * powf(A.b, g) with g = 0.4545454545f, Lb likewise from R: yes, on top of the sRGB
+ *     encoding -- the reference's quirk, kept.  blur is the separable 5-tap kernel k = (0.120078f, 0.233881f, 0.292082f, 0.233881f, 0.120078f), along y first, then
+ *     along x, one axis being v[0] + (k[1] * ((v[-1] - v[0]) + (v[1] - v[0])) + k[0] * ((v[-2] - v[0]) + (v[2] - v[0]))): the centre's weight is 1 - 2 k[1] - 2 k[0]
+ *     = 0.292082 exactly, so this is the 5-tap sum with weights that add up to one, and a constant neighbourhood comes back bit for bit.  The boundary is scipy's `reflect`: index i of an axis of length n
+ *     reads j = i mod 2n (the non-negative remainder), j < n ? j : 2n - 1 - j -- for n = 1 and 2 as well.  mA = blur(La), mB = blur(Lb), sA = blur(La * La) - mA * mA,
+ *     sB = blur(Lb * Lb) - mB * mB, sAB = blur(La * Lb) - mA * mB,
+ *       ssim = ((2.0f * mA * mB + 1e-4f) / ((mA * mA + mB * mB) + 1e-4f)) * ((2.0f * sAB + 9e-4f) / ((sA + sB) + 9e-4f)),  non-finite -> 0.
+ *  5. the sums, exact and order-free (the error map's convention): every e_c and every pixel's ssim is multiplied by 2^32 (exact) and rounded to the nearest integer
+ *     (ties to even; ssim is signed); these are summed as 64-bit integers, on the device with ONE no-return 64-bit integer atomic per sum and workgroup.  A view's
+ *     record is bit-identical from run to run and does not depend on the tile shape or the order of arrival.  8192^2 pixels x 3 x 2^32 < 2^63.
+ *  6. the record: mse = sum_sq_err * 2^-32 / (3 n) and ssim = sum_ssim * 2^-32 / n, each evaluated in double and rounded to float once; psnr = -10 * log10(mse) from
+ *     the rounded mse, in double, rounded once; +inf for mse == 0.
+ * A masked dataset pixel (-1, -1, -1, -1) gets NO special case: it is computed as its stored values say (in NRS_COLOR_LINEAR its R is 0; a test set has no masks).
+ *
+ * nrs_image_metrics: three things on `stream` -- a 16-byte clear of the two sums, the kernel, a one-thread kernel that fills n_pixels, mse, ssim, psnr -- nothing waits
+ *   for the device, nothing is allocated.  d_image 16-byte aligned, d_reference 8-byte (fp16) / 16-byte (f32) aligned, d_result 8-byte aligned.  d_ssim_map and
+ *   d_sq_err_map (either may be NULL): float [height x width], the pixel's ssim and (e_r + e_g + e_b) / 3.0f -- run.py's metric maps.
+ * nrs_dataset_image_metrics: the reference is image `index` of the dataset, read in place; width and height are the dataset's, the context is the dataset's.
+ *   NRS_ERR_STATE while that image has never been set.
+ * nrs_image_metrics_host: the CPU twin on host pointers -- the same float32 operations in the same order, the same fixed-point sums, glibc's powf.  No context, no GPU.
+ * nrs_image_metrics_summary_host: run.py's totals over n records (:292-301), in double: psnr_mean, psnr_min, psnr_max (plain minimum and maximum of the records'
+ *   psnr; run.py's starting values 1000 and 0 are not kept), ssim_mean, psnr_avgmse = -10 * log10(mean mse) (+inf for 0).
+ *
+ * Refused before any HIP call, NRS_ERR_INVALID_ARG: NULL handles, inputs or result; a zero dimension or one above NRS_IMAGE_METRICS_MAX_DIM; a struct_size other than
+ *   sizeof(nrs_image_metrics_params); a reference_format other than the two above (NRS_IMAGE_RGBA8_SRGB included); a non-finite background; a misaligned pointer; an
+ *   index past n_images; n == 0 records. */
+#define NRS_IMAGE_METRICS_MAX_DIM 8192u
+typedef struct nrs_image_metrics_params {
+	uint32_t struct_size;          /* refused unless == sizeof(nrs_image_metrics_params) */
+	uint32_t color_space;          /* nrs_color_space of the training: NRS_COLOR_SRGB blends the reference in sRGB space (step 1) */
+	float    background_color[4];  /* sRGB-encoded; run.py: (0, 0, 0, 1) */
+	uint32_t reference_format;     /* NRS_IMAGE_RGBA16F_LINEAR | NRS_IMAGE_RGBA32F_LINEAR */
+} nrs_image_metrics_params;
+typedef struct nrs_image_metrics_result {
+	int64_t  sum_sq_err;           /* sum of round(e_c * 2^32) over pixels and channels */
+	int64_t  sum_ssim;             /* sum of round(ssim * 2^32) over pixels */
+	uint32_t n_pixels;
+	float    mse, ssim, psnr;
+} nrs_image_metrics_result;
+typedef struct nrs_metrics_summary {
+	double   psnr_mean, psnr_min, psnr_max, ssim_mean, psnr_avgmse;
+	uint32_t n_views, reserved;
+} nrs_metrics_summary;
+int nrs_image_metrics(nrs_ctx* ctx, void* stream, uint32_t width, uint32_t height, const float* d_image, const void* d_reference, const nrs_image_metrics_params* params,
+                      nrs_image_metrics_result* d_result, float* d_ssim_map, float* d_sq_err_map);
+int nrs_dataset_image_metrics(nrs_dataset* ds, uint32_t index, void* stream, const float* d_image, const nrs_image_metrics_params* params, nrs_image_metrics_result* d_result,
+                              float* d_ssim_map, float* d_sq_err_map);
+int nrs_image_metrics_host(uint32_t width, uint32_t height, const float* h_image, const void* h_reference, const nrs_image_metrics_params* params,
+                           nrs_image_metrics_result* h_result, float* h_ssim_map, float* h_sq_err_map);
+int nrs_image_metrics_summary_host(const nrs_image_metrics_result* h_results, uint32_t n, nrs_metrics_summary* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 // streams are passed as void* (hipStream_t), errors become std::runtime_error (the reference throws from CUDA_CHECK_THROW).
 #pragma once
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -174,6 +175,13 @@ private:
 	bool m_zero_grad = true;
 };
 
+// nrs_image_metrics_params with run.py's defaults: a black, opaque background unless background_rgba is given
+inline nrs_image_metrics_params image_metrics_params(nrs_color_space color_space, const float* background_rgba, nrs_image_format reference_format) {
+	nrs_image_metrics_params p{(uint32_t)sizeof(nrs_image_metrics_params), (uint32_t)color_space, {0.0f, 0.0f, 0.0f, 1.0f}, (uint32_t)reference_format};
+	if (background_rgba) std::memcpy(p.background_color, background_rgba, sizeof(p.background_color));
+	return p;
+}
+
 // NerfDataset on the device (nerf_loader.h: images_data, xforms, metadata) with the front half of generate_training_samples_nerf.  A thin owner of the handle: images arrive
 // decoded (the loader and its file formats stay with the caller).
 class Dataset {
@@ -225,11 +233,31 @@ public:
 		                                   sample_images ? 1u : 0u, sample_pixels ? 1u : 0u};
 		check(nrs_dataset_rays_ex(m_ds, stream, &p, n_rays, d_rays, d_jitter, d_target_rgba, d_background, d_pixels, d_xy, d_pdf), "nrs_dataset_rays_ex");
 	}
+	// PSNR's squared error and SSIM of d_image (f32x4 per pixel, linear: an accumulate buffer) against image `index`, read where it lies (nrs_dataset_image_metrics):
+	// *d_result on the device, the two maps [height x width] when not null; nothing waits for the device
+	void image_metrics(uint32_t index, void* stream, const float* d_image, nrs_image_metrics_result* d_result, nrs_color_space color_space = NRS_COLOR_LINEAR,
+	                   const float* background_rgba = nullptr, float* d_ssim_map = nullptr, float* d_sq_err_map = nullptr) {
+		const nrs_image_metrics_params p = image_metrics_params(color_space, background_rgba, NRS_IMAGE_RGBA16F_LINEAR);
+		check(nrs_dataset_image_metrics(m_ds, index, stream, d_image, &p, d_result, d_ssim_map, d_sq_err_map), "nrs_dataset_image_metrics");
+	}
 	nrs_dataset* get() const { return m_ds; }
 
 private:
 	nrs_dataset* m_ds = nullptr;
 };
+
+// nrs_image_metrics on a caller's reference (d_reference: fp16 or f32 RGBA, linear, premultiplied), and run.py's totals over records that are back on the host
+inline void image_metrics(Context& ctx, void* stream, uint32_t width, uint32_t height, const float* d_image, const void* d_reference, nrs_image_format reference_format,
+                          nrs_image_metrics_result* d_result, nrs_color_space color_space = NRS_COLOR_LINEAR, const float* background_rgba = nullptr, float* d_ssim_map = nullptr,
+                          float* d_sq_err_map = nullptr) {
+	const nrs_image_metrics_params p = image_metrics_params(color_space, background_rgba, reference_format);
+	check(nrs_image_metrics(ctx.get(), stream, width, height, d_image, d_reference, &p, d_result, d_ssim_map, d_sq_err_map), "nrs_image_metrics");
+}
+inline nrs_metrics_summary metrics_summary(const nrs_image_metrics_result* h_results, uint32_t n) {
+	nrs_metrics_summary s{};
+	check(nrs_image_metrics_summary_host(h_results, n, &s), "nrs_image_metrics_summary_host");
+	return s;
+}
 
 // EditOperator (edit_operator.h:43-91): the interface NerfTracer::m_edit_operators holds (testbed.h:237) -- cage deformations and affine
 // duplications alike.  An operator owns its device tables.

@@ -238,6 +238,34 @@ ERROR_MAP_MAX_RESOLUTION = 1024  # NRS_ERROR_MAP_MAX_RESOLUTION
 
 
 IMAGE_RGBA8_SRGB, IMAGE_RGBA32F_LINEAR, IMAGE_RGBA16F_LINEAR = 0, 1, 2  # nrs_image_format
+IMAGE_METRICS_MAX_DIM = 8192  # NRS_IMAGE_METRICS_MAX_DIM
+
+
+class ImageMetricsParams(C.Structure):
+    """nrs_image_metrics_params; struct_size is filled in on construction, the background is run.py's (0, 0, 0, 1), the reference fp16."""
+    _fields_ = [("struct_size", C.c_uint32), ("color_space", C.c_uint32), ("background_color", C.c_float * 4), ("reference_format", C.c_uint32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(ImageMetricsParams)
+        if "background_color" not in kw and len(args) < 3:
+            self.background_color[:] = (0.0, 0.0, 0.0, 1.0)
+        if "reference_format" not in kw and len(args) < 4:
+            self.reference_format = IMAGE_RGBA16F_LINEAR
+
+
+class ImageMetricsResult(C.Structure):
+    """nrs_image_metrics_result: 32 bytes, METRICS_RECORD_DTYPE as a numpy record"""
+    _fields_ = [("sum_sq_err", C.c_int64), ("sum_ssim", C.c_int64), ("n_pixels", C.c_uint32), ("mse", C.c_float), ("ssim", C.c_float), ("psnr", C.c_float)]
+
+
+class MetricsSummary(C.Structure):
+    """nrs_metrics_summary"""
+    _fields_ = [("psnr_mean", C.c_double), ("psnr_min", C.c_double), ("psnr_max", C.c_double), ("ssim_mean", C.c_double), ("psnr_avgmse", C.c_double),
+                ("n_views", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+METRICS_RECORD_DTYPE = [("sum_sq_err", "<i8"), ("sum_ssim", "<i8"), ("n_pixels", "<u4"), ("mse", "<f4"), ("ssim", "<f4"), ("psnr", "<f4")]
 IMAGE_WHITE_TRANSPARENT, IMAGE_BLACK_TRANSPARENT = 1, 2  # NRS_IMAGE_WHITE_TRANSPARENT / _BLACK_TRANSPARENT
 RNG_STEP_DELTA = 1 << 32  # NRS_RNG_STEP_DELTA
 OPT_MASTER, OPT_M, OPT_V, OPT_STEPS, OPT_EMA, OPT_PARAMS_FP16 = range(6)  # nrs_optimizer_state
@@ -281,6 +309,7 @@ EXPORTS = [
     "nrs_dataset_create", "nrs_dataset_destroy", "nrs_dataset_set_image", "nrs_dataset_set_camera", "nrs_dataset_get_image", "nrs_dataset_rays", "nrs_dataset_mark_untrained", "nrs_rng_advance",
     "nrs_dataset_error_map_reset", "nrs_error_map_resolution", "nrs_dataset_error_map_set", "nrs_dataset_error_map_get", "nrs_dataset_error_map_accumulate",
     "nrs_dataset_error_map_build_cdfs", "nrs_error_map_cdfs_host", "nrs_dataset_rays_ex",
+    "nrs_image_metrics", "nrs_dataset_image_metrics", "nrs_image_metrics_host", "nrs_image_metrics_summary_host",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -410,6 +439,11 @@ def load():
         lib.nrs_dataset_error_map_build_cdfs.argtypes = [P, P]
         lib.nrs_error_map_cdfs_host.argtypes = [U32, U32, U32, P, P, P, P, P]
         lib.nrs_dataset_rays_ex.argtypes = [P, P, C.POINTER(DatasetRaysExParams), U32, P, P, P, P, P, P, P]
+    if hasattr(lib, "nrs_image_metrics"):  # image metrics (detected by symbol)
+        lib.nrs_image_metrics.argtypes = [P, P, U32, U32, P, P, C.POINTER(ImageMetricsParams), P, P, P]
+        lib.nrs_dataset_image_metrics.argtypes = [P, U32, P, P, C.POINTER(ImageMetricsParams), P, P, P]
+        lib.nrs_image_metrics_host.argtypes = [U32, U32, P, P, C.POINTER(ImageMetricsParams), P, P, P]
+        lib.nrs_image_metrics_summary_host.argtypes = [P, U32, C.POINTER(MetricsSummary)]
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

@@ -39,6 +39,7 @@ class Dataset(Handle):
         super().__init__(ctx.lib)
         self.ctx = ctx
         self.n_images, self.width, self.height = int(n_images), int(width), int(height)
+        self._cameras = {}   # index -> a copy of the TrainingCamera set_camera sent (get_camera: what Testbed.evaluate renders with)
         check(self.lib.nrs_dataset_create(ctx.h, self.n_images, self.width, self.height, C.byref(self.h)))
 
     def set_image(self, index, pixels, flags=0, mask_color=0, stream=None):
@@ -68,6 +69,7 @@ class Dataset(Handle):
         if not isinstance(camera, _abi.TrainingCamera):
             raise NrsError("Dataset.set_camera: camera must be a TrainingCamera")
         check(self.lib.nrs_dataset_set_camera(self.h, int(index), C.byref(camera)))
+        self._cameras[int(index)] = _abi.TrainingCamera.from_buffer_copy(camera)
 
     def rays(self, n_rays, n_rays_total, rng, snap=True, random_bg=True, stream=None, want_pixels=True, by_error=None):
         """The rays of one training step (nrs_dataset_rays).  rng = (state, inc) of the step's generator (nrs_rng_seed / nrs_rng_advance); n_rays_total: the rays of
@@ -140,6 +142,23 @@ class Dataset(Handle):
     def error_map_build_cdfs(self, stream=None):
         """cdf_x_cond_y, cdf_y, cdf_img and pmf_img from the map, on the device (nrs_dataset_error_map_build_cdfs); they take the map's resolution and become valid."""
         check(self.lib.nrs_dataset_error_map_build_cdfs(self.h, _stream_handle(stream)))
+
+    def image_metrics(self, index, image, color_space=0, background=(0.0, 0.0, 0.0, 1.0), want_maps=False, out=None, stream=None):
+        """nrs_dataset_image_metrics: image [height, width, 4] float32 on the device (linear: an accumulate buffer) against image `index` of the dataset, read where it
+        lies.  Returns what metrics.image_metrics returns: (record, ssim_map, sq_err_map); `out` is a row of a caller's [n, 32] uint8 CUDA tensor, so one evaluation
+        fills one tensor.  Nothing waits for the device."""
+        from . import metrics
+        h, w = metrics._check_image(image)
+        if (h, w) != (self.height, self.width):
+            raise NrsError(f"Dataset.image_metrics: image must be [{self.height}, {self.width}, 4]")
+        rec, (ssim_map, sq_map) = metrics._outputs(h, w, image.device, want_maps, out)
+        p = metrics.metrics_params(color_space, background)
+        check(self.lib.nrs_dataset_image_metrics(self.h, int(index), _stream_handle(stream), image.data_ptr(), C.byref(p), rec.data_ptr(), _ptr(ssim_map), _ptr(sq_map)))
+        return rec, ssim_map, sq_map
+
+    def get_camera(self, index):
+        """The camera set_camera stored for image `index` (a copy), or None while none has been set."""
+        return self._cameras.get(int(index))
 
     def mark_untrained(self, network, clear_visible=True, stream=None):
         """mark_untrained_density_grid on the network's density grid: cells no camera sees become -1 (and stay so through every later grid update), seen cells 0 where

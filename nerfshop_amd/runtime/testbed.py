@@ -35,9 +35,10 @@ def set_camera_extras(p, render_distortion=None, distortion_map=None, envmap=Non
 class Testbed:
     """The slice of ngp::Testbed the render path reads: network, occupancy, edit operators and the render knobs."""
 
-    def __init__(self, ctx, desc, aabb_scale=1, n_extra_dims=0):
+    def __init__(self, ctx, desc, aabb_scale=1, n_extra_dims=0, network=None):
+        """network: a NerfNetwork this testbed renders instead of making its own (Trainer.evaluate: the trainer's live network)."""
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
-        self.nerf_network = NerfNetwork(ctx, desc, n_extra_dims=n_extra_dims)
+        self.nerf_network = network if network is not None else NerfNetwork(ctx, desc, n_extra_dims=n_extra_dims)
         self.edit_operators = []          # NerfTracer::m_edit_operators, applied last-to-first
         self.enable_edits = True          # m_enable_edits
         self.snap_to_pixel_centers = True
@@ -62,6 +63,7 @@ class Testbed:
         self.fov, self.fov_axis = 50.625, 1   # fov() in degrees (set_camera_from_time sets it), m_fov_axis
         self.camera_path = []             # m_camera_path.m_keyframes: a list of _abi.CameraKeyframe
         self._windowless = None           # m_windowless_render_surface: the RenderBuffer of render_to_cpu
+        self._evaluate_surface = None     # the RenderBuffer of evaluate
         self.mesh = None                  # m_mesh: the Mesh of the last marching_cubes
 
     def add_edit_operator(self, op):
@@ -297,6 +299,55 @@ class Testbed:
             a1 = (np.float32(spp - 1) + np.float32(1.0)) / np.float32(spp) * np.float32(shutter_fraction)
             self.set_camera_from_time(float(np.float32(start_time) + (np.float32(end_time) - np.float32(start_time)) * (a0 + a1) / np.float32(2.0)))
         self.m_smoothed_camera = list(end_cam)                         # python_api.cu:167-168
+
+    def evaluate(self, network, dataset, spp=8, color_space=0, background=(0.0, 0.0, 0.0, 1.0), min_transmittance=1e-4, apply_operators=False, stream=None):
+        """The test loop of scripts/run.py --test_transforms (:215-302) over every image of a runtime.Dataset, all of it on the device: the accumulation of a
+        RenderBuffer of the dataset's resolution is reset, `spp` samples are rendered in batches of at most NRS_SPP_BATCH_MAX with that image's camera record --
+        xform_start as both camera matrices (run.py renders a still camera: set_nerf_camera_matrix), focal_length, principal_point as the screen centre, the record's
+        lens distortion, snap_to_pixel_centers on, rendering_min_transmittance = min_transmittance (run.py: 1e-4) -- and folded in the Linear colour space, and
+        dataset.image_metrics reads the accumulate buffer where it lies.  No tonemap pass runs: with run.py's black background, exposure 0 and the Identity curve the
+        tonemap leaves rgb as it is, and the metrics read rgb alone.  color_space is the colour space of the TRAINING (NRS_COLOR_SRGB: the reference image is blended
+        over `background` in sRGB space first), not of the fold.  After the last view ONE synchronisation and one copy of n x 32 bytes.  Returns (summary, records):
+        metrics.metrics_summary's dict and a numpy record array (fields of nrs_image_metrics_result), one record per image.  The testbed's own snap_to_pixel_centers,
+        rendering_min_transmittance and render_distortion are restored on exit, also on an exception."""
+        from . import metrics
+        if dataset.ctx is not self.ctx:
+            raise NrsError("Testbed.evaluate: the dataset belongs to another context")
+        spp, n = int(spp), dataset.n_images
+        if spp < 1:
+            raise ValueError("spp must be at least 1")
+        cameras = [dataset.get_camera(i) for i in range(n)]
+        if any(c is None for c in cameras):
+            raise NrsError("Testbed.evaluate: a camera has never been set (Dataset.set_camera)")
+        dev = _device(self.ctx)
+        buf = self._evaluate_surface
+        if buf is None or buf.in_resolution() != (dataset.width, dataset.height):
+            buf = self._evaluate_surface = RenderBuffer(dataset.width, dataset.height, device=dev)
+        s = torch.cuda.current_stream(dev) if stream is None else (stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream)))
+        saved = (self.snap_to_pixel_centers, self.rendering_min_transmittance, self.render_distortion)
+        try:
+            self.snap_to_pixel_centers, self.rendering_min_transmittance = True, float(min_transmittance)
+            with torch.cuda.stream(s):   # (the slabs are cleared by torch: on the stream the launches go to)
+                records = torch.empty((n, metrics.RECORD_BYTES), dtype=torch.uint8, device=dev)
+                for i, cam in enumerate(cameras):
+                    buf.set_spp(0)       # reset_accumulation
+                    self.render_distortion = (int(cam.distortion_mode), tuple(cam.distortion_params))
+                    matrix = list(cam.xform_start)
+                    done = 0
+                    while done < spp:
+                        k = min(spp - done, _abi.SPP_BATCH_MAX)
+                        frames = self.render_nerf_spp(network, buf, k, tuple(cam.focal_length), matrix, matrix, (0.0, 0.0, 0.0, 0.0), tuple(cam.principal_point),
+                                                      apply_operators, s)[0]
+                        buf.accumulate_spp(self.ctx, frames, s, _abi.COLOR_LINEAR)
+                        done += k
+                    dataset.image_metrics(i, buf.accumulate_buffer(), color_space, background, out=records[i], stream=s)
+                host = torch.empty((n, metrics.RECORD_BYTES), dtype=torch.uint8, pin_memory=True)
+                host.copy_(records, non_blocking=True)
+            s.synchronize()
+        finally:
+            self.snap_to_pixel_centers, self.rendering_min_transmittance, self.render_distortion = saved
+        recs = metrics.records_from_bytes(host.numpy().copy())
+        return metrics.metrics_summary(recs), recs
 
     def render_to_cpu_buffer(self):
         """The RenderBuffer render_to_cpu renders into (m_windowless_render_surface); None before the first call."""

@@ -74,6 +74,7 @@ class Trainer:
         self._grid_update.rng_state, self._grid_update.rng_inc = runtime.rng_seed(seed)
         self.density_grid_decay = float(density_grid_decay)
         self._grid_step = 0  # the training step of the last update_density_grid
+        self._eval_testbed, self._ema_network = None, None  # evaluate(): made on first use
         if density_grid is not None:
             self.network.set_density_grid(np.ascontiguousarray(density_grid, dtype=np.float32))
         else:
@@ -163,6 +164,28 @@ class Trainer:
         self.n_rays_total = (self.n_rays_total + int(n_rays)) & 0xffffffff
         u.rng_state = runtime.rng_advance(u.rng_state, u.rng_inc)
         return loss
+
+    def evaluate(self, dataset, ema=False, **kw):
+        """PSNR and SSIM of the network on a runtime.Dataset of held-out views (runtime.Testbed.evaluate: run.py's test loop, on the device; **kw goes there: spp,
+        color_space, background, min_transmittance, stream).  The views are rendered with the trainer's live parameters, or with ema=True by a second NerfNetwork
+        loaded from optimizer.export_fp16(OPT_EXPORT_EMA) with a copy of the live network's density grid as it is now.  Returns (summary, records).  Training state --
+        parameters, optimiser, generator, counters -- is untouched: the next step computes what it computes without the evaluation.
+        ema=True WAITS FOR THE DEVICE before it renders, which the live evaluation does not: the library takes a density grid from the host only, so the grid makes a
+        round trip (10 M floats down and up, and the second network's bitfield is rebuilt), on every call -- the grid may have changed since the last one.  The export
+        and the two uploads run on the current stream, which is drained before the first view is rendered, so a `stream` in **kw sees them complete.  With the live
+        parameters a `stream` other than the current one is the caller's to order behind the training steps, as everywhere in this harness."""
+        if self._eval_testbed is None:
+            self._eval_testbed = runtime.Testbed(self.ctx, self.desc, network=self.network)
+            self._eval_testbed.cone_angle_constant = self.cone_angle_constant
+        net = self.network
+        if ema:
+            if self._ema_network is None:
+                self._ema_network = runtime.NerfNetwork(self.ctx, self.desc, cell_cache_bytes=0)
+            net = self._ema_network
+            net.set_params_device(self.optimizer.export_fp16(_abi.OPT_EXPORT_EMA))
+            net.set_density_grid(self.network.get_density_grid())
+            torch.cuda.current_stream(f"cuda:{self.ctx.device}").synchronize()
+        return self._eval_testbed.evaluate(net, dataset, **kw)
 
     def fit(self, dataset, n_steps, n_rays=4096, grid_every=16, snap=True, random_bg=True, error_map=None):
         """Train on a runtime.Dataset for n_steps steps.  At training step 0 the cells no camera sees are marked untrained (mark_untrained_density_grid with
