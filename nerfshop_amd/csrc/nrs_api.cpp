@@ -1,6 +1,7 @@
 // nrs_api.cpp -- C++ host code behind the C-ABI of include/nrs.h: the error message, the ABI version, the context.  (Model, operators, render call, display: nrs_api_*.cpp.)
 // Plain C++17 + the HIP runtime API; no torch, no third-party dependencies.
 #include "nrs_host.h"
+#include "nrs_render.h"
 
 #include <cmath>
 #include <cstdio>

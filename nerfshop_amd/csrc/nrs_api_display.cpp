@@ -1,5 +1,6 @@
 // nrs_api_display.cpp -- after the render call: accumulate, tonemap, de-tile.
 #include "nrs_host.h"
+#include "nrs_display.h"
 
 #include <cmath>
 #include <cstdio>

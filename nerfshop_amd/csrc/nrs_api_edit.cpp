@@ -1,5 +1,7 @@
 // nrs_api_edit.cpp -- the edit operators: cage (tet LUT, fine look-up table, per-move updates, membrane terms) and affine duplication.
 #include "nrs_host.h"
+#include "nrs_tables.h"
+#include "nrs_cage.h"
 
 #include <cmath>
 #include <cstdio>
@@ -296,7 +298,7 @@ void affine_finish(const HostAffineBox& b, AffineBox& out) {
 		out.u[i] = b.rot[i] * b.scale[0];
 		out.v[i] = b.rot[3 + i] * b.scale[1];
 		out.w[i] = b.rot[6 + i] * b.scale[2];
-		// Eigen's 3-term reduction order x0 + (x1 + x2) in every small product / dot (Redux.h complete unrolling; see nrs_device.cuh)
+		// Eigen's 3-term reduction order x0 + (x1 + x2) in every small product / dot (Redux.h complete unrolling; see nrs_vec.cuh)
 		out.mn[i] = ((-0.5f * b.rot[i]) * b.scale[0] + ((-0.5f * b.rot[3 + i]) * b.scale[1] + (-0.5f * b.rot[6 + i]) * b.scale[2])) + b.center[i];
 		out.center[i] = b.center[i];
 	}

@@ -1,5 +1,8 @@
 // nrs_api_mesh.cpp -- mesh extraction: the marching-cubes case table (generated here, from a rule), the resolution helper, the mesh handle, the file writers.
 #include "nrs_handles.h"
+#include "nrs_network.h"
+#include "nrs_mesh.h"
+#include "nrs_scan.h"
 
 #include <cmath>
 #include <cstdio>

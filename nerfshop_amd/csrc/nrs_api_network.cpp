@@ -1,5 +1,7 @@
 // nrs_api_network.cpp -- the network operators: inference, density, gradients, grid evaluation, selection rays, the Poisson boundary fit, hash-grid encoding, sample traces.
 #include "nrs_host.h"
+#include "nrs_network.h"
+#include "nrs_network_backward.h"
 
 #include <cmath>
 

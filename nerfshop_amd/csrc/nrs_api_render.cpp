@@ -1,5 +1,7 @@
 // nrs_api_render.cpp -- the render call: tile geometry, argument checks, the operator table, the route request, the launch on its slot, statistics; the route probes.
 #include "nrs_host.h"
+#include "nrs_route.h"
+#include "nrs_render.h"
 
 #include <array>
 #include <cmath>
@@ -91,7 +93,7 @@ static int check_render_args(const nrs_model* m, const nrs_render_params* p, nrs
 // The development knobs of a render call, read once (dev_knob: a production process ignores them).
 struct RenderKnobs {
 	RouteKnobs route;
-	uint32_t dbg;      // RenderArgs::dbg: NRS_DEBUG | NRS_SKIP_PAIRS << 8 (bit it: level pair (2 it, 2 it + 1) is not gathered -- nrs_mlp.cuh: KIND_SKIP; measurement only)
+	uint32_t dbg;      // RenderArgs::dbg: NRS_DEBUG | NRS_SKIP_PAIRS << 8 (bit it: level pair (2 it, 2 it + 1) is not gathered -- nrs_hashgrid.cuh: KIND_SKIP; measurement only)
 	uint32_t reteam;   // NRS_RETEAM bit 0: at the end of a wave's work, bit 1: whenever a tail generation has thinned out
 	uint32_t steal;    // NRS_STEAL
 	bool log_teams;    // NRS_TEAM_LOG

@@ -1,6 +1,7 @@
 // nrs_api_selection.cpp -- the selection tool: region growing on the host (RegionGrowing, region_growing.cu), morphology of a bitfield level on the device with its host
 // twin (CorrectMMOperations, correct_mm_operations.cu), and the fine mesh of a selection (GrowingSelection::extract_fine_mesh, growing_selection.cu:2096-2162).
 #include "nrs_handles.h"
+#include "nrs_selection.h"
 
 #include <cmath>
 #include <cstring>

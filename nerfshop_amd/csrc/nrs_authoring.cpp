@@ -17,6 +17,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_svd3.h"
 
@@ -28,7 +29,7 @@ struct P3 { float x, y, z; };
 inline P3 sub(P3 a, P3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 inline P3 add(P3 a, P3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 inline P3 mul(P3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-// Eigen's 3-term reduction order (Eigen/src/Core/Redux.h, complete unrolling: x0 + (x1 + x2)); see nrs_device.cuh
+// Eigen's 3-term reduction order (Eigen/src/Core/Redux.h, complete unrolling: x0 + (x1 + x2)); see nrs_vec.cuh
 inline float dotp(P3 a, P3 b) { return a.x * b.x + (a.y * b.y + a.z * b.z); }
 inline P3 crossp(P3 a, P3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 inline float at(const P3& p, int i) { return i == 0 ? p.x : (i == 1 ? p.y : p.z); }

@@ -12,9 +12,14 @@
 // Kernels are HBM/latency-bound integer work: one wave per (tet, cascade) strides over the cells of the tet's bounding
 // box; the CSR scan streams the 42 MB count array twice.  Nothing here is GEMM-shaped.
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_cage.h"
+#include "nrs_scan.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_edit_warp.cuh"
 #include "nrs_scan.cuh"
 #include "nrs_svd3.h"
 
@@ -501,7 +506,7 @@ __global__ void tet_mapback_kernel(uint32_t n_tets, const float* __restrict__ or
 	for (int q = 0; q < 6; ++q) dst[q] = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
 }
 
-// ---- per-tet face planes for point_in_tet_planes (nrs_device.cuh): the tet-only half of same_side_tet, selection_utils.h:33-39 ----
+// ---- per-tet face planes for point_in_tet_planes (nrs_edit_warp.cuh): the tet-only half of same_side_tet, selection_utils.h:33-39 ----
 __global__ void tet_planes_kernel(uint32_t n_tets, const float* __restrict__ verts, const uint32_t* __restrict__ tets, float* __restrict__ planes) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n_tets) return;

@@ -4,6 +4,7 @@
 #include <math.h>
 #include <string.h>
 #include <string>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 
 using namespace nrs;

@@ -18,6 +18,7 @@
 #include <new>
 #include <string>
 
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 
 namespace {

@@ -1,7 +1,7 @@
 // nrs_dataset.h -- what nrs_api_dataset.cpp and nrs_dataset.hip share: the camera record as the device reads it and the launchers of the dataset's kernels
 // (include/nrs.h, "the dataset").  Not part of the public ABI.
 #pragma once
-#include "nrs_internal.h"
+#include "../../include/nrs.h"
 
 namespace nrs {
 

@@ -7,9 +7,14 @@
 //   error_map_cdf_kernel         construct_cdf_2d (tn:2620), construct_cdf_1d (tn:2650) and train_nerf's host loop over the images (tn:3811-3822).
 //   mark_untrained_kernel   mark_untrained_density_grid (tn:353-400).
 #include <hip/hip_runtime.h>
-#include "nrs_dataset.h"
+#include "../../include/nrs.h"
+#include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_dataset.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_random.cuh"
+#include "nrs_camera.cuh"
 
 namespace nrs {
 

@@ -4,9 +4,10 @@
 //   tonemap_*            CudaRenderBuffer::tonemap: the display step after accumulate, with 8-bit output.
 //   detile_kernel        multi-GPU tile scatter.
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_display.h"
 
 namespace nrs {
 
@@ -76,7 +77,7 @@ int launch_accumulate_spp(uint32_t n_pixels, const float* d_frames, size_t slab_
 // One thread per pixel, lanes on consecutive pixels: a wave loads 1 KiB contiguous and stores 1 KiB (RGBA32F) or 256 B (RGBA8) contiguous.  HBM-bound like accumulate
 // (32 or 20 B per pixel).  Everything is plain fp32 in the reference's operation order (-ffp-contract=off, no fmaf: bit-exact against a float restatement) except the two
 // powf of the sRGB curves (the device library's: tolerance, as in accumulate_kernel).  These are the reference's curves (common_device.cuh:31-37, :55-61) with their powf and
-// their division -- not nrs_device.cuh's srgb_to_linear, whose exp2/log2 form is good to 1e-5 only, enough for a network's colour but not for this step's 2e-6.
+// their division -- not nrs_shade.cuh's srgb_to_linear, whose exp2/log2 form is good to 1e-5 only, enough for a network's colour but not for this step's 2e-6.
 __device__ __forceinline__ float tonemap_srgb_to_linear(float s) { return s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f); }
 __device__ __forceinline__ float tonemap_linear_to_srgb(float l) { return l < 0.0031308f ? 12.92f * l : 1.055f * powf(l, 0.41666f) - 0.055f; }
 // Array3f::cwiseMax(0.f) / cwiseMin(1.f) as Eigen evaluates them: (a < b) ? b : a and (b < a) ? b : a -- a NaN and the sign of a zero pass through

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 
 using namespace nrs;

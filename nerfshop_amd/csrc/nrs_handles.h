@@ -12,7 +12,9 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
+#include "nrs_render.h"
 
 namespace nrs {
 

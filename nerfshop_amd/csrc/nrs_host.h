@@ -2,6 +2,8 @@
 // helpers, the owner of a device allocation (all three in nrs_handles.h), and the few helpers that cross unit borders.  Host-only C++17: no .hip / .cuh includes it.
 #pragma once
 #include "nrs_handles.h"
+#include "../../include/nrs.h"
+#include "nrs_internal.h"
 
 namespace nrs {
 

@@ -1,4 +1,6 @@
 // nrs_launch.cpp -- the one definition of the launchers' error message (nrs_launch.h).
+#include "../../include/nrs.h"
+#include "nrs_internal.h"
 #include "nrs_launch.h"
 
 namespace nrs {

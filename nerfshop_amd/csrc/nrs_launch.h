@@ -3,7 +3,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include "nrs_internal.h"
 
 namespace nrs {
 

@@ -10,9 +10,13 @@
 // They are bound by the lattice read (the eight corners of a cell come from three x-rows that neighbouring lanes and the L2 share); the case table sits in LDS.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_mesh.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_shade.cuh"
 #include "nrs_scan.cuh"
 
 namespace nrs {

@@ -4,7 +4,7 @@
 //   image_metrics_kernel<REF_FMT>   a workgroup of 256 threads owns a 32 x 32 tile of pixels: stencil (5 x 5 separable blur of five quantities) and reduce.
 //   image_metrics_finish_kernel     one thread: n_pixels, mse, ssim, psnr from the two sums.
 #include <hip/hip_runtime.h>
-#include "nrs_internal.h"
+#include "../../include/nrs.h"
 #include "nrs_launch.h"
 #include "nrs_metrics.h"
 

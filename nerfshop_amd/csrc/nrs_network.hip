@@ -4,13 +4,23 @@
 //   grid_eval_kernel     get_density_on_grid / get_rgba_on_grid.
 //   selection_rays_kernel, poisson_fit_kernel   the selection tool's ray shooting, the membrane boundary fit.
 //   trace_samples_kernel test hook: the (t, dt) stream of listed pixels.
-//   slice_kernel         render mode Slice: one sample per pixel on a plane, in the render kernel's packet geometry (nrs_render.cuh packet_pixel).
+//   slice_kernel         render mode Slice: one sample per pixel on a plane, in the render kernel's packet geometry (nrs_packets.cuh packet_pixel).
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
+#include "nrs_route.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_render.h"
+#include "nrs_network.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_random.cuh"
+#include "nrs_camera.cuh"
+#include "nrs_march.cuh"
+#include "nrs_shade.cuh"
+#include "nrs_hashgrid.cuh"
 #include "nrs_mlp.cuh"
-#include "nrs_render.cuh"
+#include "nrs_packets.cuh"
 
 namespace nrs {
 
@@ -276,7 +286,7 @@ int launch_poisson_fit(const DeviceModel& m, uint32_t n_verts, uint32_t n_sh, co
 	return NRS_OK;
 }
 
-// MODE: a NetOp (nrs_internal.h).
+// MODE: a NetOp (nrs_network.h).
 // 768-thread workgroups: 12 waves share one LDS copy of the weights (24 KB) next to their 12 feature slabs (48 KB), two workgroups per CU
 // = 6 waves/SIMD at <= 80 VGPRs.  (256-thread workgroups, the first shape, put 3 workgroups = 3 waves/SIMD on a CU: the weights' copy
 // per workgroup was what filled the LDS.)

@@ -19,9 +19,12 @@
 //
 // Grid gradients: per sample, level and corner, two fp32 atomics (w_corner * g_x[2 l + f]) at the entry the forward's index function names: 256 per sample.
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_network_backward.h"
+#include "nrs_vec.cuh"
+#include "nrs_hashgrid.cuh"
 #include "nrs_mlp.cuh"
 
 namespace nrs {

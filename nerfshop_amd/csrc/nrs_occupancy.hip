@@ -4,9 +4,17 @@
 //   occ_accel_*          the marching accelerator (OccAccel) derived from the bitfield.
 //   grid_refresh / grid_ema   the deformed-space occupancy refresh: the operators, hash grid + density MLP on MFMA, max-splat.
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
+#include "nrs_route.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_occupancy.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_random.cuh"
+#include "nrs_edit_warp.cuh"
+#include "nrs_shade.cuh"
+#include "nrs_hashgrid.cuh"
 #include "nrs_mlp.cuh"
 
 namespace nrs {
@@ -229,6 +237,28 @@ __host__ __device__ constexpr uint32_t inverse_mod_2_32(uint32_t k) { // Newton:
 }
 constexpr uint32_t kSampleMulInv = inverse_mod_2_32(kSampleMul) & (kGridVol - 1u);
 static_assert(((kSampleMul * kSampleMulInv) & (kGridVol - 1u)) == 1u, "inverse of the sample multiplier mod 2^21");
+
+// generate_grid_samples_nerf_nonuniform, cn:179-208: cell index + a uniformly random warped position inside that cell
+// `rng` arrives already advanced by 4 * i (the kernel splits that skip into a wave-uniform and a per-lane part).
+__device__ __forceinline__ uint32_t generate_grid_sample(Pcg32 rng, uint32_t i, uint32_t n_elements, uint32_t step, const Box3& aabb,
+                                                         const float* __restrict__ grid_in, uint32_t n_cascades, float thresh, f3& wpos) {
+	const uint32_t level = (uint32_t)(rng.next_float() * n_cascades) % n_cascades;
+	uint32_t idx = 0;
+	#pragma unroll 1
+	for (uint32_t j = 0; j < 10; ++j) {
+		idx = ((i + step * n_elements) * 56924617u + j * 19349663u + 96925573u) % kGridVol;
+		idx += level * kGridVol;
+		if (grid_in[idx] > thresh) break;
+	}
+	const uint32_t pos_idx = idx % kGridVol;
+	const float x = (float)morton3D_invert(pos_idx >> 0), y = (float)morton3D_invert(pos_idx >> 1), z = (float)morton3D_invert(pos_idx >> 2);
+	const float rx = rng.next_float(), ry = rng.next_float(), rz = rng.next_float();
+	const float s = __uint_as_float((127u + level) << 23); // scalbnf(1, level)
+	const float inv = 1.0f / (float)kGrid;                  // exact: x / 128 == x * 2^-7
+	const f3 pos = {((x + rx) * inv - 0.5f) * s + 0.5f, ((y + ry) * inv - 0.5f) * s + 0.5f, ((z + rz) * inv - 0.5f) * s + 0.5f};
+	wpos = warp_position(pos, aabb);
+	return idx;
+}
 
 template <int NUM>
 __global__ __launch_bounds__(256) void grid_refresh_kernel(const DeviceModel m, const GridUpdateArgs a) {

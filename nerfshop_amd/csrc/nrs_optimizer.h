@@ -1,7 +1,7 @@
 // nrs_optimizer.h -- what nrs_api_optimizer.cpp, nrs_optimizer.hip and nrs_api_model.cpp share: the argument block and launchers of the optimiser step
 // (include/nrs.h, "optimiser"), and the two doors through which an optimiser bound to a model hands it new parameters.  Not part of the public ABI.
 #pragma once
-#include "nrs_internal.h"
+#include "../../include/nrs.h"
 
 struct nrs_model;
 

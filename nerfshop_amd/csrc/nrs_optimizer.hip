@@ -7,6 +7,7 @@
 // IEEE division and square root, so the result can be compared against a float32 restatement bit by bit.  The bias correction comes from a host-made table, not from powf.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include "../../include/nrs.h"
 #include "nrs_launch.h"
 #include "nrs_optimizer.h"
 

@@ -12,12 +12,23 @@
 //                        for its tail).  TEAM == 0 waves re-team when a generation has thinned out, test a team's next positions
 //                        in parallel, and hand rays over to waves of their workgroup that have run out of work.
 // nrs_render_rows.hip instantiates it, one instantiation per row of kRoutes (nrs_route.h); slice_kernel (nrs_network.hip) shares the packet geometry
-// (packet_pixel); tools/one_kernel.sh compiles ONE explicit instantiation from this header for register work.
+// (nrs_packets.cuh); tools/one_kernel.sh compiles ONE explicit instantiation from this header for register work.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
-#include "nrs_device.cuh"
+#include "nrs_route.h"
+#include "nrs_render.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_random.cuh"
+#include "nrs_camera.cuh"
+#include "nrs_march.cuh"
+#include "nrs_edit_warp.cuh"
+#include "nrs_shade.cuh"
+#include "nrs_hashgrid.cuh"
 #include "nrs_mlp.cuh"
+#include "nrs_packets.cuh"
 
 namespace nrs {
 
@@ -102,37 +113,6 @@ __device__ __forceinline__ uint32_t claim_packet(unsigned long long* state, uint
 	return (uint32_t)__builtin_amdgcn_readfirstlane((int)result);
 }
 
-// packet -> pixel of this lane.  Packets are 8x8 pixel blocks; with lane teams (TEAM lanes per ray) a packet is the 64 / TEAM
-// pixels of an 8x4 / 4x4 block and the TEAM lanes of a team stand on the same pixel.
-template <int TEAM>
-__device__ __forceinline__ bool packet_pixel(const RenderArgs& a, uint32_t pk, int lane, uint32_t& x, uint32_t& y, uint32_t& out_idx) {
-	constexpr uint32_t PW = TEAM >= 16 ? 2u : (TEAM >= 4 ? 4u : 8u), PH = 64u / TEAM / PW; // 8x8, 8x4, 4x4, 4x2, 2x2
-	const uint32_t W = (uint32_t)a.p.resolution[0], H = (uint32_t)a.p.resolution[1];
-	const uint32_t idx = (uint32_t)lane / TEAM;
-	const uint32_t lx = idx % PW, ly = idx / PW;
-	if (a.p.tile_size == 0) {
-		// whole image: packets in row-major order (runs of neighbouring packets per claim were measured and lose: a wave's
-		// unstarted packets are invisible to idle waves)
-		// (packet rows from the middle of the image outwards -- thick rays first, silhouettes last -- measured in round 6: -4 % lego, -1 % varied, -11 % membrane:
-		// neighbouring rows share more than a shorter tail saves; profiles/r06/ab_roworder_*.txt)
-		const uint32_t bx = pk % a.tiles_x, by = pk / a.tiles_x;
-		x = bx * PW + lx;
-		y = by * PH + ly;
-		out_idx = x + W * y;
-	} else {
-		const uint32_t ppt = a.packets_per_tile_x * (a.p.tile_size / PH);
-		const uint32_t k = pk / ppt, b = pk % ppt;
-		const uint32_t stride = a.p.tile_stride ? a.p.tile_stride : 1;
-		const uint32_t T = a.p.tile_first + k * stride;
-		const uint32_t Tx = T % a.tiles_x, Ty = T / a.tiles_x;
-		const uint32_t tx = (b % a.packets_per_tile_x) * PW + lx, ty = (b / a.packets_per_tile_x) * PH + ly;
-		x = Tx * a.p.tile_size + tx;
-		y = Ty * a.p.tile_size + ty;
-		out_idx = (k * a.p.tile_size + ty) * a.p.tile_size + tx;
-	}
-	return x < W && y < H;
-}
-
 // WAVES = waves per workgroup (they share one LDS copy of the weights); OCC = waves per SIMD the register allocator must
 // leave room for (__launch_bounds__' second argument).
 // PROF adds s_memtime stamps around the phases of a round (NRS_DEBUG & 4); the production instantiation has none.
@@ -158,38 +138,6 @@ __device__ __forceinline__ bool packet_pixel(const RenderArgs& a, uint32_t pk, i
 // the common path pays neither its registers nor its code.
 // AFFINE compiles in the AffineDuplication operator (edit_warp's second kind): frames whose operators are all cage
 // deformations -- the common case and the benchmark -- run the instantiation without it (2 % faster: 122 vs 128 VGPRs).
-// where pixel (x, y) of this launch lands in the caller's buffers: packet_pixel's out_idx from the pixel alone
-__device__ __forceinline__ uint32_t pixel_out_idx(const RenderArgs& a, uint32_t x, uint32_t y) {
-	if (a.p.tile_size == 0) return x + (uint32_t)a.p.resolution[0] * y;
-	const uint32_t ts = a.p.tile_size, Tx = x / ts, Ty = y / ts, T = Ty * a.tiles_x + Tx;
-	const uint32_t stride = a.p.tile_stride ? a.p.tile_stride : 1;
-	const uint32_t k = (T - a.p.tile_first) / stride;
-	return (k * ts + (y - Ty * ts)) * ts + (x - Tx * ts);
-}
-
-// Hybrid launches (TEAM == 0, whole-image mode): every tail_every-th (3rd) packet row of the image is taken out of the 8x8 packet
-// list and appended to the queue as 4x4 packets ("tail" packets, a uniform sample of the picture, so the same share of the rays
-// whatever the scene).  Waves that reach them switch to lane teams: the last rays of a frame then take a quarter of a
-// ray's life while the waves still on their last 64-ray generation finish (see render_kernel).
-__device__ __forceinline__ bool packet_pixel_bulk(const RenderArgs& a, uint32_t pk, int lane, uint32_t& x, uint32_t& y, uint32_t& out_idx) {
-	const uint32_t W = (uint32_t)a.p.resolution[0], H = (uint32_t)a.p.resolution[1];
-	const uint32_t rb = pk / a.tiles_x, col = pk % a.tiles_x, row = rb + rb / (a.tail_every - 1u); // every tail_every-th row is a tail row
-	x = col * 8u + ((uint32_t)lane & 7u);
-	y = row * 8u + ((uint32_t)lane >> 3);
-	out_idx = x + W * y;
-	return x < W && y < H;
-}
-__device__ __forceinline__ bool packet_pixel_tail(const RenderArgs& a, uint32_t q, int lane, uint32_t& x, uint32_t& y, uint32_t& out_idx) {
-	const uint32_t W = (uint32_t)a.p.resolution[0], H = (uint32_t)a.p.resolution[1];
-	// a tail row is 8 pixels high; its packets are 4x4 / 8x4 / 8x8 pixels with fill_lanes = 4 / 2 / 1 lanes on a pixel (as in packet_pixel<4 / 2 / 1>)
-	const uint32_t L = a.fill_lanes, cols = L == 4u ? a.tiles_x * 2u : a.tiles_x, per_row = cols * (L == 1u ? 1u : 2u);
-	const uint32_t trow = q / per_row, s = q % per_row, sy = s / cols, sx = s % cols;
-	const uint32_t idx = (uint32_t)lane / L, pw = L == 4u ? 4u : 8u;
-	x = sx * pw + (idx % pw);
-	y = (trow * a.tail_every + a.tail_every - 1u) * 8u + sy * 4u + (idx / pw);
-	out_idx = x + W * y;
-	return x < W && y < H;
-}
 
 // TEAM = lanes per ray (1, 2, 4) -- *lane teams* for launches with too few rays to fill the GPU (one GPU's tiles of a frame
 // sharded over 4-8 GPUs).  A ray needs one round per sample and a round is a latency chain, so such a launch takes one
@@ -619,10 +567,10 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 					empty |= edit_warp<!POISSON>(a2.edits[ei], true, wpos, wdir); // (the membrane catch-all rows stand at their register limit like the membrane kernel)
 				} else if (POISSON) {
 					uint32_t scan; // (a local of the iteration, selected below: a pointer that is sometimes null made warp_scan a stack object)
-					empty |= tet_warp<false>(a2.edits[ei], true, wpos, wdir, sm.coarse, &scan); // (the parent's map-back: no register to spare, nrs_device.cuh)
+					empty |= tet_warp<false>(a2.edits[ei], true, wpos, wdir, sm.coarse, &scan); // (the parent's map-back: no register to spare, nrs_edit_warp.cuh)
 					if (ei == a2.n_edits - 1) warp_scan = scan;
 				} else {
-					empty |= tet_warp<GATE == 0, GATE == 0>(a2.edits[ei], true, wpos, wdir, sm.coarse, nullptr, PROF ? &pf_scan : nullptr); // (the gated kernel keeps the long chain: nrs_device.cuh find_tet)
+					empty |= tet_warp<GATE == 0, GATE == 0>(a2.edits[ei], true, wpos, wdir, sm.coarse, nullptr, PROF ? &pf_scan : nullptr); // (the gated kernel keeps the long chain: nrs_edit_warp.cuh find_tet)
 				}
 			}
 		}

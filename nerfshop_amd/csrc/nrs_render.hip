@@ -3,9 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <utility>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
+#include "nrs_route.h"
 #include "nrs_launch.h"
 #include "nrs_render.h"
+#include "nrs_render_rows.h"
 
 namespace nrs {
 

@@ -3,8 +3,12 @@
 // compile in parallel.  Row ROW belongs to shard ROW % NRS_ROW_SHARDS: every row is in exactly one shard, and a new row of kRoutes needs no edit here.
 #include <hip/hip_runtime.h>
 #include <utility>
+#include "../../include/nrs.h"
+#include "nrs_internal.h"
+#include "nrs_route.h"
 #include "nrs_launch.h"
 #include "nrs_render.h"
+#include "nrs_render_rows.h"
 #include "nrs_render.cuh"
 
 #if !defined(NRS_ROW_SHARD) || !defined(NRS_ROW_SHARDS) || NRS_ROW_SHARD < 0 || NRS_ROW_SHARD >= NRS_ROW_SHARDS

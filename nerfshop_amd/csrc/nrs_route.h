@@ -43,7 +43,7 @@ constexpr bool route_carries_views(bool poisson, bool affine, int xtra, bool bat
 constexpr bool same_traits(XtraTraits a, XtraTraits b) { return a.extra == b.extra && a.intro == b.intro && a.deep == b.deep && a.light == b.light && a.gate == b.gate; }
 static_assert(same_traits(xtra_traits(kXtraExtraViews), xtra_traits(kXtraExtra)), "XTRA 9 is XTRA 1 with the view table: the same body otherwise");
 static_assert(route_carries_views(false, false, kXtraExtraViews, true) && !route_carries_views(false, false, kXtraExtra, true), "of the two lean EXTRA twins, XTRA 9 reads the view table");
-constexpr int kNumRuntime = -1; // NUM: tiny-cuda-nn's other roundings chosen at run time from DeviceModel::numerics (nrs_mlp.cuh encode_num)
+constexpr int kNumRuntime = -1; // NUM: tiny-cuda-nn's other roundings chosen at run time from DeviceModel::numerics (nrs_hashgrid.cuh encode_num)
 
 // ---- one instantiation ----------------------------------------------------------------------------------------------------------------------------------
 enum RouteEntry : int {
@@ -243,7 +243,7 @@ inline RoutePlan plan_route(const RouteRequest& q) {
 		return refuse(NRS_ERR_STATE);
 	}
 	// Cone stepping is what the reference switches on for aabb_scale > 1 (tn:3410-3425): scenes whose fine hashed levels no two samples of a wave share, so that their
-	// 8 MB of table lines thrash the 4 MB L2 of an XCD -- the GATE instantiation time-multiplexes it (nrs_mlp.cuh encode_to_lds; profiles/r06_garden.md: L2 misses per
+	// 8 MB of table lines thrash the 4 MB L2 of an XCD -- the GATE instantiation time-multiplexes it (nrs_hashgrid.cuh encode_to_lds; profiles/r06_garden.md: L2 misses per
 	// sample 11.5 -> 7.2, +5 % on the garden frame).  A unit-cube scene (constant steps) never takes it: there the gate costs 18 %.
 	// (only where the gate has something to separate: the two, three or four finest level PAIRS hashed without records -- one phase each -- and records below them;
 	// more hashed pairs than phases would run the GATE instantiation ungated, 5 % behind the default kernel: profiles/r06/ab_gate_phases_*.txt)

@@ -3,8 +3,9 @@
 // The callers (cage look-up tables: nrs_cage.hip, 1 value per tile of 4096 cells; marching cubes: nrs_mesh.hip, 2 values per block of 256 points; training rays:
 // nrs_train.hip, 2 values per tile of 1024 rays) sum their tiles into `sums`, launch this, and scan inside each tile on top of its now exclusive prefix.
 #include <hip/hip_runtime.h>
-#include "nrs_internal.h"
+#include "../../include/nrs.h"
 #include "nrs_launch.h"
+#include "nrs_scan.h"
 #include "nrs_scan.cuh"
 
 namespace nrs {

@@ -11,9 +11,11 @@
 // Erosion is the same walk on the complement -- a cell survives iff no in-grid tap is clear iff the complement's dilation misses it -- which also shifts 1 in at the ends.
 // A level is 256 KiB and stays in L2 between the launches; every launch covers it exactly (no tail, no bounds test needed: the grid sizes are static_asserted).
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_selection.h"
+#include "nrs_grid_math.cuh"
 
 namespace nrs {
 

@@ -4,9 +4,13 @@
 //   weight_fragments_kernel, brick_*   the MFMA weight fragments read from HBM; the sparse cell records (nrs_model_set_sparse_cell_cache).
 //   map_rays_kernel      EditOperator::map_rays / map_positions on caller batches.
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
+#include "nrs_tables.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_edit_warp.cuh"
 
 namespace nrs {
 

@@ -2,6 +2,7 @@
 // Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 
 namespace nrs {

@@ -11,11 +11,15 @@
 // "one lane per sample" below.  No float atomics: every output is a function of the inputs alone.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include "../../include/nrs.h"
 #include "nrs_internal.h"
 #include "nrs_launch.h"
-#include "nrs_device.cuh"
-#include "nrs_scan.cuh"
+#include "nrs_scan.h"
 #include "nrs_train.h"
+#include "nrs_vec.cuh"
+#include "nrs_grid_math.cuh"
+#include "nrs_shade.cuh"
+#include "nrs_scan.cuh"
 
 namespace nrs {
 

@@ -58,6 +58,27 @@ def test_the_render_kernel_header_rebuilds_every_shard_and_no_streaming_object()
     objects, link = _rebuilt_if_touched("nrs_render.cuh")
     assert _shards(objects) == _all_shards(), objects
     assert not objects & ({"nrs_display", "nrs_tables", "nrs_occupancy", "nrs_cage", "nrs_render"} | API_OBJECTS), objects
+    # (slice_kernel takes the packet geometry from nrs_packets.cuh: the network object no longer sees the render kernel, and neither does any other subsystem)
+    assert not objects & {"nrs_network", "nrs_network_backward", "nrs_train", "nrs_dataset", "nrs_mesh", "nrs_selection", "nrs_scan", "nrs_optimizer", "nrs_metrics"}, objects
+    assert link
+
+
+def test_the_edit_warp_header_rebuilds_every_shard_and_the_three_units_that_warp_samples():
+    objects, link = _rebuilt_if_touched("nrs_edit_warp.cuh")
+    assert _shards(objects) == _all_shards(), objects
+    assert objects - _shards(objects) == {"nrs_cage", "nrs_occupancy", "nrs_tables"}, objects  # the users of the tet search and the affine warp outside the render kernel
+    assert link
+
+
+def test_the_mesh_launcher_header_rebuilds_the_mesh_unit_and_its_callers():
+    objects, link = _rebuilt_if_touched("nrs_mesh.h")
+    assert objects == {"nrs_mesh", "nrs_api_mesh"}, objects  # (no render shard, no other device object)
+    assert link
+
+
+def test_the_shade_header_reaches_no_unit_that_shades_nothing():
+    objects, link = _rebuilt_if_touched("nrs_shade.cuh")
+    assert not objects & {"nrs_cage", "nrs_selection", "nrs_tables", "nrs_scan", "nrs_optimizer", "nrs_metrics"}, objects
     assert link
 
 

@@ -1,4 +1,4 @@
-"""The fine look-up table under the cage's 128^3 cell -> tet LUT (round 6; nrs_cage.hip fine_lists_kernel, nrs_device.cuh find_tet) is a shortcut of the reference's
+"""The fine look-up table under the cage's 128^3 cell -> tet LUT (round 6; nrs_cage.hip fine_lists_kernel, nrs_edit_warp.cuh find_tet) is a shortcut of the reference's
 scan (interpolate_tet, cage_deformation.cu:197-269: the first tet of the cell's list that contains the sample): every result must be the plain scan's, bit for bit.
 The plain scan is the same library with NRS_NO_FINE_LUT (a measurement knob: its own process); both are also held against the oracle elsewhere
 (tests/test_gpu_parity.py::test_map_rays_bit_exact, tests/test_gpu_bench_parity.py)."""

@@ -1,4 +1,4 @@
-"""The lattice jump of the voxel walk (nrs_device.cuh: lattice_jump) under cameras chosen to stress its guard: many directions, views along the axes --
+"""The lattice jump of the voxel walk (nrs_march.cuh: lattice_jump) under cameras chosen to stress its guard: many directions, views along the axes --
 rays whose direction has a zero or tiny component (1 / d infinite or huge: the band B then refuses the jump and the cell-by-cell walk must take over) -- and both
 places it runs: the fill's first hit (the (t, dt) stream of nrs_trace_samples: bit for bit against the oracle's cell-by-cell walk) and the per-round walk of the render
 kernel (per-pixel sample counts and depth against the oracle).  tests/test_lattice.py checks the integer arithmetic on the CPU."""

@@ -1,4 +1,4 @@
-"""The cage operator's memory chain (nrs_device.cuh find_tet / scan_fine_cell_for_tet / tet_warp): the fine window through scalar loads, the head word per fine
+"""The cage operator's memory chain (nrs_edit_warp.cuh find_tet / scan_fine_cell_for_tet / tet_warp): the fine window through scalar loads, the head word per fine
 cell (DeviceEdit::fine_head) and the map-back record per tet (DeviceEdit::mapback) change which loads bring the operands, not one float operation.  So
 CageDeformation.map_rays / map_positions must give the oracle's operator (cage_deformation.cu:136-269 restated on the CPU) bit for bit: coordinates, directions and
 the empty mask, in every state an operator goes through -- as created (fine table with heads), after a cage move (table dropped: the plain scan, map-back records

@@ -1,4 +1,4 @@
-"""The arithmetic fact behind lattice_jump (nrs_device.cuh; DESIGN.md 4, "Lattice jump"), checked on the CPU with IEEE float32 (numpy): with a constant step dt the
+"""The arithmetic fact behind lattice_jump (nrs_march.cuh; DESIGN.md 4, "Lattice jump"), checked on the CPU with IEEE float32 (numpy): with a constant step dt the
 parameters a voxel walk stands on are t (+) dt (+) dt ...; inside one binade [2^e, 2^(e+1)) every such rounded addition adds the SAME number q of ulps, q = dt / ulp(t)
 rounded to the nearest integer (no ties for this dt: the increment then does not depend on the parity of t), so the lattice point k steps on is the integer addition
 bits(t) + k q -- what the kernel computes instead of the chain.  The formulas here are the kernel's (x = dt 2^(150 - e_t), q = rint(x), ulps left in the binade)."""

@@ -1,8 +1,8 @@
 """The route planner (nerfshop_amd/csrc/nrs_route.h plan_route) on the CPU: every request is refused for a documented reason or gets a row of the
 instantiation table whose traits serve it -- the conditions launch_render's last guard (nrs_render.hip check_route) states, asked of the plan before any launch.
 
-The planner is reached through nrs_route_probe, a symbol libnrs.so exports for this test alone (declared in nrs_internal.h, not part of include/nrs.h);
-RouteRequest / RouteProbe below mirror the structs of nrs_route.h / nrs_internal.h, and the symbol refuses a mirror whose size has drifted."""
+The planner is reached through nrs_route_probe, a symbol libnrs.so exports for this test alone (declared in nrs_render.h, not part of include/nrs.h);
+RouteRequest / RouteProbe below mirror the structs of nrs_route.h / nrs_render.h, and the symbol refuses a mirror whose size has drifted."""
 import ctypes as C
 import itertools
 import re

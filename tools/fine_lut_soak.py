@@ -1,4 +1,4 @@
-"""Soak of the fine look-up table under the cage's cell -> tet LUT (round 6: nrs_cage.hip fine_lists_kernel, nrs_device.cuh find_tet): random cages -- lattice
+"""Soak of the fine look-up table under the cage's cell -> tet LUT (round 6: nrs_cage.hip fine_lists_kernel, nrs_edit_warp.cuh find_tet): random cages -- lattice
 sizes, translations, twists up to folded tets, both scene scales -- and, per cage, 2^20 positions (a fifth of them ON vertices / edge midpoints / faces of tets, where
 two tets pass the containment test and the ORDER of the cell's list decides), map_rays and map_positions bit for bit against the oracle (interpolate_tet,
 cage_deformation.cu:197-269 as restated in oracle/nrs_oracle.cpp and pinned to the reference's compiled code by tests/test_ref_pin.py).  Too long for the test tier

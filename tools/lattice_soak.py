@@ -1,4 +1,4 @@
-"""Soak of the lattice jump (nrs_device.cuh): the first samples of every pixel of 300 random cameras (a tenth of them within a hundredth of a degree of a coordinate
+"""Soak of the lattice jump (nrs_march.cuh): the first samples of every pixel of 300 random cameras (a tenth of them within a hundredth of a degree of a coordinate
 axis), 11 M rays, bit for bit against the oracle's cell-by-cell walk.  Too long for the test tier (tests/test_gpu_lattice_jump.py is its short form); run through gpurun:
     python tools/lattice_soak.py
 Round 5's run: 11 059 200 rays, 5 028 799 with samples, cameras with any differing bit: 0; then 120 whole frames (the render kernel's per-round walk): none with a
