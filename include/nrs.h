@@ -839,8 +839,8 @@ int  nrs_selection_fine_mesh(nrs_ctx* ctx, void* stream, nrs_selection* sel, int
 /* The two steps between "rays + the colours they should have" and nrs_network_backward: generate_training_samples_nerf (src/testbed_nerf.cu:1087, from :1188 on: everything
  * after the ray exists) and compute_loss_kernel_train_nerf (:1685-1985) with the seven losses of :103-171.  Callers detect these entry points by symbol (dlsym);
  * NRS_ABI_VERSION is unchanged because no existing layout changes.  The rays themselves -- image / pixel selection, lens distortion, rolling shutter -- come from a
- * dataset (nrs_dataset_rays, below) or from the caller.  Not here: the envmap and its
- * gradient, exposure and its gradient, the error map and sharpness, max_level_rand_training, image / pixel PDFs (img_pdf = xy_pdf = 1), fill_rollover_and_rescale
+ * dataset (nrs_dataset_rays, below) or from the caller.  The envmap and its gradient are nrs_envmap_*'s and nrs_ray_loss_ex's, further down.  Not here: exposure and
+ * its gradient, the error map and sharpness, max_level_rand_training, image / pixel PDFs (img_pdf = xy_pdf = 1), fill_rollover_and_rescale
  * (nrs_network_backward takes any n), the camera-gradient kernels, the distill variants, light-direction models.
  *
  * Both calls are asynchronous on `stream`, never wait for the device and keep their per-ray workspace in the model: it is allocated on the first call of a size and
@@ -991,7 +991,7 @@ size_t   nrs_optimizer_n_params(const nrs_optimizer* opt, size_t* n_matrix);
  * of the pixel's time, lens distortion), the look-ups compute_loss_kernel_train_nerf repeats for a ray's target and background (:1777-1806), the loader's image
  * conversion (from_rgba32, common_device.cuh:513-540; from_fullp, src/nerf_loader.cu:62) and mark_untrained_density_grid (:353-400).  Callers detect these entry
  * points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  The error-map CDFs (cdf_img, cdf_x_cond_y) are
- * nrs_dataset_rays_ex's, further down: nrs_dataset_rays is the `cdf == nullptr` branches.  Not here: explicit per-pixel rays (rays_in), the trainable per-pixel distortion map, the envmap and exposure, light directions (a dataset serves
+ * nrs_dataset_rays_ex's, further down: nrs_dataset_rays is the `cdf == nullptr` branches.  Not here: explicit per-pixel rays (rays_in), the trainable per-pixel distortion map, exposure (the envmap is nrs_envmap_*'s, further down), light directions (a dataset serves
  * n_extra_dims == 0 models), sharpening and the sharpness map, EXR, the adaptive rays_per_batch of train_nerf (it reads counters back), decoding image files (the
  * Python package does that).
  *
@@ -1206,6 +1206,94 @@ int nrs_dataset_image_metrics(nrs_dataset* ds, uint32_t index, void* stream, con
 int nrs_image_metrics_host(uint32_t width, uint32_t height, const float* h_image, const void* h_reference, const nrs_image_metrics_params* params,
                            nrs_image_metrics_result* h_result, float* h_ssim_map, float* h_sq_err_map);
 int nrs_image_metrics_summary_host(const nrs_image_metrics_result* h_results, uint32_t n, nrs_metrics_summary* out);
+
+/* ---- the environment map: a trained background behind the last sample ------------------------------------------------------------------------------ */
+/* The m_envmap the reference trains next to the network (src/testbed.cu:2427-2441, configs/nerf/base.json:76-103): the background a training ray sees
+ * (src/testbed_nerf.cu:1792-1801), its gradient (:1961-1984) and its own optimiser step (:3731-3733, :3766-3768).  What it learns is what nrs_render_params::d_envmap
+ * reads.  All of it is new surface, detected by symbol (nrs_envmap_create); nrs_ray_loss, nrs_training_samples, nrs_dataset_rays* and nrs_optimizer_* are what they
+ * were.  Not here: per-image exposure and its gradient (:1803, :1946-1959), loading envmap.png, the equirectangular reader, the distill kernels, light-direction
+ * models.  A DELIBERATE OMISSION: rays with zero samples are still not emitted by nrs_training_samples.  The reference's train_envmap switch (:1214) emits them, but
+ * its loss kernel returns at :1838 for a ray without compact samples before it reaches the envmap's gradient: the switch changes which slots exist and no gradient.
+ *
+ * An nrs_envmap owns res_x x res_y RGBA float texels, laid out like d_envmap ([res_y][res_x][4], >= 1 x 1; a lookup wraps in x and clamps in y), an unbound
+ * optimiser over its 4 * res_x * res_y floats with n_matrix = 0 (THE RULE of the optimiser block, every texel channel a non-matrix parameter: a channel whose
+ * gradient is zero is not touched, the EMA advances for all), a float gradient of that size and a gradient accumulator of signed 64-bit cells.  The default
+ * Adam parameters (params == NULL, or what nrs_envmap_default_adam_params fills in) are base.json's envmap block: beta 0.9 / 0.99, epsilon 1e-10, ema_decay 0.99,
+ * non_matrix_lr_factor 1; l2_reg is irrelevant because there are no matrix weights.  The learning-rate schedule is the caller's: base.json's is 1e-2 with
+ * nrs_exponential_decay_lr(1e-2, 10000, 5000, 0.33, step).  A FRESH MAP IS ALL ZEROS until texels are set (this library's rule: the reference's initial values
+ * are tiny-cuda-nn's, which is not part of the reference tree).  The training loss reads the LIVE texels (the optimiser's master weights); rendering and evaluation
+ * use the EMA (params() versus params_inference()).  As everywhere in the optimiser the EMA follows the fp16 copy of the weights (a deviation stated there).
+ *
+ * nrs_envmap_create / _destroy; nrs_envmap_resolution.  Creation allocates everything and waits for the device once; there is no lazy state, so no call here returns
+ *   NRS_ERR_STATE.
+ * nrs_envmap_set_texels: the live texels from a host (on_device == 0; returns when the copy is done) or device pointer, [res_y][res_x][4] f32; resets the optimiser as
+ *   nrs_optimizer_set_weights does (the EMA becomes the texels) and zeroes the gradient and the cells.
+ * nrs_envmap_get: synchronous (waits for the device first), n = 4 * res_x * res_y elements to the host.  NRS_ENVMAP_TEXELS: the live texels; NRS_ENVMAP_EMA; NRS_ENVMAP_GRADIENT:
+ *   (float)((double)cell * 2^-32) of the cells as they are now, f32 -- the gradient the next step will read (zero right after a step); NRS_ENVMAP_CELLS: the cells, int64.
+ * nrs_envmap_export: asynchronous; the live (ema == 0) or the EMA texels into d_out [res_y][res_x][4] f32 on the device: what d_envmap takes.
+ *
+ * nrs_envmap_background: one thread per ray slot s < min(*d_ray_counter, n_rays).  i = d_ray_indices[s] (nrs_training_samples; a slot with i >= n_rays is skipped),
+ *   d = d_rays[6 i + 3 ..], looked up in the live texels by the render path's read_envmap (envmap.cuh:30-63: theta = acosf(clamp(d.y)), phi = atan2f(-d.x, d.z),
+ *   f = (phi / 2pi + 0.5, theta / pi) * (res - 1), t = (int)f, w = f - t, bilinear in the order ((w00 a + w10 b) + w01 c) + w11 e).  Two records per slot:
+ *     d_background_linear[3 s ..] = env.rgb + srgb_to_linear(bg) * (1 - env.a), bg = d_background[3 s ..] (by slot, sRGB-encoded, as nrs_ray_loss takes it) or
+ *       default_background[3] when d_background is NULL; srgb_to_linear is the ray loss's (a division and powf);
+ *     d_footprint[4 s ..] = (tx, ty as int32, wx, wy as float32 bits): the texel and the weights of that lookup BEFORE wrapping and clamping; 16-byte aligned.
+ *   Slots at or past the counter are not written.  The footprint is computed once per ray and step and handed to the gradient pass (the reference's
+ *   deposit_envmap_gradient repeats acosf / atan2f), which also makes that pass a function of integers and float32 products alone.
+ *
+ * nrs_ray_loss_ex: nrs_ray_loss with two optional additions, both behind null checks where a ray is finished; the walk over the samples is the same code.
+ *   d_background_linear [n_rays x 3] f32 by slot replaces srgb_to_linear(d_background / params->background); everything after that line is unchanged.
+ *   d_ray_aux [n_rays x 12] 32-bit words by slot, 16-byte aligned, written for live rays: words 0..2 g (loss_and_gradient's gradient), 3 T behind the ray's last
+ *   sample, 4..6 the target, 7..9 C (the colour the loss saw, background included), 10 n (u32: the ray's effective count, 0 where nrs_ray_loss treats it as 0),
+ *   11 M (u32).  With both NULL every output has nrs_ray_loss's bits; nrs_ray_loss IS that call.
+ *
+ * nrs_envmap_accumulate <- :1961-1983, one thread per slot s < min(*d_ray_counter, n_rays).  A slot deposits iff d_numsteps_out[2 s] == aux.n && aux.n > 0: the ray has
+ *   samples and was neither stopped (M < n) nor clipped by the compact buffer (M' < M).  Then, in fp32 without contraction, in this order:
+ *     lg = aux.g, or, if params->envmap_loss_type != params->loss_type, loss_and_gradient(envmap_loss_type, aux.target, aux.C) per channel (the reference's own
+ *       envmap loss is RelativeL2, testbed.cu:2438; nrs_envmap_accumulate_params has no default: the caller names both);
+ *     dbg = aux.T * lg;   unless train_in_linear_colors:  dbg = dbg / srgb_to_linear_derivative(linear_to_srgb(d_background_linear[3 s + c])) with
+ *       srgb_to_linear_derivative(x) = x <= 0.04045f ? 1.0f / 12.92f : 2.4f / 1.055f * powf((x + 0.055f) / 1.055f, 1.4f) (the loss saw the background sRGB-encoded);
+ *     v[c] = (loss_scale / (float)n_rays) * dbg[c];   alpha's gradient is 0 as in the reference (:1981): alpha texels never move.
+ *   DEPOSIT (the error map's rule, signed): the four weights (1 - wx) * (1 - wy), wx * (1 - wy), (1 - wx) * wy, wx * wy of the slot's footprint; for each weight and
+ *   channel p = v[c] * w; skipped unless p is finite and non-zero; clamped to +-512; multiplied by 2^32 (exact); rounded to nearest, ties to even, into int64; added
+ *   with ONE no-return 64-bit integer atomic to channel c of texel (wrap(tx + dx), clamp(ty + dy)) -- wrap adds or subtracts res_x once, as the lookup does, and then
+ *   clamps into the map, which acts for a footprint no lookup wrote alone.  2^21 rays of the clamp value sum to 2^62: a cell never wraps.
+ *   TWO DEVIATIONS, both deliberate: the reference rounds v and the weight to fp16 and adds with float (or half2) atomics; here nothing is rounded to fp16 (the
+ *   fixed-point step 2^-32 is finer than fp16's at every magnitude) and the sum does not depend on the order of arrival: two calls give the same bits.
+ * nrs_envmap_step: asynchronous, reads nothing back.  One kernel writes gradient[i] = (float)((double)cell[i] * 2^-32) and zeroes every cell it read non-zero; then the
+ *   optimiser's step kernel runs on the texels with that gradient, loss_scale, learning_rate and zero_grad = 1.
+ *
+ * Refused before any HIP call, NRS_ERR_INVALID_ARG: NULL handles or required pointers (with n_rays > 0); a wrong struct_size; a resolution < 1 or with
+ *   4 * res_x * res_y > 2^31; n_rays > 2^21; an unknown loss type or `which`; n != 4 * res_x * res_y in get; a misaligned d_footprint / d_ray_aux; a loss_scale that is
+ *   not finite (or, for the step, <= 0); a negative or non-finite learning_rate; adam params the optimiser refuses.  No entry point takes both an envmap and a model,
+ *   so there is no context mismatch to refuse here.  n_rays == 0 is NRS_OK. */
+typedef struct nrs_envmap nrs_envmap;
+typedef enum nrs_envmap_what { NRS_ENVMAP_TEXELS = 0, NRS_ENVMAP_EMA = 1, NRS_ENVMAP_GRADIENT = 2, NRS_ENVMAP_CELLS = 3 } nrs_envmap_what;
+#define NRS_RAY_AUX_WORDS 12u
+typedef struct nrs_envmap_accumulate_params {
+	uint32_t struct_size;            /* refused unless == sizeof(nrs_envmap_accumulate_params) */
+	uint32_t loss_type;              /* the step's nrs_loss_type: what aux.g was computed with */
+	uint32_t envmap_loss_type;       /* the envmap's own; the reference: NRS_LOSS_RELATIVE_L2 */
+	float    loss_scale;
+	uint32_t train_in_linear_colors;
+} nrs_envmap_accumulate_params;
+void     nrs_envmap_default_adam_params(nrs_adam_params* out);
+int      nrs_envmap_create(nrs_ctx* ctx, uint32_t res_x, uint32_t res_y, const nrs_adam_params* params, nrs_envmap** out);
+void     nrs_envmap_destroy(nrs_envmap* envmap);
+int      nrs_envmap_resolution(const nrs_envmap* envmap, uint32_t* res_x, uint32_t* res_y);
+int      nrs_envmap_set_texels(nrs_envmap* envmap, const float* texels_f32, int on_device, void* stream);
+int      nrs_envmap_get(nrs_envmap* envmap, int which, void* h_out, size_t n);
+int      nrs_envmap_export(nrs_envmap* envmap, int ema, float* d_out, void* stream);
+int      nrs_envmap_background(nrs_envmap* envmap, void* stream, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices, const float* d_rays,
+                               const float* d_background, const float* default_background, float* d_background_linear, int32_t* d_footprint);
+int      nrs_ray_loss_ex(nrs_model* model, void* stream, const nrs_ray_loss_params* params, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_numsteps,
+                         uint32_t n_samples, const float* d_coords, uint32_t ld_in, const void* d_output_fp16, uint32_t ld_out, int out_layout, const float* d_target_rgba,
+                         const float* d_background, const float* d_ray_origins, uint32_t* d_numsteps_out, float* d_coords_out, void* d_dL_doutput_fp16, uint32_t ld_dl,
+                         int dl_layout, float* d_loss, uint32_t* d_counter_out, const float* d_background_linear, uint32_t* d_ray_aux);
+int      nrs_envmap_accumulate(nrs_envmap* envmap, void* stream, const nrs_envmap_accumulate_params* params, uint32_t n_rays, const uint32_t* d_ray_counter,
+                               const uint32_t* d_numsteps_out, const uint32_t* d_ray_aux, const float* d_background_linear, const int32_t* d_footprint);
+int      nrs_envmap_step(nrs_envmap* envmap, void* stream, float loss_scale, float learning_rate);
+uint32_t nrs_envmap_step_count(const nrs_envmap* envmap);
 
 #ifdef __cplusplus
 }

@@ -113,6 +113,15 @@ public:
 		                   d_target_rgba, d_background, d_ray_origins, d_numsteps_out, d_coords_out, dL_doutput.data, dL_doutput.n, dL_doutput.layout, d_loss,
 		                   d_counter_out), "nrs_ray_loss");
 	}
+	// ray_loss with the two additions of the trainable environment map (nrs_ray_loss_ex): the linear background a ray sees (Envmap::background) and the per-slot record
+	// the envmap's gradient reads (NRS_RAY_AUX_WORDS words per slot); either may be NULL
+	void ray_loss_ex(void* stream, const nrs_ray_loss_params& params, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_numsteps, const InputMatrix& coords,
+	                 const OutputMatrix& output, const float* d_target_rgba, const float* d_background, const float* d_ray_origins, uint32_t* d_numsteps_out,
+	                 float* d_coords_out, OutputMatrix& dL_doutput, float* d_loss, uint32_t* d_counter_out, const float* d_background_linear, uint32_t* d_ray_aux) {
+		check(nrs_ray_loss_ex(m_model, stream, &params, n_rays, d_ray_counter, d_numsteps, coords.n, coords.data, coords.rows, output.data, output.n, output.layout,
+		                      d_target_rgba, d_background, d_ray_origins, d_numsteps_out, d_coords_out, dL_doutput.data, dL_doutput.n, dL_doutput.layout, d_loss,
+		                      d_counter_out, d_background_linear, d_ray_aux), "nrs_ray_loss_ex");
+	}
 	// tcnn::Network::visualize_activation(stream, layer, dimension, input, output): the activation itself, f32 [n] (testbed_nerf.cu:2926, :3159)
 	void visualize_activation(void* stream, uint32_t layer, uint32_t dimension, const InputMatrix& input, float* d_out_n) {
 		if (input.rows != NRS_NETWORK_INPUT_FLOATS) throw std::runtime_error("NerfNetwork::visualize_activation: input must have 7 rows");
@@ -244,6 +253,55 @@ public:
 
 private:
 	nrs_dataset* m_ds = nullptr;
+};
+
+// Testbed::m_envmap as the training loop uses it (testbed.h: envmap, its loss and optimiser; nrs.h "the environment map"): res_x x res_y RGBA texels trained behind the
+// last sample of every ray.  A fresh map is all zeros.  The learning rate is the caller's schedule (envmap_lr: base.json's envmap block).
+class Envmap {
+public:
+	static nrs_adam_params base_params() { // base.json's envmap optimiser: Ema(0.99) over Adam(0.9, 0.99, 1e-10)
+		nrs_adam_params p{};
+		nrs_envmap_default_adam_params(&p);
+		return p;
+	}
+	static nrs_envmap_accumulate_params accumulate_params(const nrs_ray_loss_params& loss, nrs_loss_type envmap_loss_type = NRS_LOSS_RELATIVE_L2) {
+		return nrs_envmap_accumulate_params{(uint32_t)sizeof(nrs_envmap_accumulate_params), loss.loss_type, (uint32_t)envmap_loss_type, loss.loss_scale,
+		                                    loss.train_in_linear_colors};
+	}
+	// ExponentialDecay(10000, 5000, 0.33) over 1e-2, for the step after steps_done finished ones
+	static float envmap_lr(uint32_t steps_done) { return nrs_exponential_decay_lr(1e-2f, 10000, 5000, 0.33f, steps_done); }
+
+	Envmap(Context& ctx, uint32_t res_x, uint32_t res_y) { check(nrs_envmap_create(ctx.get(), res_x, res_y, nullptr, &m_env), "nrs_envmap_create"); }
+	Envmap(Context& ctx, uint32_t res_x, uint32_t res_y, const nrs_adam_params& params) { check(nrs_envmap_create(ctx.get(), res_x, res_y, &params, &m_env), "nrs_envmap_create"); }
+	~Envmap() { nrs_envmap_destroy(m_env); }
+	Envmap(const Envmap&) = delete;
+	Envmap& operator=(const Envmap&) = delete;
+
+	size_t n_floats() const {
+		uint32_t x = 0, y = 0;
+		check(nrs_envmap_resolution(m_env, &x, &y), "nrs_envmap_resolution");
+		return (size_t)4 * x * y;
+	}
+	void set_texels(const float* texels, bool on_device, void* stream) { check(nrs_envmap_set_texels(m_env, texels, on_device ? 1 : 0, stream), "nrs_envmap_set_texels"); }
+	void get(nrs_envmap_what which, void* h_out) { check(nrs_envmap_get(m_env, which, h_out, n_floats()), "nrs_envmap_get"); }
+	// the EMA (params_inference) or the live texels (params) into d_out [res_y][res_x][4]: what nrs_render_params::d_envmap takes
+	void export_texels(bool ema, float* d_out, void* stream) { check(nrs_envmap_export(m_env, ema ? 1 : 0, d_out, stream), "nrs_envmap_export"); }
+	// per ray slot: the linear background behind the ray (for NerfNetwork::ray_loss_ex) and the lookup's footprint (for accumulate)
+	void background(void* stream, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices, const float* d_rays, const float* d_background,
+	                const float* default_background, float* d_background_linear, int32_t* d_footprint) {
+		check(nrs_envmap_background(m_env, stream, n_rays, d_ray_counter, d_ray_indices, d_rays, d_background, default_background, d_background_linear, d_footprint),
+		      "nrs_envmap_background");
+	}
+	void accumulate(void* stream, const nrs_envmap_accumulate_params& params, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_numsteps_out,
+	                const uint32_t* d_ray_aux, const float* d_background_linear, const int32_t* d_footprint) {
+		check(nrs_envmap_accumulate(m_env, stream, &params, n_rays, d_ray_counter, d_numsteps_out, d_ray_aux, d_background_linear, d_footprint), "nrs_envmap_accumulate");
+	}
+	void step(void* stream, float loss_scale, float learning_rate) { check(nrs_envmap_step(m_env, stream, loss_scale, learning_rate), "nrs_envmap_step"); }
+	uint32_t step() const { return nrs_envmap_step_count(m_env); }
+	nrs_envmap* get() const { return m_env; }
+
+private:
+	nrs_envmap* m_env = nullptr;
 };
 
 // nrs_image_metrics on a caller's reference (d_reference: fp16 or f32 RGBA, linear, premultiplied), and run.py's totals over records that are back on the host

@@ -202,6 +202,21 @@ class AdamParams(C.Structure):
             setattr(self, k, v)
 
 
+def envmap_adam_params():
+    """The optimiser of base.json's envmap block (nrs_envmap_default_adam_params): Adam 0.9 / 0.99 / 1e-10, Ema 0.99; l2_reg never acts (no matrix weights)"""
+    return AdamParams(epsilon=1e-10, l2_reg=0.0, ema_decay=0.99)
+
+
+class EnvmapAccumulateParams(C.Structure):
+    """nrs_envmap_accumulate_params; struct_size is filled in on construction, the envmap's own loss defaults to the reference's RelativeL2 (testbed.cu:2438)"""
+    _fields_ = [("struct_size", C.c_uint32), ("loss_type", C.c_uint32), ("envmap_loss_type", C.c_uint32), ("loss_scale", C.c_float), ("train_in_linear_colors", C.c_uint32)]
+
+    def __init__(self, loss_type=LOSS_L2, envmap_loss_type=LOSS_RELATIVE_L2, loss_scale=128.0, train_in_linear_colors=0):
+        super().__init__()
+        self.struct_size = C.sizeof(EnvmapAccumulateParams)
+        self.loss_type, self.envmap_loss_type, self.loss_scale, self.train_in_linear_colors = int(loss_type), int(envmap_loss_type), float(loss_scale), int(train_in_linear_colors)
+
+
 class TrainingCamera(C.Structure):
     """nrs_training_camera; struct_size is filled in on construction.  Matrices are 3 x 4 column-major like RenderParams.camera_matrix0."""
     _fields_ = [("struct_size", C.c_uint32), ("xform_start", C.c_float * 12), ("xform_end", C.c_float * 12), ("focal_length", C.c_float * 2),
@@ -272,6 +287,10 @@ OPT_MASTER, OPT_M, OPT_V, OPT_STEPS, OPT_EMA, OPT_PARAMS_FP16 = range(6)  # nrs_
 OPT_EXPORT_WEIGHTS, OPT_EXPORT_EMA = 0, 1  # nrs_optimizer_export
 # the schedule of configs/nerf/base.json: ExponentialDecay(decay_start, decay_interval, decay_base) over a learning rate of 1e-2
 BASE_LEARNING_RATE, BASE_DECAY_START, BASE_DECAY_INTERVAL, BASE_DECAY_BASE = 1e-2, 20000, 10000, 0.33
+# the schedule of its envmap block: ExponentialDecay(10000, 5000, 0.33) over 1e-2
+ENVMAP_LEARNING_RATE, ENVMAP_DECAY_START, ENVMAP_DECAY_INTERVAL, ENVMAP_DECAY_BASE = 1e-2, 10000, 5000, 0.33
+ENVMAP_TEXELS, ENVMAP_EMA, ENVMAP_GRADIENT, ENVMAP_CELLS = 0, 1, 2, 3  # nrs_envmap_what
+RAY_AUX_WORDS = 12  # NRS_RAY_AUX_WORDS
 
 # every symbol include/nrs.h declares; tests check the library exports exactly these
 EXPORTS = [
@@ -310,6 +329,8 @@ EXPORTS = [
     "nrs_dataset_error_map_reset", "nrs_error_map_resolution", "nrs_dataset_error_map_set", "nrs_dataset_error_map_get", "nrs_dataset_error_map_accumulate",
     "nrs_dataset_error_map_build_cdfs", "nrs_error_map_cdfs_host", "nrs_dataset_rays_ex",
     "nrs_image_metrics", "nrs_dataset_image_metrics", "nrs_image_metrics_host", "nrs_image_metrics_summary_host",
+    "nrs_envmap_default_adam_params", "nrs_envmap_create", "nrs_envmap_destroy", "nrs_envmap_resolution", "nrs_envmap_set_texels", "nrs_envmap_get", "nrs_envmap_export",
+    "nrs_envmap_background", "nrs_ray_loss_ex", "nrs_envmap_accumulate", "nrs_envmap_step", "nrs_envmap_step_count",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -444,6 +465,22 @@ def load():
         lib.nrs_dataset_image_metrics.argtypes = [P, U32, P, P, C.POINTER(ImageMetricsParams), P, P, P]
         lib.nrs_image_metrics_host.argtypes = [U32, U32, P, P, C.POINTER(ImageMetricsParams), P, P, P]
         lib.nrs_image_metrics_summary_host.argtypes = [P, U32, C.POINTER(MetricsSummary)]
+    if hasattr(lib, "nrs_envmap_create"):  # the trainable environment map (detected by symbol)
+        lib.nrs_envmap_default_adam_params.argtypes = [C.POINTER(AdamParams)]
+        lib.nrs_envmap_default_adam_params.restype = None
+        lib.nrs_envmap_create.argtypes = [P, U32, U32, C.POINTER(AdamParams), C.POINTER(P)]
+        lib.nrs_envmap_destroy.argtypes = [P]
+        lib.nrs_envmap_destroy.restype = None
+        lib.nrs_envmap_resolution.argtypes = [P, C.POINTER(U32), C.POINTER(U32)]
+        lib.nrs_envmap_set_texels.argtypes = [P, P, I, P]
+        lib.nrs_envmap_get.argtypes = [P, I, P, C.c_size_t]
+        lib.nrs_envmap_export.argtypes = [P, I, P, P]
+        lib.nrs_envmap_background.argtypes = [P, P, U32, P, P, P, P, C.POINTER(C.c_float * 3), P, P]
+        lib.nrs_ray_loss_ex.argtypes = [P, P, C.POINTER(RayLossParams), U32, P, P, U32, P, U32, P, U32, I, P, P, P, P, P, P, U32, I, P, P, P, P]
+        lib.nrs_envmap_accumulate.argtypes = [P, P, C.POINTER(EnvmapAccumulateParams), U32, P, P, P, P, P]
+        lib.nrs_envmap_step.argtypes = [P, P, C.c_float, C.c_float]
+        lib.nrs_envmap_step_count.argtypes = [P]
+        lib.nrs_envmap_step_count.restype = U32
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

@@ -1,4 +1,4 @@
-// nrs_api_train.cpp -- the training-ray path behind the C-ABI: nrs_training_samples, nrs_ray_loss.  Everything that can be refused is refused before the first HIP call.
+// nrs_api_train.cpp -- the training-ray path behind the C-ABI: nrs_training_samples, nrs_ray_loss, nrs_ray_loss_ex.  Everything that can be refused is refused before the first HIP call.
 #include "nrs_handles.h"
 #include "nrs_train.h"
 
@@ -40,6 +40,15 @@ int nrs_ray_loss(nrs_model* m, void* stream, const nrs_ray_loss_params* p, uint3
                  const float* d_coords, uint32_t ld_in, const void* d_output_fp16, uint32_t ld_out, int out_layout, const float* d_target_rgba, const float* d_background,
                  const float* d_ray_origins, uint32_t* d_numsteps_out, float* d_coords_out, void* d_dL_doutput_fp16, uint32_t ld_dl, int dl_layout, float* d_loss,
                  uint32_t* d_counter_out) {
+	return nrs_ray_loss_ex(m, stream, p, n_rays, d_ray_counter, d_numsteps, n_samples, d_coords, ld_in, d_output_fp16, ld_out, out_layout, d_target_rgba, d_background,
+	                       d_ray_origins, d_numsteps_out, d_coords_out, d_dL_doutput_fp16, ld_dl, dl_layout, d_loss, d_counter_out, nullptr, nullptr);
+}
+
+// (the messages name nrs_ray_loss for both doors: one body)
+int nrs_ray_loss_ex(nrs_model* m, void* stream, const nrs_ray_loss_params* p, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_numsteps, uint32_t n_samples,
+                    const float* d_coords, uint32_t ld_in, const void* d_output_fp16, uint32_t ld_out, int out_layout, const float* d_target_rgba, const float* d_background,
+                    const float* d_ray_origins, uint32_t* d_numsteps_out, float* d_coords_out, void* d_dL_doutput_fp16, uint32_t ld_dl, int dl_layout, float* d_loss,
+                    uint32_t* d_counter_out, const float* d_background_linear, uint32_t* d_ray_aux) {
 	if (!m || !p || !d_coords_out || !d_dL_doutput_fp16 || !d_counter_out || (n_rays && (!d_numsteps || !d_coords || !d_output_fp16 || !d_target_rgba || !d_numsteps_out)))
 		return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: NULL argument");
 	if (p->struct_size != sizeof(nrs_ray_loss_params)) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: params->struct_size is not sizeof(nrs_ray_loss_params)");
@@ -56,6 +65,7 @@ int nrs_ray_loss(nrs_model* m, void* stream, const nrs_ray_loss_params* p, uint3
 	if (!std::isfinite(p->loss_scale)) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: loss_scale is not finite");
 	if (p->near_distance > 0.f && !d_ray_origins) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: near_distance > 0 needs d_ray_origins");
 	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: more than 2^21 rays (the sample counters are 32 bits wide)");
+	if (((uintptr_t)d_ray_aux & 15u) != 0u) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss_ex: d_ray_aux is not 16-byte aligned");
 	if (n_rays) { // the compaction is not done in place
 		const char *in0 = (const char*)d_coords, *in1 = in0 + (size_t)n_samples * ld_in * sizeof(float);
 		const char *out0 = (const char*)d_coords_out, *out1 = out0 + (size_t)p->max_samples_compacted * ld_in * sizeof(float);
@@ -67,7 +77,7 @@ int nrs_ray_loss(nrs_model* m, void* stream, const nrs_ray_loss_params* p, uint3
 	a.p = *p; a.n_rays = n_rays; a.ray_counter = d_ray_counter; a.numsteps = d_numsteps; a.n_samples = n_samples; a.coords = d_coords; a.ld_in = ld_in;
 	a.output = d_output_fp16; a.ld_out = ld_out; a.out_layout = out_layout; a.target_rgba = d_target_rgba; a.background = d_background; a.origins = d_ray_origins;
 	a.numsteps_out = d_numsteps_out; a.coords_out = d_coords_out; a.dl = d_dL_doutput_fp16; a.ld_dl = ld_dl; a.dl_layout = dl_layout; a.loss = d_loss;
-	a.counter_out = d_counter_out;
+	a.counter_out = d_counter_out; a.background_linear = d_background_linear; a.ray_aux = d_ray_aux;
 	a.ws = n_rays ? m->d_train_ws.get() : nullptr;
 	NRS_LAUNCH(launch_ray_loss(m->dm, a, stream));
 	return NRS_OK;

@@ -86,7 +86,10 @@ __device__ __forceinline__ void read_image2(const float* __restrict__ data, cons
 }
 // read_envmap (envmap.cuh:30-63): spherical coordinates of the direction (acosf / atan2f: the device library's, as sincosf in the thin-lens branch --
 // tolerance, not bits, against the host-compiled reference), bilinear lookup wrapping in x and clamped in y
-__device__ __forceinline__ float4 read_envmap(const float* __restrict__ data, const int32_t* res, f3 dir) {
+// Its two halves, each stated once: the footprint of a direction -- the texel and the bilinear weights, before wrapping and clamping -- and the lookup at a footprint.
+// The render path calls them back to back (read_envmap); the training path keeps the footprint between the background and the envmap's gradient (nrs_envmap.hip).
+struct EnvmapFootprint { int tx, ty; float wx, wy; };
+__device__ __forceinline__ EnvmapFootprint envmap_footprint(const int32_t* res, f3 dir) {
 	const float PI = 3.14159265358979323846f;
 	const f3 d = {dir.z, -dir.x, dir.y};
 	const float theta = acosf(fminf(fmaxf(d.z, -1.0f), 1.0f));
@@ -94,7 +97,11 @@ __device__ __forceinline__ float4 read_envmap(const float* __restrict__ data, co
 	const float cyl_x = theta / PI, cyl_y = (phi / (2.0f * PI) + 0.5f);
 	const float fx = cyl_y * (float)(res[0] - 1), fy = cyl_x * (float)(res[1] - 1);
 	const int tx = (int)fx, ty = (int)fy;
-	const float wx = fx - (float)tx, wy = fy - (float)ty;
+	return EnvmapFootprint{tx, ty, fx - (float)tx, fy - (float)ty};
+}
+__device__ __forceinline__ float4 envmap_lookup(const float* __restrict__ data, const int32_t* res, const EnvmapFootprint& f) {
+	const int tx = f.tx, ty = f.ty;
+	const float wx = f.wx, wy = f.wy;
 	auto wrapx = [&](int x) { return x < 0 ? x + res[0] : (x >= res[0] ? x - res[0] : x); };
 	const int x0 = wrapx(tx), x1 = wrapx(tx + 1), y0 = max(min(ty, res[1] - 1), 0), y1 = max(min(ty + 1, res[1] - 1), 0);
 	const float4* q = reinterpret_cast<const float4*>(data);
@@ -103,6 +110,7 @@ __device__ __forceinline__ float4 read_envmap(const float* __restrict__ data, co
 	return make_float4(((w00 * a.x + w10 * b.x) + w01 * c.x) + w11 * e.x, ((w00 * a.y + w10 * b.y) + w01 * c.y) + w11 * e.y,
 	                   ((w00 * a.z + w10 * b.z) + w01 * c.z) + w11 * e.z, ((w00 * a.w + w10 * b.w) + w01 * c.w) + w11 * e.w);
 }
+__device__ __forceinline__ float4 read_envmap(const float* __restrict__ data, const int32_t* res, f3 dir) { return envmap_lookup(data, res, envmap_footprint(res, dir)); }
 
 // pixel_to_ray (common_device.cuh:245-295): origin and UN-normalised direction of pixel (x, y) through the camera of its ray time
 // (init_rays_with_payload_kernel_nerf, tn:2551-2567).  offset = ld_random_pixel_offset(snap ? 0 : spp), computed once per thread by the caller.

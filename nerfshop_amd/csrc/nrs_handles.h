@@ -1,4 +1,4 @@
-// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, dataset, optimiser), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
+// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, dataset, optimiser, environment map), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
 // work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp, nrs_api_selection.cpp) includes
 // this header alone.  Host-only C++17: no .hip / .cuh includes it.
 #pragma once
@@ -246,4 +246,14 @@ struct nrs_optimizer {
 	uint32_t step_count = 0;
 	uint32_t variant = 0;               // NRS_OPTIMIZER_VARIANT at creation (measurements: nrs_optimizer.h)
 	bool have_weights = false;
+};
+
+// The trainable environment map (nrs_api_envmap.cpp, nrs_envmap.hip).  The texels are the master weights of its own unbound optimiser: live = NRS_OPT_MASTER, EMA = NRS_OPT_EMA.
+struct nrs_envmap {
+	nrs_ctx* ctx = nullptr;
+	uint32_t res_x = 0, res_y = 0;
+	uint32_t n = 0;                              // 4 * res_x * res_y
+	nrs_optimizer* opt = nullptr;                // n parameters, n_matrix = 0; owned
+	nrs::DeviceBuffer<float> d_grad;             // [n]: zero between steps (the step clears what it reads)
+	nrs::DeviceBuffer<unsigned long long> d_cells; // [n]: int64 fixed point, 2^-32 per unit; zero between steps
 };

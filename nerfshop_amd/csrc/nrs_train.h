@@ -8,6 +8,7 @@
 namespace nrs {
 
 constexpr uint32_t kTrainMaxRays = 1u << 21; // 2^21 rays x NERF_STEPS = 2^31 samples: every sum of counts fits 32 bits
+constexpr uint32_t kRayAuxWords = 12;        // nrs_ray_loss_ex's record per slot: g[3], T, target[3], C[3], n, M
 constexpr uint32_t kTrainScanTile = 1024;    // rays per tile of the scan over the per-ray counts
 inline uint32_t train_scan_tiles(uint32_t n_rays) { return (n_rays + kTrainScanTile - 1u) / kTrainScanTile; }
 // what the scan keeps behind a view's per-ray arrays: two sums per tile, then the two totals
@@ -77,6 +78,8 @@ struct RayLossArgs {
 	float* loss;                 // nullable
 	uint32_t* counter_out;
 	uint32_t* ws;                // RayLossWs: train_ws_words<RayLossWs>(n_rays) words (NULL when n_rays == 0)
+	const float* background_linear; // nullable: [n_rays][3] by slot, replaces srgb_to_linear(background) (nrs_ray_loss_ex)
+	uint32_t* ray_aux;           // nullable: [n_rays][kRayAuxWords], 16-byte aligned (nrs_ray_loss_ex)
 };
 
 int launch_training_samples(const DeviceModel& m, const TrainSamplesArgs& a, void* stream);

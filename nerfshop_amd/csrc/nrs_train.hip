@@ -19,6 +19,7 @@
 #include "nrs_vec.cuh"
 #include "nrs_grid_math.cuh"
 #include "nrs_shade.cuh"
+#include "nrs_loss.cuh"
 #include "nrs_scan.cuh"
 
 namespace nrs {
@@ -213,29 +214,6 @@ __device__ __forceinline__ float network_to_rgb_derivative(float v, uint32_t act
 		default: return 1.0f;
 	}
 }
-// common_device.cuh:31-37, :55-61, with powf: once per ray, and the loss is compared more tightly than a displayed colour
-__device__ __forceinline__ float train_srgb_to_linear(float s) { return s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f); }
-__device__ __forceinline__ float train_linear_to_srgb(float l) { return l < 0.0031308f ? 12.92f * l : 1.055f * powf(l, 0.41666f) - 0.055f; }
-
-// loss_and_gradient (tn:173-185) of one channel: the seven functions of tn:103-171, Huber with alpha = 1
-__device__ __forceinline__ void loss_and_gradient(uint32_t type, float target, float pred, float& loss, float& grad) {
-	const float diff = pred - target;
-	switch (type) {
-		case NRS_LOSS_RELATIVE_L2: { const float f = 1.0f / (pred * pred + 1e-2f); loss = diff * diff * f; grad = 2.0f * diff * f; break; }
-		case NRS_LOSS_L1: loss = fabsf(diff); grad = copysignf(1.0f, diff); break;
-		case NRS_LOSS_MAPE: { const float f = 1.0f / (fabsf(pred) + 1e-2f); loss = fabsf(diff) * f; grad = copysignf(f, diff); break; }
-		case NRS_LOSS_SMAPE: { const float f = 1.0f / (0.5f * (fabsf(pred) + fabsf(target)) + 1e-2f); loss = fabsf(diff) * f; grad = copysignf(f, diff); break; }
-		case NRS_LOSS_HUBER: {
-			const float ad = fabsf(diff);
-			loss = ad > 1.0f ? ad - 0.5f : 0.5f * diff * diff;
-			grad = ad > 1.0f ? (diff > 0 ? 1.0f : -1.0f) : diff;
-			break;
-		}
-		case NRS_LOSS_LOG_L1: { const float div = fabsf(diff) + 1.0f; loss = logf(div); grad = copysignf(1.0f / div, diff); break; }
-		default: loss = diff * diff; grad = 2.0f * diff; break; // L2
-	}
-}
-
 // the four raw outputs of sample s
 struct RawOut { float v[4]; };
 __device__ __forceinline__ RawOut load_raw(const __half* __restrict__ out, uint32_t ld, int layout, size_t s) {
@@ -280,7 +258,11 @@ __device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uin
 	// tn:1789-1828
 	const nrs_ray_loss_params& p = a.p;
 	const float* bgp = a.background ? a.background + 3 * (size_t)i : p.background;
-	f3 bg = mk3(train_srgb_to_linear(bgp[0]), train_srgb_to_linear(bgp[1]), train_srgb_to_linear(bgp[2]));
+	f3 bg;
+	if (a.background_linear) { // nrs_ray_loss_ex: what the ray sees behind its last sample, already linear (the environment map over the background, nrs_envmap_background)
+		const float* bl = a.background_linear + 3 * (size_t)i;
+		bg = mk3(bl[0], bl[1], bl[2]);
+	} else bg = mk3(train_srgb_to_linear(bgp[0]), train_srgb_to_linear(bgp[1]), train_srgb_to_linear(bgp[2]));
 	const float* texp = a.target_rgba + 4 * (size_t)i;
 	const float4 tex = make_float4(texp[0], texp[1], texp[2], texp[3]);
 	f3 target;
@@ -306,6 +288,12 @@ __device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uin
 	ws.C[0][i] = C.x; ws.C[1][i] = C.y; ws.C[2][i] = C.z;
 	ws.g[0][i] = gx; ws.g[1][i] = gy; ws.g[2][i] = gz;
 	ws.loss[i] = sum3(lx, ly, lz) / 3.0f / (float)a.n_rays;
+	if (a.ray_aux) { // nrs_ray_loss_ex: the slot's record, kRayAuxWords words (g, T | target, C.x | C.yz, n, M)
+		float4* aux = reinterpret_cast<float4*>(a.ray_aux + kRayAuxWords * (size_t)i);
+		aux[0] = make_float4(gx, gy, gz, T);
+		aux[1] = make_float4(target.x, target.y, target.z, C.x);
+		aux[2] = make_float4(C.y, C.z, __uint_as_float(n), __uint_as_float(M));
+	}
 }
 
 // ---- one lane per sample -------------------------------------------------------------------------------------------------------------------------------------

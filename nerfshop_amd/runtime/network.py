@@ -194,13 +194,15 @@ class NerfNetwork(Handle):
                 torch.empty(n, dtype=torch.float32, device=device), torch.empty(1, dtype=torch.int32, device=device))
 
     def ray_loss(self, stream, params, numsteps, coords, output, target_rgba, background=None, ray_origins=None, ray_counter=None, n_rays=None,
-                 out=None, dl_planes=False):
+                 out=None, dl_planes=False, background_linear=None, aux=None):
         """compute_loss_kernel_train_nerf (nrs_ray_loss): composite the samples of every ray, take the loss against target_rgba and write its gradient, compacted.
         params: RayLossParams (max_samples_compacted set).  numsteps [n_rays, 2] u32-as-int32 (count, base); coords [n_samples, >= 7] f32; output fp16 as
         inference wrote it ([16, n_el] or [n_samples, 16]); target_rgba [n_rays, 4] f32; background [n_rays, 3] / ray_origins [n_rays, 3] f32 or None; ray_counter: a
         one-element int32 CUDA tensor (live rays) or None; n_rays: the normaliser, default numsteps.shape[0].
         Returns (numsteps_out [n_rays, 2] int32, coords_out [max, ld] f32, dL_doutput fp16 [max, 16] or -- dl_planes -- [16, max], loss [n_rays] f32, counter [1] int32);
-        `out` may bring these five tensors to reuse.  Rows 4..15 of dL_doutput are not written (a fresh one is zero)."""
+        `out` may bring these five tensors to reuse.  Rows 4..15 of dL_doutput are not written (a fresh one is zero).
+        background_linear [n_rays, 3] f32 by slot (Envmap.background) replaces the linearised background; aux [n_rays, 12] int32 receives the slot's record (g[3], T,
+        target[3], C[3] as float bits, n, M).  Either goes through nrs_ray_loss_ex; with both None this is nrs_ray_loss."""
         if not isinstance(params, _abi.RayLossParams):
             raise NrsError("ray_loss: params must be a RayLossParams")
         _require_cuda(numsteps, torch.int32, "numsteps")
@@ -237,10 +239,22 @@ class NerfNetwork(Handle):
         if tuple(numsteps_out.shape) != tuple(numsteps.shape) or tuple(coords_out.shape) != (cap, ld_in) or loss.numel() < numsteps.shape[0] or counter.numel() < 1:
             raise NrsError("ray_loss: an output tensor has the wrong shape")
         dl_layout, ld_dl = self._out_layout(dl, cap)
-        check(self.lib.nrs_ray_loss(self.h, _stream_handle(stream), C.byref(params), n, _ptr(ray_counter), numsteps.data_ptr(),
-                                    n_samples, coords.data_ptr(), ld_in, output.data_ptr(), ld_out, layout, target_rgba.data_ptr(),
-                                    _ptr(background), _ptr(ray_origins),
-                                    numsteps_out.data_ptr(), coords_out.data_ptr(), dl.data_ptr(), ld_dl, dl_layout, loss.data_ptr(), counter.data_ptr()))
+        args = (self.h, _stream_handle(stream), C.byref(params), n, _ptr(ray_counter), numsteps.data_ptr(),
+                n_samples, coords.data_ptr(), ld_in, output.data_ptr(), ld_out, layout, target_rgba.data_ptr(),
+                _ptr(background), _ptr(ray_origins),
+                numsteps_out.data_ptr(), coords_out.data_ptr(), dl.data_ptr(), ld_dl, dl_layout, loss.data_ptr(), counter.data_ptr())
+        if background_linear is None and aux is None:
+            check(self.lib.nrs_ray_loss(*args))
+            return numsteps_out, coords_out, dl, loss, counter
+        if background_linear is not None:
+            _require_cuda(background_linear, torch.float32, "background_linear")
+            if tuple(background_linear.shape) != (numsteps.shape[0], 3):
+                raise NrsError("ray_loss: background_linear must be [n_rays, 3]")
+        if aux is not None:
+            _require_cuda(aux, torch.int32, "aux")
+            if tuple(aux.shape) != (numsteps.shape[0], _abi.RAY_AUX_WORDS):
+                raise NrsError("ray_loss: aux must be [n_rays, 12] int32")
+        check(self.lib.nrs_ray_loss_ex(*args, _ptr(background_linear), _ptr(aux)))
         return numsteps_out, coords_out, dl, loss, counter
 
     def training_samples(self, stream, rays, jitter, cone_angle_constant, max_samples, ld=7):

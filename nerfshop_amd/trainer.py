@@ -1,4 +1,5 @@
-"""The reference's training loop from the ray on, end to end on the device: samples -> inference -> ray loss -> backward -> the fused optimiser step.
+"""The reference's training loop from the ray on, end to end on the device: samples -> inference -> ray loss -> backward -> the fused optimiser step,
+with an optional trained environment map behind the last sample (Trainer(..., envmap=(256, 128))).
 
     trainer = Trainer(ctx, synth.model_desc(1), seed=11, density_grid=grid)      # or no grid: the first update_density_grid() makes one from the network
     for i in range(n_steps):
@@ -53,8 +54,18 @@ class Trainer:
 
     def __init__(self, ctx, desc, seed=1337, weights=None, density_grid=None, max_samples=1 << 18, max_cascade=0, cone_angle_constant=0.0, adam=None,
                  loss_params=None, learning_rate=_abi.BASE_LEARNING_RATE, decay=(_abi.BASE_DECAY_START, _abi.BASE_DECAY_INTERVAL, _abi.BASE_DECAY_BASE),
-                 density_grid_decay=0.95):
+                 density_grid_decay=0.95, envmap=None, envmap_loss_type=_abi.LOSS_RELATIVE_L2, envmap_learning_rate=_abi.ENVMAP_LEARNING_RATE,
+                 envmap_decay=(_abi.ENVMAP_DECAY_START, _abi.ENVMAP_DECAY_INTERVAL, _abi.ENVMAP_DECAY_BASE)):
+        """envmap: None, a runtime.Envmap or a (res_x, res_y) pair: an environment map trained next to the network (m_envmap) -- the background behind a ray's last
+        sample, with base.json's envmap loss (RelativeL2) and its own schedule, ExponentialDecay(10000, 5000, 0.33) over 1e-2, on training_step."""
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
+        if envmap is not None and not isinstance(envmap, runtime.Envmap):
+            envmap = runtime.Envmap(ctx, int(envmap[0]), int(envmap[1]))
+        if envmap is not None and envmap.ctx is not ctx:
+            raise NrsError("Trainer: the envmap belongs to another context")
+        self.envmap, self.envmap_loss_type = envmap, int(envmap_loss_type)
+        self.envmap_learning_rate, self.envmap_decay = float(envmap_learning_rate), tuple(envmap_decay)
+        self._envmap_bufs = None
         self.network = runtime.NerfNetwork(ctx, desc, cell_cache_bytes=0)  # no cell-record cache: it would be rebuilt after every step
         self.optimizer = runtime.Optimizer(ctx, network=self.network, params=adam)
         n = self.optimizer.n_params
@@ -83,6 +94,10 @@ class Trainer:
     def current_learning_rate(self):
         start, interval, base = self.decay
         return runtime.exponential_decay_lr(self.training_step, self.learning_rate, start, interval, base)
+
+    def current_envmap_learning_rate(self):
+        start, interval, base = self.envmap_decay
+        return runtime.exponential_decay_lr(self.training_step, self.envmap_learning_rate, start, interval, base)
 
     def update_density_grid(self, stream=None):
         """training_prep_nerf (src/testbed_nerf.cu:4460-4468): uniform samples over every cell while the training step is below 256, a quarter uniform plus a quarter
@@ -118,12 +133,25 @@ class Trainer:
         bg = None if background is None else background.index_select(0, slots)
         if self._loss_bufs is None or self._loss_bufs[0].shape[0] != n_rays:
             self._loss_bufs = net.ray_loss_buffers(n_rays, self.max_samples, device=rays.device)
-        _, coords_out, dl, loss, _ = net.ray_loss(None, self.loss_params, numsteps, coords, self._out16, target, background=bg, ray_counter=counters[:1],
-                                                  out=self._loss_bufs)
+        env, bg_linear, aux = self.envmap, None, None
+        if env is not None:  # the background the ray sees through the envmap's live texels, and the lookup's footprint for the gradient
+            if self._envmap_bufs is None or self._envmap_bufs[0].shape[0] != n_rays:
+                self._envmap_bufs = (torch.zeros((n_rays, 3), dtype=torch.float32, device=rays.device), torch.zeros((n_rays, 4), dtype=torch.int32, device=rays.device),
+                                     torch.zeros((n_rays, _abi.RAY_AUX_WORDS), dtype=torch.int32, device=rays.device))
+            aux = self._envmap_bufs[2]
+            p = self.loss_params
+            bg_linear, footprint = env.background(rays, ray_indices, counters[:1], background=bg, default_background=tuple(p.background), out=self._envmap_bufs[:2])
+        numsteps_out, coords_out, dl, loss, _ = net.ray_loss(None, self.loss_params, numsteps, coords, self._out16, target, background=bg, ray_counter=counters[:1],
+                                                             out=self._loss_bufs, background_linear=bg_linear, aux=aux)
         if after_loss is not None:
             after_loss(counters[:1], ray_indices, loss)
+        if env is not None:
+            acc = _abi.EnvmapAccumulateParams(p.loss_type, self.envmap_loss_type, p.loss_scale, p.train_in_linear_colors)
+            env.accumulate(acc, counters[:1], numsteps_out, aux, bg_linear, footprint, n_rays=n_rays)
         net.backward(None, coords_out, dl, self.grad, None, accumulate=True)
         self.optimizer.step(self.grad, loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate(), zero_grad=True)
+        if env is not None:
+            env.step(loss_scale=float(self.loss_params.loss_scale), lr=self.current_envmap_learning_rate())
         self.training_step += 1
         return loss.sum()
 
@@ -185,6 +213,8 @@ class Trainer:
             net.set_params_device(self.optimizer.export_fp16(_abi.OPT_EXPORT_EMA))
             net.set_density_grid(self.network.get_density_grid())
             torch.cuda.current_stream(f"cuda:{self.ctx.device}").synchronize()
+        # the envmap as the testbed renders it: the EMA texels with ema=True, the live ones otherwise (params_inference() / params())
+        self._eval_testbed.envmap = None if self.envmap is None else self.envmap.export(ema=bool(ema))
         return self._eval_testbed.evaluate(net, dataset, **kw)
 
     def fit(self, dataset, n_steps, n_rays=4096, grid_every=16, snap=True, random_bg=True, error_map=None):
