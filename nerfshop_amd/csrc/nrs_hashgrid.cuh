@@ -33,12 +33,14 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 enum { KIND_DENSE = 0, KIND_HASHED = 1, KIND_MIXED = 2, KIND_RECORD = 3, KIND_SPARSE = 4, KIND_SKIP = 5 };
 
+constexpr int kRollRecordLevels = 12; // the level plan of rolling_eval_sixteen: base.json's table under the default cell-cache budget (levels 0..11 records, 12..15 hashed)
 // Per-block model state in LDS: weight fragments, kind of each level pair (the level table itself is read with scalar loads).
 struct ModelLds {
 	half8 w[kNumFrags * 64];
 	uint32_t kinds[8];        // kind of the level pair (2 it, 2 it + 1): both records / both hashed / both dense, else KIND_MIXED
 	uint32_t kinds_native[8]; // the kinds without the cell records (samples outside [0,1]^3 take these)
 	uint32_t one_line;        // NRS_DEBUG & 1
+	uint32_t rolling;         // the level plan is "kRollRecordLevels record levels, then hashed ones" (rolling_eval_sixteen), and no measurement knob changes the kinds
 };
 // Per-wave feature slab: feat[it][sel][lane], sel 0 = the lane's own sample, 1 = its partner's (lane ^ 32) sample.
 struct FeatLds { uint32_t feat[8][2][64]; };
@@ -57,7 +59,15 @@ __device__ __forceinline__ void stage_model_to_lds(const DeviceModel& m, ModelLd
 		// attributed level pair by level pair (profiles/r06_garden_levels.md).  Pictures are wrong; a production process cannot set it (dev_knob).
 		if ((dbg >> 8) & (1u << threadIdx.x)) s.kinds[threadIdx.x] = s.kinds_native[threadIdx.x] = KIND_SKIP;
 	}
-	if (threadIdx.x == 0) s.one_line = dbg & 1u;
+	if (threadIdx.x == 0) {
+		s.one_line = dbg & 1u;
+		uint32_t rolling = (dbg & 0xff01u) == 0u ? 1u : 0u;
+		for (uint32_t l = 0; l < kLevels; ++l) {
+			const bool want_record = l < (uint32_t)kRollRecordLevels;
+			if (want_record ? m.levels[l].cached != 1u : (m.levels[l].cached != 0u || m.levels[l].hashed == 0u)) rolling = 0u;
+		}
+		s.rolling = rolling;
+	}
 	__syncthreads();
 }
 
@@ -403,6 +413,43 @@ __device__ __forceinline__ void hashed_eval_four(const GridView& gv, const Level
 	f3_ = zero_if<ZERO>(!act, interpolate<NETACC>(cc(lp3, q), v3));
 }
 
+// ALL SIXTEEN levels of one sample as a pipeline over LEVELS, four deep, for the level plan of base.json's default cell-cache budget: kRollRecordLevels record levels, then
+// hashed ones (ModelLds::rolling says whether the model has it).  The blocks above issue four levels, wait for all of them and interpolate with nothing in flight: four fully
+// exposed trips per gather.  Here the prologue issues levels 0..3, and step L consumes level L and issues level L + 4 into the eight registers that level L has just freed:
+// 32 loaded dwords stay in flight throughout (the register peak of one block), and every load behind the prologue has three levels' interpolation between its issue and its
+// first use.  Straight-line code, no loop: the waits are partial counts on the in-order vector-memory counter (a back edge would make each a wait for everything).
+// Per (sample, level) the operations and the loaded words are those of record_eval_four / hashed_eval_four<INCUBE>: the same bits.  The weights are recomputed behind an opaque
+// copy of the position at every step, as there.  Slab layout as encode_to_lds writes it: the pair's first feature waits in one register for its second.
+template <int L> struct LevelTag { static constexpr int value = L; };
+template <bool NETACC = false, bool ZERO = true>
+__device__ __forceinline__ void rolling_eval_sixteen(const GridView& gv, const LevelParams* __restrict__ lv, FeatLds& fl, int lane, int g, f3 pos, bool act) {
+	f3 q = act ? pos : mk3(0.f, 0.f, 0.f);
+	uint32_t v[4][8];
+	uint32_t held = 0u;
+	auto issue = [&](auto tag) {
+		constexpr int L = decltype(tag)::value;
+		if (L < kRollRecordLevels) issue_record_loads(gv, lv[L], cell_coords_incube(lv[L], q), v[L & 3]);
+		else issue_gathers<true>(gv, lv[L], cell_coords_incube(lv[L], q), v[L & 3]);
+	};
+	auto step = [&](auto tag) {
+		constexpr int L = decltype(tag)::value;
+		asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z)); // the weights are recomputed, not carried across the loads
+		const uint32_t f = zero_if<ZERO>(!act, interpolate<NETACC>(cell_coords_incube(lv[L], q), v[L & 3]));
+		if constexpr (L + 4 < (int)kLevels) issue(LevelTag<L + 4>{});
+		if (L & 1) {
+			fl.feat[L >> 1][0][lane] = g ? f : held;
+			fl.feat[L >> 1][1][lane ^ 32] = g ? held : f;
+		} else {
+			held = f;
+		}
+	};
+	issue(LevelTag<0>{}); issue(LevelTag<1>{}); issue(LevelTag<2>{}); issue(LevelTag<3>{});
+	step(LevelTag<0>{}); step(LevelTag<1>{}); step(LevelTag<2>{}); step(LevelTag<3>{});
+	step(LevelTag<4>{}); step(LevelTag<5>{}); step(LevelTag<6>{}); step(LevelTag<7>{});
+	step(LevelTag<8>{}); step(LevelTag<9>{}); step(LevelTag<10>{}); step(LevelTag<11>{});
+	step(LevelTag<12>{}); step(LevelTag<13>{}); step(LevelTag<14>{}); step(LevelTag<15>{});
+}
+
 // One level of one sample, kind decided at run time (wave-uniform): the pairs whose two levels are of different kinds (the one
 // dense | hashed pair of a model without cell records, a records | no-records boundary at an odd level) come here, level after level.
 template <bool NETACC = false, bool ZERO = true>
@@ -434,10 +481,19 @@ __device__ __forceinline__ uint32_t level_eval_one(const GridView& gv, const Lev
 // same bits as before: the arithmetic per (sample, level) did not change.  The slab layout the MLP reads is unchanged too:
 // feat[it][0][l] = level 2 it + g(l) of lane l's sample, feat[it][1][l] = the same level of lane (l ^ 32)'s sample; so the level
 // of the lane's own parity goes to [0][lane] and the other one to [1][lane ^ 32] (a conflict-free permutation of the banks).
-template <bool NETACC = false, bool QUADS = false, bool ZERO = true, int GATE = 0> // (GATE: 0, or the largest number of L2 phases -- trailing hashed level pairs -- to gate)
+// ROLL: the default level plan's gather as one rolling pipeline over the sixteen levels (rolling_eval_sixteen) where the wave can take it; everything else runs the loop below.
+template <bool NETACC = false, bool QUADS = false, bool ZERO = true, int GATE = 0, bool ROLL = false> // (GATE: 0, or the largest number of L2 phases -- trailing hashed level pairs -- to gate)
 __device__ __forceinline__ void encode_to_lds(const GridView& gv, const LevelParams* __restrict__ lv, const ModelLds& ml, FeatLds& fl, int lane, int g, f3 pos, bool act) {
+	static_assert(!ROLL || (QUADS && GATE == 0), "the rolling gather replaces the four-level blocks of the ungated kernel");
 	// the records cover [0,1]^3; a wave with a sample outside it (a warped sample of an edit, rarely) gathers the native way
 	const bool outside = __any(act && outside_unit_cube(pos));
+	if (ROLL && !outside && __builtin_amdgcn_readfirstlane(ml.rolling) != 0u) {
+		rolling_eval_sixteen<NETACC, ZERO>(gv, lv, fl, lane, g, pos, act);
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (as at the end of the loop below)
+		__builtin_amdgcn_wave_barrier();
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		return;
+	}
 	const uint32_t* kinds = outside ? ml.kinds_native : ml.kinds;
 	const bool one_line = __builtin_amdgcn_readfirstlane(ml.one_line) != 0u; // profiling (NRS_DEBUG & 1): every gather of a wave hits one 128-byte line
 	int it = 0, it_end = 8;
@@ -583,10 +639,10 @@ __device__ __forceinline__ void level_input_gradient(const GridView& gv, const L
 }
 
 // (the encoding's NUM dispatcher; what NUM means: nrs_mlp.cuh)
-template <int NUM, bool QUADS = false, bool ZERO = true, int GATE = 0>
+template <int NUM, bool QUADS = false, bool ZERO = true, int GATE = 0, bool ROLL = false>
 __device__ __forceinline__ void encode_num(uint32_t nm, const GridView& gv, const LevelParams* __restrict__ lv, const ModelLds& ml, FeatLds& fl, int lane, int g, f3 pos, bool act) {
-	if (NUM == kNumRuntime ? (nm & 1u) != 0u : (NUM & 1) != 0) encode_to_lds<true, QUADS, ZERO, GATE>(gv, lv, ml, fl, lane, g, pos, act);
-	else encode_to_lds<false, QUADS, ZERO, GATE>(gv, lv, ml, fl, lane, g, pos, act);
+	if (NUM == kNumRuntime ? (nm & 1u) != 0u : (NUM & 1) != 0) encode_to_lds<true, QUADS, ZERO, GATE, ROLL>(gv, lv, ml, fl, lane, g, pos, act);
+	else encode_to_lds<false, QUADS, ZERO, GATE, ROLL>(gv, lv, ml, fl, lane, g, pos, act);
 }
 
 } // namespace nrs

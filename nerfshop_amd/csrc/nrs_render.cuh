@@ -49,6 +49,9 @@ constexpr int kTeamMax = 4; // the widest lane team of the automatic schedule (e
 #ifndef NRS_MEASURE
 #define NRS_MEASURE 0
 #endif
+#ifndef NRS_ROLL_PROF
+#define NRS_ROLL_PROF 0 // (measurement builds: the rolling gather in the wave log's PROF instantiations too, see render_body's kRoll)
+#endif
 constexpr uint32_t kRefillWhenIdle = 64;
 // (Round 6 measured the middle ground once more on the automatic schedule: idle lanes refilled in place from 16 / 32 / 48 idle lanes while the queue has packets, instead of
 // re-teaming the survivors of a thinned generation: lego + cage 12.5 -> 11.4 / 11.4 / 11.8, varied 11.2 -> 9.7 / 9.1 / 9.8 Gsamples/s; profiles/r06/ab_refill_*.txt.)
@@ -179,6 +182,10 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 	// four levels per round trip in the gathers (encode_to_lds QUADS): the automatic schedule's instantiations with the default or the fully tiny-cuda-nn roundings -- since
 	// round 6 the membrane instantiation too (both of its gathers: 9.68 -> 10.06 Gsamples/s, same registers; profiles/r06/ab_poisson_quads.txt)
 	constexpr bool kQuads = TEAM == 0 && !EXTRA && NUM >= 0;
+	// the rolling gather of the default level plan (encode_to_lds ROLL) on the rows that gather four levels per trip and hold it in the parent's registers: not the gated kernel
+	// (it keeps the loop), not the membrane rows (scratch 40 -> 1120 bytes at 128 VGPRs, 147 -> 168 VGPRs + 960 bytes in the 12-wave build) and not the wave log's PROF twins
+	// (scratch 208 -> 224 bytes; -DNRS_ROLL_PROF=1 builds them with it to measure the gather's share of the new path: profiles/gather_rolling.md)
+	constexpr bool kRoll = kQuads && !kX.gate && !POISSON && (!PROF || NRS_ROLL_PROF);
 	constexpr int GATE = kX.gate ? (int)kGateMaxPhases : 0; // the plain kernel with the L2 phase gate on the four finest hashed levels (encode_to_lds): cone-stepping scenes
 	// The two argument structs (~1.3 KB of wave-uniform values) live in the kernel-argument segment and are read with scalar loads.
 	// Left alone, the compiler hoists every such load out of the frame loop and then spills ~150 scalar registers into VGPR lanes
@@ -585,9 +592,9 @@ __device__ __forceinline__ void render_body(const DeviceModel& m_arg, const Rend
 		// ---- gather: own sample (block g) and the partner lane's sample (block 1-g), levels 2*it+g ----
 #if NRS_MEASURE == 3
 		{ f3 wp2 = wpos; asm volatile("" : "+v"(wp2.x), "+v"(wp2.y), "+v"(wp2.z));
-		  encode_num<NUM, kQuads>(nm, gv, m2.levels, sm.ml, fl, lane, g, wp2, act); }
+		  encode_num<NUM, kQuads, true, 0, kRoll>(nm, gv, m2.levels, sm.ml, fl, lane, g, wp2, act); }
 #endif
-		encode_num<NUM, kQuads, false, GATE>(nm, gv, m2.levels, sm.ml, fl, lane, g, wpos, act); // (four record levels in flight: the hybrid instantiation has the registers; features of idle lanes are never looked at: not zeroed)
+		encode_num<NUM, kQuads, false, GATE, kRoll>(nm, gv, m2.levels, sm.ml, fl, lane, g, wpos, act); // (four record levels in flight: the hybrid instantiation has the registers; features of idle lanes are never looked at: not zeroed)
 		NRS_PHASE(4); // SH + MLP
 		const f3 pdir = mk3(xchg32(wdir.x), xchg32(wdir.y), xchg32(wdir.z));
 		half8 sh_own, sh_par;
