@@ -839,8 +839,8 @@ int  nrs_selection_fine_mesh(nrs_ctx* ctx, void* stream, nrs_selection* sel, int
 /* The two steps between "rays + the colours they should have" and nrs_network_backward: generate_training_samples_nerf (src/testbed_nerf.cu:1087, from :1188 on: everything
  * after the ray exists) and compute_loss_kernel_train_nerf (:1685-1985) with the seven losses of :103-171.  Callers detect these entry points by symbol (dlsym);
  * NRS_ABI_VERSION is unchanged because no existing layout changes.  The rays themselves -- image / pixel selection, lens distortion, rolling shutter -- come from a
- * dataset (nrs_dataset_rays, below) or from the caller.  The envmap and its gradient are nrs_envmap_*'s and nrs_ray_loss_ex's, further down.  Not here: exposure and
- * its gradient, the error map and sharpness, max_level_rand_training, image / pixel PDFs (img_pdf = xy_pdf = 1), fill_rollover_and_rescale
+ * dataset (nrs_dataset_rays, below) or from the caller.  The envmap and its gradient are nrs_envmap_*'s and nrs_ray_loss_ex's, further down; per-image exposure enters
+ * through the target colour alone and is nrs_exposure_*'s, at the end.  Not here: the error map and sharpness, max_level_rand_training, image / pixel PDFs (img_pdf = xy_pdf = 1), fill_rollover_and_rescale
  * (nrs_network_backward takes any n), the camera-gradient kernels, the distill variants, light-direction models.
  *
  * Both calls are asynchronous on `stream`, never wait for the device and keep their per-ray workspace in the model: it is allocated on the first call of a size and
@@ -991,7 +991,7 @@ size_t   nrs_optimizer_n_params(const nrs_optimizer* opt, size_t* n_matrix);
  * of the pixel's time, lens distortion), the look-ups compute_loss_kernel_train_nerf repeats for a ray's target and background (:1777-1806), the loader's image
  * conversion (from_rgba32, common_device.cuh:513-540; from_fullp, src/nerf_loader.cu:62) and mark_untrained_density_grid (:353-400).  Callers detect these entry
  * points by symbol (dlsym); NRS_ABI_VERSION is unchanged because no existing layout changes.  The error-map CDFs (cdf_img, cdf_x_cond_y) are
- * nrs_dataset_rays_ex's, further down: nrs_dataset_rays is the `cdf == nullptr` branches.  Not here: explicit per-pixel rays (rays_in), the trainable per-pixel distortion map, exposure (the envmap is nrs_envmap_*'s, further down), light directions (a dataset serves
+ * nrs_dataset_rays_ex's, further down: nrs_dataset_rays is the `cdf == nullptr` branches.  Not here: explicit per-pixel rays (rays_in), the trainable per-pixel distortion map (the envmap is nrs_envmap_*'s and per-image exposure nrs_exposure_*'s, further down), light directions (a dataset serves
  * n_extra_dims == 0 models), sharpening and the sharpness map, EXR, the adaptive rays_per_batch of train_nerf (it reads counters back), decoding image files (the
  * Python package does that).
  *
@@ -1211,7 +1211,7 @@ int nrs_image_metrics_summary_host(const nrs_image_metrics_result* h_results, ui
 /* The m_envmap the reference trains next to the network (src/testbed.cu:2427-2441, configs/nerf/base.json:76-103): the background a training ray sees
  * (src/testbed_nerf.cu:1792-1801), its gradient (:1961-1984) and its own optimiser step (:3731-3733, :3766-3768).  What it learns is what nrs_render_params::d_envmap
  * reads.  All of it is new surface, detected by symbol (nrs_envmap_create); nrs_ray_loss, nrs_training_samples, nrs_dataset_rays* and nrs_optimizer_* are what they
- * were.  Not here: per-image exposure and its gradient (:1803, :1946-1959), loading envmap.png, the equirectangular reader, the distill kernels, light-direction
+ * were.  Per-image exposure and its gradient (:1803, :1946-1959) are nrs_exposure_*'s, below.  Not here: loading envmap.png, the equirectangular reader, the distill kernels, light-direction
  * models.  A DELIBERATE OMISSION: rays with zero samples are still not emitted by nrs_training_samples.  The reference's train_envmap switch (:1214) emits them, but
  * its loss kernel returns at :1838 for a ray without compact samples before it reaches the envmap's gradient: the switch changes which slots exist and no gradient.
  *
@@ -1294,6 +1294,99 @@ int      nrs_envmap_accumulate(nrs_envmap* envmap, void* stream, const nrs_envma
                                const uint32_t* d_numsteps_out, const uint32_t* d_ray_aux, const float* d_background_linear, const int32_t* d_footprint);
 int      nrs_envmap_step(nrs_envmap* envmap, void* stream, float loss_scale, float learning_rate);
 uint32_t nrs_envmap_step_count(const nrs_envmap* envmap);
+
+/* ---- per-image exposure: a trained brightness per training view ------------------------------------------------------------------------------------ */
+/* m_nerf.training.optimize_exposure (testbed.h:590, off by default; exposure_l2_reg 0 at :593, n_steps_between_cam_updates 16 at :563; the per-image
+ * AdamOptimizer<Array3f>(1e-3f) of src/testbed.cu:2309, adam_optimizer.h:38-45): three log2 exposures per training image, trained next to the network.  Exposure
+ * enters ONLY through the target colour: exposure_scale = exp(0.6931471805599453f * exposure[img]) multiplies the premultiplied rgb of the target texel in both colour
+ * branches of src/testbed_nerf.cu:1808-1823, so handing nrs_ray_loss_ex a pre-scaled target (scale * rgb, a) is the reference's expression, with the product
+ * rounded once in fp32; and its gradient (:1946-1959) needs nothing beyond what nrs_ray_loss_ex writes into the ray's aux record.  All of it is new surface,
+ * detected by symbol (nrs_exposure_create); NRS_ABI_VERSION is unchanged because no existing layout changes, and nrs_ray_loss_ex is used as it is.  A training view
+ * is DISPLAYED with nrs_tonemap_params::exposure = m_exposure + exposure[view] (src/testbed.cu:2808; one value per view: the tonemap takes a scalar, so a caller with
+ * three different channels picks one or their mean).  Not here: the distortion map, camera extrinsics, focal length (they need the ray-direction gradients).
+ *
+ * An nrs_exposure owns n_images x 3 float exposures (ALL ZERO WHEN FRESH: scale 1), Adam first and second moments of that size, ONE step count shared by all images,
+ * n_images x 3 signed 64-bit fixed-point gradient cells (2^-32 per unit, the envmap's) and a host-side count of the rays accumulated since the last step.
+ * The parameters -- params == NULL, or what nrs_exposure_default_params fills in -- are nrs_exposure_params: beta1 0.9, beta2 0.99, epsilon 1e-8 (adam_optimizer.h:24), l2_reg 0
+ * (exposure_l2_reg), steps_between_updates 16 (n_steps_between_cam_updates: the number of training steps whose gradients one nrs_exposure_step averages).
+ *
+ * nrs_exposure_create / _destroy / _n_images / _step_count.  Creation allocates everything, zeroes it and waits for the device once.
+ * nrs_exposure_set: the exposures from the host, [n_images][3] f32, or all zeros (h_values == NULL); resets the moments, the step count, the cells and the ray count
+ *   (the reference's per-frame reset_state).  Returns when the copy is done.
+ * nrs_exposure_get: synchronous (waits for the device first), n = 3 * n_images elements to the host.  NRS_EXPOSURE_VALUES, _M, _V: f32; NRS_EXPOSURE_CELLS: int64;
+ *   NRS_EXPOSURE_GRADIENT: (float)((double)cell * 2^-32) of the cells as they are now, f32 (zero right after a step).
+ * nrs_exposure_export: asynchronous; the exposures into d_out [n_images][3] f32 on the device.
+ *
+ * nrs_exposure_targets <- :1803-1823, one thread per ray slot s < min(*d_ray_counter, n_rays).  d_pixels [n_rays x 2] u32 (img, pixel) BY RAY INDEX, as
+ *   nrs_dataset_rays writes it; d_target_rgba [n_rays x 4] f32 by ray index; d_target_out [n_rays x 4] f32 BY SLOT (what nrs_ray_loss_ex takes as d_target_rgba);
+ *   d_scale [n_rays x 4] 32-bit words by slot, 16-byte aligned.  i = d_ray_indices[s], img = d_pixels[2 i]; a slot with i >= n_rays or img >= n_images is SKIPPED:
+ *   nothing is written for it and it never deposits (nrs_exposure_accumulate skips i >= n_rays itself and reads the slot's d_scale record as the caller left it: a
+ *   caller whose batches can hold an img >= n_images fills d_scale with 0xff bytes, or zeros, beforehand -- an img word >= n_images is skipped, a zero scale adds 0).
+ *     scale[c] = expf(0.6931471805599453f * exposure[3 img + c]);   d_target_out[4 s ..] = (scale * rgb, a) of d_target_rgba[4 i ..];   d_scale[4 s ..] = (scale.xyz
+ *     as f32 bits, img).  One pass replaces the gather of the target by slot.  The scale is computed once per ray and step and handed to the gradient pass, not
+ *     recomputed (the envmap's footprint follows the same rule), so that pass is a function of float32 products alone.
+ * nrs_exposure_accumulate <- :1946-1959, one thread per slot s < min(*d_ray_counter, n_rays).  A slot that nrs_exposure_targets would not skip deposits iff
+ *   d_numsteps_out[2 s] > 0 (the reference returns at :1838 otherwise).  A STOPPED RAY STILL DEPOSITS, unlike the envmap's rule.  With i = d_ray_indices[s],
+ *   (scale, img) = d_scale[4 s ..] and aux the slot's nrs_ray_loss_ex record, in fp32 without contraction, in this order:
+ *     dgt[c] = -aux.g[c] / pdf,  pdf = d_xy_pdf ? d_xy_pdf[i] : 1 (by ray index; the reference's `/ xy_pdf`, :1948);
+ *     unless train_in_linear_colors:  dgt[c] = dgt[c] / srgb_to_linear_derivative(aux.target[c])  (the aux record's target is the sRGB-encoded one there; the
+ *       derivative is the envmap block's);
+ *     v[c] = (((loss_scale / (float)n_rays) * dgt[c]) * scale[c]) * 0.6931471805599453f   (`/ n_rays`: :1889).
+ *   DEPOSIT (the envmap's rule, the same code): v[c] skipped unless finite and non-zero; clamped to +-512; multiplied by 2^32 (exact); rounded to nearest, ties to even,
+ *   into int64; added to cell 3 img + c.  THE SUM IS FORMED PER WAVE FIRST: image_idx (:1072) hands out images in runs of consecutive ray indices and slots keep the
+ *   input order, so the 64 lanes of a wave almost always share one image.  Each lane quantises; the wave then peels its distinct images one at a time (a ballot of
+ *   the lanes left, the image of the first of them broadcast), sums the quantised values of that image's lanes across the wave and issues ONE no-return 64-bit
+ *   integer atomic per image, channel and wave (none for a zero sum).  Integer sums do not depend on their order: the cells hold the bits one atomic per lane would
+ *   leave, and two calls give the same bits.  DEVIATION: the reference adds floats with atomicAdd; nothing here depends on the order of arrival.
+ *   The call adds n_rays to the handle's ray count; the call that would take the count past 2^21 is refused with NRS_ERR_STATE before any HIP call (2^21 rays of the
+ *   clamp value sum to 2^62: a cell never wraps).  nrs_exposure_step and nrs_exposure_set reset the count.
+ * nrs_exposure_step <- :3885-3911, asynchronous, reads nothing back; one kernel of one workgroup.  Per image and channel, in fp32 in adam_optimizer.h's order:
+ *     g = (float)((double)cell * 2^-32) * pcls + value * l2_reg,   pcls = (float)n_images / loss_scale / (float)steps_between_updates on the host (:3838);
+ *     m = beta1 * m + (1 - beta1) * g;   v = beta2 * v + (1 - beta2) * (g * g);   value -= alr * (m / (sqrtf(v) + epsilon)).
+ *   AN IMAGE WITHOUT RAYS STILL STEPS (g = value * l2_reg, the moments decay, the value moves by momentum), as in the reference -- unlike the network optimiser's
+ *   zero-gradient skip (the optimiser block's RULE).  alr = learning_rate * sqrt(1 - beta2^t) / (1 - beta1^t) with the incremented step count t, evaluated in float64
+ *   on the host and rounded once: A DEVIATION (the reference uses float std::pow; nrs_exponential_decay_lr deviates in the same way).  Then the renormalisation
+ *   (:3900-3909):  mean[c] = (float)(sum_i (double)value[i][c] / (double)n_images), the float64 sum in ONE fixed order, the kernel's and the host twin's (two calls give the same
+ *   bits): 1024 strided partial sums, partial j adding the images j, j + 1024, ... in rising order, then the partials in rising order -- up to 1024 images that is
+ *   the images in their order;
+ *   value[i][c] -= mean[c].  The cells are zeroed and the ray count reset.  ONE STEP COUNT IS SHARED BY ALL IMAGES: A DEVIATION (the reference keeps one optimiser per
+ *   image, and they only diverge through its per-frame reset_state, which is nrs_exposure_set here).  learning_rate is the caller's: the reference passes the network
+ *   optimiser's current one (m_optimizer->learning_rate(), :3897).
+ * nrs_exposure_step_host: the step's host twin on caller arrays, built from the same arithmetic as the kernel (one header, read by both): cells [3 n_images] int64,
+ *   values, m, v [3 n_images] f32 and *step_count are read and written in place (cells become zero, *step_count is incremented).  No device, no handle.
+ *
+ * Refused before any HIP call, NRS_ERR_INVALID_ARG: NULL handles or required pointers (with n_rays > 0); a wrong struct_size; n_images == 0 or above 2^20; betas
+ *   outside [0, 1); a non-positive or non-finite epsilon or loss_scale; a negative or non-finite l2_reg or learning_rate; steps_between_updates == 0; n_rays > 2^21;
+ *   an unknown `which`; n != 3 * n_images in get; a misaligned d_scale or d_ray_aux; d_target_out aliasing d_target_rgba.  n_rays == 0 is NRS_OK (and counts no rays). */
+typedef struct nrs_exposure nrs_exposure;
+typedef enum nrs_exposure_what { NRS_EXPOSURE_VALUES = 0, NRS_EXPOSURE_M = 1, NRS_EXPOSURE_V = 2, NRS_EXPOSURE_CELLS = 3, NRS_EXPOSURE_GRADIENT = 4 } nrs_exposure_what;
+#define NRS_EXPOSURE_MAX_IMAGES (1u << 20)
+typedef struct nrs_exposure_params {
+	uint32_t struct_size;            /* refused unless == sizeof(nrs_exposure_params) */
+	float    beta1, beta2, epsilon;  /* 0.9, 0.99, 1e-8 */
+	float    l2_reg;                 /* exposure_l2_reg: 0 */
+	uint32_t steps_between_updates;  /* n_steps_between_cam_updates: 16 */
+} nrs_exposure_params;
+typedef struct nrs_exposure_accumulate_params {
+	uint32_t struct_size;            /* refused unless == sizeof(nrs_exposure_accumulate_params) */
+	float    loss_scale;             /* the ray loss's */
+	uint32_t train_in_linear_colors; /* the ray loss's */
+} nrs_exposure_accumulate_params;
+void     nrs_exposure_default_params(nrs_exposure_params* out);
+int      nrs_exposure_create(nrs_ctx* ctx, uint32_t n_images, const nrs_exposure_params* params, nrs_exposure** out);
+void     nrs_exposure_destroy(nrs_exposure* exposure);
+uint32_t nrs_exposure_n_images(const nrs_exposure* exposure);
+uint32_t nrs_exposure_step_count(const nrs_exposure* exposure);
+int      nrs_exposure_set(nrs_exposure* exposure, const float* h_values);
+int      nrs_exposure_get(nrs_exposure* exposure, int which, void* h_out, size_t n);
+int      nrs_exposure_export(nrs_exposure* exposure, float* d_out, void* stream);
+int      nrs_exposure_targets(nrs_exposure* exposure, void* stream, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices, const uint32_t* d_pixels,
+                              const float* d_target_rgba, float* d_target_out, uint32_t* d_scale);
+int      nrs_exposure_accumulate(nrs_exposure* exposure, void* stream, const nrs_exposure_accumulate_params* params, uint32_t n_rays, const uint32_t* d_ray_counter,
+                                 const uint32_t* d_ray_indices, const uint32_t* d_numsteps_out, const uint32_t* d_ray_aux, const uint32_t* d_scale, const float* d_xy_pdf);
+int      nrs_exposure_step(nrs_exposure* exposure, void* stream, float loss_scale, float learning_rate);
+int      nrs_exposure_step_host(uint32_t n_images, const nrs_exposure_params* params, float loss_scale, float learning_rate, int64_t* cells, float* values, float* m,
+                                float* v, uint32_t* step_count);
 
 #ifdef __cplusplus
 }

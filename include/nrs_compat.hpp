@@ -304,6 +304,48 @@ private:
 	nrs_envmap* m_env = nullptr;
 };
 
+// m_nerf.training.cam_exposure with optimize_exposure (testbed.h; nrs.h "per-image exposure"): a log2 exposure per training image and channel, trained through the
+// target colour.  Fresh exposures are zero.  The learning rate is the caller's: the reference passes the network optimiser's current one.
+class Exposure {
+public:
+	static nrs_exposure_params default_params() { // the per-image AdamOptimizer (0.9, 0.99, 1e-8), exposure_l2_reg 0, n_steps_between_cam_updates 16
+		nrs_exposure_params p{};
+		nrs_exposure_default_params(&p);
+		return p;
+	}
+	static nrs_exposure_accumulate_params accumulate_params(const nrs_ray_loss_params& loss) {
+		return nrs_exposure_accumulate_params{(uint32_t)sizeof(nrs_exposure_accumulate_params), loss.loss_scale, loss.train_in_linear_colors};
+	}
+
+	Exposure(Context& ctx, uint32_t n_images) { check(nrs_exposure_create(ctx.get(), n_images, nullptr, &m_exp), "nrs_exposure_create"); }
+	Exposure(Context& ctx, uint32_t n_images, const nrs_exposure_params& params) { check(nrs_exposure_create(ctx.get(), n_images, &params, &m_exp), "nrs_exposure_create"); }
+	~Exposure() { nrs_exposure_destroy(m_exp); }
+	Exposure(const Exposure&) = delete;
+	Exposure& operator=(const Exposure&) = delete;
+
+	uint32_t n_images() const { return nrs_exposure_n_images(m_exp); }
+	// the values from the host ([n_images][3], or nullptr for zeros); the per-frame reset_state of the reference: moments, step count and cells start again
+	void set(const float* h_values) { check(nrs_exposure_set(m_exp, h_values), "nrs_exposure_set"); }
+	void get(nrs_exposure_what which, void* h_out) { check(nrs_exposure_get(m_exp, which, h_out, (size_t)3 * n_images()), "nrs_exposure_get"); }
+	void export_values(float* d_out, void* stream) { check(nrs_exposure_export(m_exp, d_out, stream), "nrs_exposure_export"); }
+	// per ray slot: the target scaled by its image's 2^exposure (for NerfNetwork::ray_loss_ex, in place of a gather) and the scale (for accumulate)
+	void targets(void* stream, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices, const uint32_t* d_pixels, const float* d_target_rgba,
+	             float* d_target_out, uint32_t* d_scale) {
+		check(nrs_exposure_targets(m_exp, stream, n_rays, d_ray_counter, d_ray_indices, d_pixels, d_target_rgba, d_target_out, d_scale), "nrs_exposure_targets");
+	}
+	void accumulate(void* stream, const nrs_exposure_accumulate_params& params, uint32_t n_rays, const uint32_t* d_ray_counter, const uint32_t* d_ray_indices,
+	                const uint32_t* d_numsteps_out, const uint32_t* d_ray_aux, const uint32_t* d_scale, const float* d_xy_pdf) {
+		check(nrs_exposure_accumulate(m_exp, stream, &params, n_rays, d_ray_counter, d_ray_indices, d_numsteps_out, d_ray_aux, d_scale, d_xy_pdf), "nrs_exposure_accumulate");
+	}
+	// every n_steps_between_cam_updates training steps
+	void step(void* stream, float loss_scale, float learning_rate) { check(nrs_exposure_step(m_exp, stream, loss_scale, learning_rate), "nrs_exposure_step"); }
+	uint32_t step() const { return nrs_exposure_step_count(m_exp); }
+	nrs_exposure* get() const { return m_exp; }
+
+private:
+	nrs_exposure* m_exp = nullptr;
+};
+
 // nrs_image_metrics on a caller's reference (d_reference: fp16 or f32 RGBA, linear, premultiplied), and run.py's totals over records that are back on the host
 inline void image_metrics(Context& ctx, void* stream, uint32_t width, uint32_t height, const float* d_image, const void* d_reference, nrs_image_format reference_format,
                           nrs_image_metrics_result* d_result, nrs_color_space color_space = NRS_COLOR_LINEAR, const float* background_rgba = nullptr, float* d_ssim_map = nullptr,

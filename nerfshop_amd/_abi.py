@@ -217,6 +217,30 @@ class EnvmapAccumulateParams(C.Structure):
         self.loss_type, self.envmap_loss_type, self.loss_scale, self.train_in_linear_colors = int(loss_type), int(envmap_loss_type), float(loss_scale), int(train_in_linear_colors)
 
 
+class ExposureParams(C.Structure):
+    """nrs_exposure_params; the defaults are the reference's per-image AdamOptimizer (0.9 / 0.99 / 1e-8), exposure_l2_reg 0 and n_steps_between_cam_updates 16"""
+    _fields_ = [("struct_size", C.c_uint32), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("l2_reg", C.c_float), ("steps_between_updates", C.c_uint32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.struct_size = C.sizeof(ExposureParams)
+        self.beta1, self.beta2, self.epsilon, self.l2_reg, self.steps_between_updates = 0.9, 0.99, 1e-8, 0.0, 16
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError(f"ExposureParams has no field {k}")
+            setattr(self, k, v)
+
+
+class ExposureAccumulateParams(C.Structure):
+    """nrs_exposure_accumulate_params; struct_size is filled in on construction"""
+    _fields_ = [("struct_size", C.c_uint32), ("loss_scale", C.c_float), ("train_in_linear_colors", C.c_uint32)]
+
+    def __init__(self, loss_scale=128.0, train_in_linear_colors=0):
+        super().__init__()
+        self.struct_size = C.sizeof(ExposureAccumulateParams)
+        self.loss_scale, self.train_in_linear_colors = float(loss_scale), int(train_in_linear_colors)
+
+
 class TrainingCamera(C.Structure):
     """nrs_training_camera; struct_size is filled in on construction.  Matrices are 3 x 4 column-major like RenderParams.camera_matrix0."""
     _fields_ = [("struct_size", C.c_uint32), ("xform_start", C.c_float * 12), ("xform_end", C.c_float * 12), ("focal_length", C.c_float * 2),
@@ -291,6 +315,8 @@ BASE_LEARNING_RATE, BASE_DECAY_START, BASE_DECAY_INTERVAL, BASE_DECAY_BASE = 1e-
 ENVMAP_LEARNING_RATE, ENVMAP_DECAY_START, ENVMAP_DECAY_INTERVAL, ENVMAP_DECAY_BASE = 1e-2, 10000, 5000, 0.33
 ENVMAP_TEXELS, ENVMAP_EMA, ENVMAP_GRADIENT, ENVMAP_CELLS = 0, 1, 2, 3  # nrs_envmap_what
 RAY_AUX_WORDS = 12  # NRS_RAY_AUX_WORDS
+EXPOSURE_VALUES, EXPOSURE_M, EXPOSURE_V, EXPOSURE_CELLS, EXPOSURE_GRADIENT = 0, 1, 2, 3, 4  # nrs_exposure_what
+EXPOSURE_MAX_IMAGES = 1 << 20  # NRS_EXPOSURE_MAX_IMAGES
 
 # every symbol include/nrs.h declares; tests check the library exports exactly these
 EXPORTS = [
@@ -331,6 +357,8 @@ EXPORTS = [
     "nrs_image_metrics", "nrs_dataset_image_metrics", "nrs_image_metrics_host", "nrs_image_metrics_summary_host",
     "nrs_envmap_default_adam_params", "nrs_envmap_create", "nrs_envmap_destroy", "nrs_envmap_resolution", "nrs_envmap_set_texels", "nrs_envmap_get", "nrs_envmap_export",
     "nrs_envmap_background", "nrs_ray_loss_ex", "nrs_envmap_accumulate", "nrs_envmap_step", "nrs_envmap_step_count",
+    "nrs_exposure_default_params", "nrs_exposure_create", "nrs_exposure_destroy", "nrs_exposure_n_images", "nrs_exposure_step_count", "nrs_exposure_set", "nrs_exposure_get",
+    "nrs_exposure_export", "nrs_exposure_targets", "nrs_exposure_accumulate", "nrs_exposure_step", "nrs_exposure_step_host",
 ]
 SNAPSHOT_ALLOW_LIGHT_DIRS = 1  # NRS_SNAPSHOT_ALLOW_LIGHT_DIRS
 SPP_BATCH_MAX = 64  # NRS_SPP_BATCH_MAX
@@ -481,6 +509,23 @@ def load():
         lib.nrs_envmap_step.argtypes = [P, P, C.c_float, C.c_float]
         lib.nrs_envmap_step_count.argtypes = [P]
         lib.nrs_envmap_step_count.restype = U32
+    if hasattr(lib, "nrs_exposure_create"):  # per-image exposure (detected by symbol)
+        lib.nrs_exposure_default_params.argtypes = [C.POINTER(ExposureParams)]
+        lib.nrs_exposure_default_params.restype = None
+        lib.nrs_exposure_create.argtypes = [P, U32, C.POINTER(ExposureParams), C.POINTER(P)]
+        lib.nrs_exposure_destroy.argtypes = [P]
+        lib.nrs_exposure_destroy.restype = None
+        lib.nrs_exposure_n_images.argtypes = [P]
+        lib.nrs_exposure_n_images.restype = U32
+        lib.nrs_exposure_step_count.argtypes = [P]
+        lib.nrs_exposure_step_count.restype = U32
+        lib.nrs_exposure_set.argtypes = [P, P]
+        lib.nrs_exposure_get.argtypes = [P, I, P, C.c_size_t]
+        lib.nrs_exposure_export.argtypes = [P, P, P]
+        lib.nrs_exposure_targets.argtypes = [P, P, U32, P, P, P, P, P, P]
+        lib.nrs_exposure_accumulate.argtypes = [P, P, C.POINTER(ExposureAccumulateParams), U32, P, P, P, P, P, P]
+        lib.nrs_exposure_step.argtypes = [P, P, C.c_float, C.c_float]
+        lib.nrs_exposure_step_host.argtypes = [U32, C.POINTER(ExposureParams), C.c_float, C.c_float, P, P, P, P, C.POINTER(U32)]
     lib.nrs_density_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), I, P]
     lib.nrs_rgba_on_grid.argtypes = [P, P, C.POINTER(U32 * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3), P]
     lib.nrs_edit_create.argtypes = [P, C.POINTER(ModelDesc), C.POINTER(TetMesh), C.POINTER(P)]

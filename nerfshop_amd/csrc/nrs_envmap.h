@@ -6,8 +6,6 @@
 namespace nrs {
 
 constexpr size_t kEnvmapMaxParams = 1ull << 31;  // 4 floats per texel; the optimiser's own limit (kAdamMaxParams)
-constexpr float kEnvmapDepositClamp = 512.0f;    // 2^21 rays x 512 x 2^32 = 2^62: a cell never wraps
-constexpr float kEnvmapCellScale = 4294967296.0f; // 2^32
 
 struct EnvmapBackgroundArgs {
 	uint32_t n_rays;

@@ -39,12 +39,7 @@ __global__ __launch_bounds__(256) void envmap_background_kernel(const EnvmapBack
 	reinterpret_cast<int4*>(a.footprint)[s] = make_int4(f.tx, f.ty, __float_as_int(f.wx), __float_as_int(f.wy));
 }
 
-// One deposit (include/nrs.h, "the environment map", DEPOSIT): skipped unless finite and non-zero, clamped to +-512, scaled by 2^32 (exact), rounded to nearest even;
-// the add returns nothing.
-__device__ __forceinline__ long long envmap_quantise(float p) {
-	if (!(fabsf(p) <= 3.402823466e38f) || p == 0.0f) return 0ll; // NaN, +-inf, +-0
-	return (long long)rintf(fminf(fmaxf(p, -kEnvmapDepositClamp), kEnvmapDepositClamp) * kEnvmapCellScale);
-}
+// One deposit (include/nrs.h, "the environment map", DEPOSIT): envmap_quantise (nrs_loss.cuh), and the add returns nothing.
 __device__ __forceinline__ void envmap_deposit(unsigned long long* cell, float p) {
 	const long long q = envmap_quantise(p);
 	if (q) (void)__hip_atomic_fetch_add(cell, (unsigned long long)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

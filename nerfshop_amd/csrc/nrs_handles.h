@@ -1,4 +1,4 @@
-// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, dataset, optimiser, environment map), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
+// nrs_handles.h -- the opaque structs of include/nrs.h (context, model, edit, selection, dataset, optimiser, environment map, exposure), the error helpers and the owner of a device allocation: what a host unit behind the C-ABI needs to
 // work on a context or a model.  nrs_host.h adds the helpers that cross the borders of the older units; a unit that needs none of them (nrs_api_mesh.cpp, nrs_api_selection.cpp) includes
 // this header alone.  Host-only C++17: no .hip / .cuh includes it.
 #pragma once
@@ -256,4 +256,15 @@ struct nrs_envmap {
 	nrs_optimizer* opt = nullptr;                // n parameters, n_matrix = 0; owned
 	nrs::DeviceBuffer<float> d_grad;             // [n]: zero between steps (the step clears what it reads)
 	nrs::DeviceBuffer<unsigned long long> d_cells; // [n]: int64 fixed point, 2^-32 per unit; zero between steps
+};
+
+// Per-image exposure (nrs_api_exposure.cpp, nrs_exposure.hip): n = 3 * n_images elements per array.
+struct nrs_exposure {
+	nrs_ctx* ctx = nullptr;
+	uint32_t n_images = 0;
+	nrs_exposure_params p{};
+	nrs::DeviceBuffer<float> d_values, d_m, d_v;
+	nrs::DeviceBuffer<unsigned long long> d_cells; // int64 fixed point, 2^-32 per unit; zero after a step
+	uint32_t step_count = 0;                       // one for all images
+	uint32_t rays_accumulated = 0;                 // since the last step or set: at most 2^21
 };

@@ -1,6 +1,7 @@
 // nrs_scan.cuh -- the scans of a wave and of a workgroup, stated once (gfx950, 64 lanes).
 //
 //   wave_inclusive_add       sum over lanes 0..lane.
+//   wave_sum                 sum over the 64 lanes, 64 bits wide (per-image exposure's deposits).
 //   wave_segmented_scan      `op` over the lanes st..lane of a segment (seg_scan_mul, seg_scan_add).
 //   block_exclusive_add      per-thread values -> "sum in front of this thread" and the workgroup's total, N values at once: the wave scan, then
 //   block_combine_waves      the cross-wave half, for a caller that numbers inside its waves itself (mc_count_kernel: ballots).
@@ -17,6 +18,13 @@ namespace nrs {
 __device__ __forceinline__ uint32_t wave_inclusive_add(uint32_t v, uint32_t lane) {
 	#pragma unroll
 	for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)v, d); if (lane >= d) v += u; }
+	return v;
+}
+
+// the sum over all 64 lanes, in every lane (a butterfly; integers: no order to keep)
+__device__ __forceinline__ long long wave_sum(long long v) {
+	#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
 	return v;
 }
 

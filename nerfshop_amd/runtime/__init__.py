@@ -18,6 +18,7 @@ from .context import Context
 from .dataset import Dataset, error_map_cdfs_host, error_map_resolution
 from .edits import AffineDuplication, CageDeformation
 from .envmap import Envmap
+from .exposure import Exposure, exposure_step_host
 from .mesh import Mesh, mesh_from_density
 from .metrics import image_metrics, image_metrics_host, metrics_summary
 from .network import DEFAULT_CELL_CACHE_BYTES, NerfNetwork, rng_advance, rng_seed

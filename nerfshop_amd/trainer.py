@@ -1,5 +1,6 @@
 """The reference's training loop from the ray on, end to end on the device: samples -> inference -> ray loss -> backward -> the fused optimiser step,
-with an optional trained environment map behind the last sample (Trainer(..., envmap=(256, 128))).
+with an optional trained environment map behind the last sample (Trainer(..., envmap=(256, 128))) and an optional trained exposure per training image
+(Trainer(..., exposure=True)).
 
     trainer = Trainer(ctx, synth.model_desc(1), seed=11, density_grid=grid)      # or no grid: the first update_density_grid() makes one from the network
     for i in range(n_steps):
@@ -55,10 +56,23 @@ class Trainer:
     def __init__(self, ctx, desc, seed=1337, weights=None, density_grid=None, max_samples=1 << 18, max_cascade=0, cone_angle_constant=0.0, adam=None,
                  loss_params=None, learning_rate=_abi.BASE_LEARNING_RATE, decay=(_abi.BASE_DECAY_START, _abi.BASE_DECAY_INTERVAL, _abi.BASE_DECAY_BASE),
                  density_grid_decay=0.95, envmap=None, envmap_loss_type=_abi.LOSS_RELATIVE_L2, envmap_learning_rate=_abi.ENVMAP_LEARNING_RATE,
-                 envmap_decay=(_abi.ENVMAP_DECAY_START, _abi.ENVMAP_DECAY_INTERVAL, _abi.ENVMAP_DECAY_BASE)):
+                 envmap_decay=(_abi.ENVMAP_DECAY_START, _abi.ENVMAP_DECAY_INTERVAL, _abi.ENVMAP_DECAY_BASE), exposure=None, exposure_l2_reg=0.0, cam_update_every=16):
         """envmap: None, a runtime.Envmap or a (res_x, res_y) pair: an environment map trained next to the network (m_envmap) -- the background behind a ray's last
-        sample, with base.json's envmap loss (RelativeL2) and its own schedule, ExponentialDecay(10000, 5000, 0.33) over 1e-2, on training_step."""
+        sample, with base.json's envmap loss (RelativeL2) and its own schedule, ExponentialDecay(10000, 5000, 0.33) over 1e-2, on training_step.
+        exposure: None, True or a runtime.Exposure: a log2 exposure per training image and channel, trained next to the network (m_nerf.training.optimize_exposure).
+        True makes one on the first step_dataset, when the number of images is known, with exposure_l2_reg and cam_update_every (the reference's exposure_l2_reg and
+        n_steps_between_cam_updates) as its l2_reg and steps_between_updates; a runtime.Exposure brings its own parameters.  Every step deposits the exposure's
+        gradient; the step on which cam_update_every of them have been accumulated runs Exposure.step with the network's current learning rate.  exposures() returns
+        the values: a training view is displayed with the tonemap's exposure + exposures()[view]."""
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
+        if exposure is not None and exposure is not True and not isinstance(exposure, runtime.Exposure):
+            raise NrsError("Trainer: exposure must be None, True or a runtime.Exposure")
+        if isinstance(exposure, runtime.Exposure) and exposure.ctx is not ctx:
+            raise NrsError("Trainer: the exposure belongs to another context")
+        if int(cam_update_every) < 1:
+            raise NrsError("Trainer: cam_update_every must be at least 1")
+        self.exposure, self.exposure_l2_reg, self.cam_update_every = exposure, float(exposure_l2_reg), int(cam_update_every)
+        self._exposure_bufs, self._steps_since_cam_update = None, 0
         if envmap is not None and not isinstance(envmap, runtime.Envmap):
             envmap = runtime.Envmap(ctx, int(envmap[0]), int(envmap[1]))
         if envmap is not None and envmap.ctx is not ctx:
@@ -114,26 +128,45 @@ class Trainer:
         self.network.update_density_grid(u, stream=stream)
         self._grid_step = self.training_step
 
-    def step(self, rays, target_rgba, jitter=None, background=None):
+    def step(self, rays, target_rgba, jitter=None, background=None, pixels=None, xy_pdf=None):
         """One training step on rays [n, 6] f32 with the colours they should have, target_rgba [n, 4] f32 (linear, premultiplied); jitter [n] in [0, 1) or None,
-        background [n, 3] (sRGB-encoded) or None for loss_params.background.  Returns the mean loss as a 0-d CUDA tensor.  Nothing waits for the device."""
-        return self._step(rays, target_rgba, jitter, background, None)
+        background [n, 3] (sRGB-encoded) or None for loss_params.background.  Returns the mean loss as a 0-d CUDA tensor.  Nothing waits for the device.
+        With an exposure: pixels [n, 2] int32 (image, pixel) by ray names each ray's image (required), and xy_pdf [n] f32 by ray, or None for 1, is the density the
+        pixel was drawn with inside its image -- the divisor of the exposure's gradient."""
+        return self._step(rays, target_rgba, jitter, background, None, pixels, xy_pdf)
 
-    def _step(self, rays, target_rgba, jitter, background, after_loss):
+    def exposures(self):
+        """The trained exposures [n_images, 3] f32 on the host (log2: a channel is scaled by 2^value), or None without an exposure or before the first dataset step
+        has made one.  A training view is displayed with the tonemap's exposure + exposures()[view] (runtime.Testbed's tonemap parameter)."""
+        return self.exposure.get() if isinstance(self.exposure, runtime.Exposure) else None
+
+    def _step(self, rays, target_rgba, jitter, background, after_loss, pixels=None, xy_pdf=None):
         """step(); after_loss(ray_counter, ray_indices, loss), if given, runs between the ray loss and the backward pass and may rewrite the per-slot losses in place."""
         net = self.network
         n_rays = int(rays.shape[0])
         if tuple(target_rgba.shape) != (n_rays, 4):
             raise NrsError("Trainer.step: target_rgba must be [n_rays, 4]")
+        expo = self.exposure
+        if expo is not None:
+            if pixels is None:
+                raise NrsError("Trainer.step: with an exposure, `pixels` must name each ray's image")
+            if expo is True:
+                raise NrsError("Trainer.step: exposure=True is made by the first step_dataset, which knows the number of images; pass a runtime.Exposure to step() directly")
         coords, numsteps, ray_indices, counters = net.training_samples(None, rays, jitter, self.cone_angle_constant, self.max_samples)
         net.inference_strided(None, coords, self._out16)
         # the loss reads its per-ray inputs by ray SLOT: gather them with the generator's indices (slots at or past counters[0] are not live)
         slots = ray_indices.to(torch.int64)
-        target = target_rgba.index_select(0, slots)
+        if expo is None:
+            target = target_rgba.index_select(0, slots)
+        else:  # the gather and the image's 2^exposure in one pass; the scale is kept for the gradient
+            if self._exposure_bufs is None or self._exposure_bufs[0].shape[0] != n_rays:
+                self._exposure_bufs = (torch.zeros((n_rays, 4), dtype=torch.float32, device=rays.device), torch.zeros((n_rays, 4), dtype=torch.int32, device=rays.device),
+                                       None if self.envmap is not None else torch.zeros((n_rays, _abi.RAY_AUX_WORDS), dtype=torch.int32, device=rays.device))
+            target, scale = expo.targets(ray_indices, counters[:1], pixels, target_rgba, out=self._exposure_bufs[:2])
         bg = None if background is None else background.index_select(0, slots)
         if self._loss_bufs is None or self._loss_bufs[0].shape[0] != n_rays:
             self._loss_bufs = net.ray_loss_buffers(n_rays, self.max_samples, device=rays.device)
-        env, bg_linear, aux = self.envmap, None, None
+        env, bg_linear, aux = self.envmap, None, None if expo is None else self._exposure_bufs[2]
         if env is not None:  # the background the ray sees through the envmap's live texels, and the lookup's footprint for the gradient
             if self._envmap_bufs is None or self._envmap_bufs[0].shape[0] != n_rays:
                 self._envmap_bufs = (torch.zeros((n_rays, 3), dtype=torch.float32, device=rays.device), torch.zeros((n_rays, 4), dtype=torch.int32, device=rays.device),
@@ -148,10 +181,19 @@ class Trainer:
         if env is not None:
             acc = _abi.EnvmapAccumulateParams(p.loss_type, self.envmap_loss_type, p.loss_scale, p.train_in_linear_colors)
             env.accumulate(acc, counters[:1], numsteps_out, aux, bg_linear, footprint, n_rays=n_rays)
+        if expo is not None:
+            lp = self.loss_params
+            expo.accumulate(_abi.ExposureAccumulateParams(lp.loss_scale, lp.train_in_linear_colors), counters[:1], ray_indices, numsteps_out, aux, scale, xy_pdf=xy_pdf,
+                            n_rays=n_rays)
         net.backward(None, coords_out, dl, self.grad, None, accumulate=True)
         self.optimizer.step(self.grad, loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate(), zero_grad=True)
         if env is not None:
             env.step(loss_scale=float(self.loss_params.loss_scale), lr=self.current_envmap_learning_rate())
+        if expo is not None:  # the camera update of train_nerf (src/testbed_nerf.cu:3834-3915): every cam_update_every steps, with the network's learning rate
+            self._steps_since_cam_update += 1
+            if self._steps_since_cam_update >= self.cam_update_every:
+                expo.step(loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate())
+                self._steps_since_cam_update = 0
         self.training_step += 1
         return loss.sum()
 
@@ -165,9 +207,19 @@ class Trainer:
         ray's loss is deposited after the ray loss (the returned loss is then the sum of loss / pdf, the loss the reference reports); and once steps_between steps have
         passed the CDFs are rebuilt and steps_between grows.  All on the device; with both sampling switches off the step computes what it computes without a schedule."""
         u = self._grid_update
+        if self.exposure is not None:
+            if error_map is not None and error_map.sample_images and error_map.sample_pixels:
+                raise NrsError("Trainer.step_dataset: exposure with sample_images and sample_pixels: the exposure's gradient is divided by the pixel's density alone, "
+                               "but the dataset writes the product of the image's and the pixel's, and the two cannot be told apart")
+            if self.exposure is True:
+                self.exposure = runtime.Exposure(self.ctx, dataset.n_images,
+                                                 _abi.ExposureParams(l2_reg=self.exposure_l2_reg, steps_between_updates=self.cam_update_every))
+            elif self.exposure.n_images != dataset.n_images:
+                raise NrsError("Trainer.step_dataset: the exposure was made for another number of images")
         if error_map is None:
-            rays, jitter, target, background, _ = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg, want_pixels=False)
-            loss = self.step(rays, target, jitter=jitter, background=background)
+            rays, jitter, target, background, pixels = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg,
+                                                                    want_pixels=self.exposure is not None)
+            loss = self.step(rays, target, jitter=jitter, background=background, pixels=pixels)
         else:
             em = error_map
             if em.steps_since == 0:
@@ -181,7 +233,9 @@ class Trainer:
             def accumulate(ray_counter, ray_indices, loss):
                 em.last_loss = (ray_counter.clone(), ray_indices.clone(), loss.clone()) if em.keep_last else None
                 dataset.error_map_accumulate(n_rays, ray_counter, ray_indices, loss, xy, pixels, pdf=pdf, loss_weighted=loss)
-            loss = self._step(rays, target, jitter, background, accumulate)
+            # the exposure's divisor is xy_pdf alone (src/testbed_nerf.cu:1948): with images drawn uniformly the dataset's pdf is exactly that
+            xy_pdf = pdf if self.exposure is not None and by_error[1] else None
+            loss = self._step(rays, target, jitter, background, accumulate, pixels if self.exposure is not None else None, xy_pdf)
             em.steps_since += 1
             if em.steps_since >= em.steps_between:
                 dataset.error_map_build_cdfs()
