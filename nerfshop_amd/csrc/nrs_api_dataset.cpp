@@ -1,8 +1,9 @@
 // nrs_api_dataset.cpp -- the dataset behind the C-ABI: create / destroy, images (converted on the device), cameras (kept on the host, sent in one block), the pixel
 // rays of a training step, mark_untrained, and the training error map (its cells, its CDFs, the rays drawn from them).  Everything that can be refused is refused before the first HIP call.
-#include "nrs_handles.h"
+#include "nrs_train_host.h"
 #include "nrs_dataset.h"
 #include "nrs_train.h"
+#include "nrs_cells.h"
 
 #include <cmath>
 #include <cstring>
@@ -113,7 +114,7 @@ int nrs_dataset_rays(nrs_dataset* ds, void* stream, const nrs_dataset_rays_param
 	if (!ds || !p) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays: NULL argument");
 	if (p->struct_size != sizeof(nrs_dataset_rays_params)) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays: params->struct_size is not sizeof(nrs_dataset_rays_params)");
 	if (n_rays && (!d_rays || !d_jitter || !d_target_rgba || (p->random_bg_color && !d_background))) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays: NULL output");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays: more than 2^21 rays (the generator's limit)");
+	NRS_TRY(check_ray_count(n_rays, "nrs_dataset_rays", " (the generator's limit)"));
 	NRS_TRY(check_complete(ds, "nrs_dataset_rays"));
 	if (n_rays == 0) return NRS_OK;
 	HIP_TRY(hipSetDevice(ds->ctx->device));
@@ -147,7 +148,6 @@ static int size_map(nrs_dataset* ds, uint32_t res_x, uint32_t res_y) {
 	ds->map_res_x = res_x; ds->map_res_y = res_y;
 	return NRS_OK;
 }
-static uint64_t quantise_deposit(float v) { return v > 0.0f ? (uint64_t)(std::fmin(v, 1024.0f) * 4294967296.0f) : 0ull; } // nrs_dataset.hip's error_map_quantise
 
 int nrs_dataset_error_map_reset(nrs_dataset* ds, uint32_t res_x, uint32_t res_y, void* stream) {
 	if (!ds) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_error_map_reset: NULL argument");
@@ -170,7 +170,7 @@ int nrs_dataset_error_map_set(nrs_dataset* ds, uint32_t res_x, uint32_t res_y, c
 	NRS_TRY(check_map_resolution(ds, res_x, res_y, "nrs_dataset_error_map_set"));
 	const size_t n = (size_t)ds->n_images * res_y * res_x;
 	std::vector<uint64_t> cells(n);
-	for (size_t k = 0; k < n; ++k) cells[k] = quantise_deposit(h_data_f32[k]);
+	for (size_t k = 0; k < n; ++k) cells[k] = error_cell_quantise(h_data_f32[k]);
 	HIP_TRY(hipSetDevice(ds->ctx->device));
 	HIP_TRY(hipDeviceSynchronize());
 	NRS_TRY(size_map(ds, res_x, res_y));
@@ -200,7 +200,7 @@ int nrs_dataset_error_map_get(nrs_dataset* ds, int what, void* h_out, size_t* co
 	if (what == NRS_ERROR_MAP_FLOAT) { // the reference's float map, formed where it is read
 		std::vector<uint64_t> cells(n);
 		HIP_TRY(hipMemcpy(cells.data(), src, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-		for (size_t k = 0; k < n; ++k) ((float*)h_out)[k] = (float)cells[k] * 0x1p-32f;
+		for (size_t k = 0; k < n; ++k) ((float*)h_out)[k] = error_cell_to_float(cells[k]);
 		return NRS_OK;
 	}
 	HIP_TRY(hipMemcpy(h_out, src, n * (what == NRS_ERROR_MAP_CELLS ? sizeof(uint64_t) : sizeof(float)), hipMemcpyDeviceToHost));
@@ -211,7 +211,7 @@ int nrs_dataset_error_map_accumulate(nrs_dataset* ds, void* stream, uint32_t n_r
                                      const float* d_xy, const uint32_t* d_pixels, const float* d_pdf, float* d_loss_weighted) {
 	if (!ds) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_error_map_accumulate: NULL argument");
 	if (n_rays && (!d_ray_counter || !d_ray_indices || !d_loss || !d_xy || !d_pixels)) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_error_map_accumulate: NULL input");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_error_map_accumulate: more than 2^21 rays (what the cells hold without a wrap)");
+	NRS_TRY(check_ray_count(n_rays, "nrs_dataset_error_map_accumulate", " (what the cells hold without a wrap)"));
 	if (!ds->map_res_x) return fail(NRS_ERR_STATE, "nrs_dataset_error_map_accumulate: there is no map (nrs_dataset_error_map_reset)");
 	if (n_rays == 0) return NRS_OK;
 	HIP_TRY(hipSetDevice(ds->ctx->device));
@@ -292,7 +292,7 @@ int nrs_dataset_rays_ex(nrs_dataset* ds, void* stream, const nrs_dataset_rays_ex
 	if (!ds || !p) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays_ex: NULL argument");
 	if (p->struct_size != sizeof(nrs_dataset_rays_ex_params)) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays_ex: params->struct_size is not sizeof(nrs_dataset_rays_ex_params)");
 	if (n_rays && (!d_rays || !d_jitter || !d_target_rgba || (p->random_bg_color && !d_background))) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays_ex: NULL output");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_dataset_rays_ex: more than 2^21 rays (the generator's limit)");
+	NRS_TRY(check_ray_count(n_rays, "nrs_dataset_rays_ex", " (the generator's limit)"));
 	NRS_TRY(check_complete(ds, "nrs_dataset_rays_ex"));
 	if ((p->sample_images_by_error || p->sample_pixels_by_error) && !ds->cdf_valid)
 		return fail(NRS_ERR_STATE, "nrs_dataset_rays_ex: sampling by error without valid CDFs (nrs_dataset_error_map_build_cdfs)");

@@ -1,7 +1,7 @@
 // nrs_api_envmap.cpp -- the trainable environment map behind the C-ABI (include/nrs.h, "the environment map"): the handle, its texels and their optimiser, the
 // background of a training ray, the gradient's deposits and the step.  Everything that can be refused is refused before the first HIP call; background, accumulate, step
 // and export never wait for the device.
-#include "nrs_handles.h"
+#include "nrs_train_host.h"
 #include "nrs_envmap.h"
 #include "nrs_train.h"
 
@@ -19,12 +19,6 @@ nrs_adam_params default_envmap_adam() {
 	p.beta1 = 0.9f; p.beta2 = 0.99f; p.epsilon = 1e-10f; p.l2_reg = 0.0f; p.non_matrix_lr_factor = 1.0f; p.ema_decay = 0.99f;
 	return p;
 }
-
-int check_rays(uint32_t n_rays, const char* who) {
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, std::string(who) + ": more than 2^21 rays");
-	return NRS_OK;
-}
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0u; }
 
 } // namespace
 
@@ -96,16 +90,7 @@ int nrs_envmap_get(nrs_envmap* e, int which, void* h_out, size_t n) {
 	if (which == NRS_ENVMAP_EMA) return nrs_optimizer_get_state(e->opt, NRS_OPT_EMA, h_out, n);
 	HIP_TRY(hipSetDevice(e->ctx->device));
 	HIP_TRY(hipDeviceSynchronize());
-	if (which == NRS_ENVMAP_CELLS) {
-		HIP_TRY(hipMemcpy(h_out, e->d_cells.get(), n * sizeof(int64_t), hipMemcpyDeviceToHost));
-		return NRS_OK;
-	}
-	// the gradient the next step will read: the step's own expression on the cells as they are now (after a step: zero)
-	std::vector<int64_t> cells(n);
-	HIP_TRY(hipMemcpy(cells.data(), e->d_cells.get(), n * sizeof(int64_t), hipMemcpyDeviceToHost));
-	float* g = (float*)h_out;
-	for (size_t i = 0; i < n; ++i) g[i] = (float)((double)cells[i] * 0x1p-32);
-	return NRS_OK;
+	return signed_cells_to_host(e, n, which == NRS_ENVMAP_GRADIENT, h_out); // the cells, or the gradient the next step will read (after a step: zero)
 }
 
 int nrs_envmap_export(nrs_envmap* e, int ema, float* d_out, void* stream) {
@@ -121,7 +106,7 @@ int nrs_envmap_background(nrs_envmap* e, void* stream, uint32_t n_rays, const ui
 	if (!e || (n_rays && (!d_ray_counter || !d_ray_indices || !d_rays || !d_background_linear || !d_footprint)))
 		return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_background: NULL argument");
 	if (!d_background && !default_background) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_background: neither d_background nor default_background");
-	NRS_TRY(check_rays(n_rays, "nrs_envmap_background"));
+	NRS_TRY(check_ray_count(n_rays, "nrs_envmap_background"));
 	if (!aligned16(d_footprint)) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_background: d_footprint is not 16-byte aligned");
 	if (n_rays == 0) return NRS_OK;
 	HIP_TRY(hipSetDevice(e->ctx->device));
@@ -144,7 +129,7 @@ int nrs_envmap_accumulate(nrs_envmap* e, void* stream, const nrs_envmap_accumula
 	if (p->loss_type > (uint32_t)NRS_LOSS_RELATIVE_L2 || p->envmap_loss_type > (uint32_t)NRS_LOSS_RELATIVE_L2)
 		return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_accumulate: unknown loss_type or envmap_loss_type");
 	if (!std::isfinite(p->loss_scale)) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_accumulate: loss_scale is not finite");
-	NRS_TRY(check_rays(n_rays, "nrs_envmap_accumulate"));
+	NRS_TRY(check_ray_count(n_rays, "nrs_envmap_accumulate"));
 	if (!aligned16(d_ray_aux) || !aligned16(d_footprint)) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_accumulate: d_ray_aux or d_footprint is not 16-byte aligned");
 	if (n_rays == 0) return NRS_OK;
 	HIP_TRY(hipSetDevice(e->ctx->device));
@@ -160,8 +145,7 @@ int nrs_envmap_accumulate(nrs_envmap* e, void* stream, const nrs_envmap_accumula
 
 int nrs_envmap_step(nrs_envmap* e, void* stream, float loss_scale, float learning_rate) {
 	if (!e) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_step: NULL envmap");
-	if (!std::isfinite(loss_scale) || !(loss_scale > 0.f)) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_step: loss_scale is not finite or <= 0");
-	if (!std::isfinite(learning_rate) || learning_rate < 0.f) return fail(NRS_ERR_INVALID_ARG, "nrs_envmap_step: learning_rate is negative or not finite");
+	NRS_TRY(check_step_scalars(loss_scale, learning_rate, "nrs_envmap_step"));
 	HIP_TRY(hipSetDevice(e->ctx->device));
 	NRS_LAUNCH(launch_envmap_cells_to_gradient(e->n, e->d_cells.get(), e->d_grad.get(), stream));
 	return nrs_optimizer_step(e->opt, stream, e->d_grad.get(), loss_scale, learning_rate, 1);

@@ -1,7 +1,7 @@
 // nrs_api_exposure.cpp -- per-image exposure behind the C-ABI (include/nrs.h, "per-image exposure"): the handle, its values and moments, the scaled target of a
 // training ray, the gradient's deposits, the step and the step's host twin.  Everything that can be refused is refused before the first HIP call; targets, accumulate,
 // step and export never wait for the device.
-#include "nrs_handles.h"
+#include "nrs_train_host.h"
 #include "nrs_exposure.h"
 #include "nrs_train.h"
 
@@ -31,13 +31,6 @@ int check_params(const nrs_exposure_params* p, uint32_t n_images, const char* wh
 	if (p->steps_between_updates == 0u) return fail(NRS_ERR_INVALID_ARG, w + ": steps_between_updates is 0");
 	return NRS_OK;
 }
-int check_step(float loss_scale, float learning_rate, const char* who) {
-	const std::string w(who);
-	if (!std::isfinite(loss_scale) || !(loss_scale > 0.f)) return fail(NRS_ERR_INVALID_ARG, w + ": loss_scale is not finite or <= 0");
-	if (!std::isfinite(learning_rate) || learning_rate < 0.f) return fail(NRS_ERR_INVALID_ARG, w + ": learning_rate is negative or not finite");
-	return NRS_OK;
-}
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0u; }
 
 int zero_state(nrs_exposure* e, bool values_too) {
 	const size_t n = 3 * (size_t)e->n_images;
@@ -105,17 +98,7 @@ int nrs_exposure_get(nrs_exposure* e, int which, void* h_out, size_t n) {
 	if (n != 3 * (size_t)e->n_images) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_get: n is not 3 * n_images");
 	HIP_TRY(hipSetDevice(e->ctx->device));
 	HIP_TRY(hipDeviceSynchronize());
-	if (which == NRS_EXPOSURE_CELLS) {
-		HIP_TRY(hipMemcpy(h_out, e->d_cells.get(), n * sizeof(int64_t), hipMemcpyDeviceToHost));
-		return NRS_OK;
-	}
-	if (which == NRS_EXPOSURE_GRADIENT) { // the step's own expression on the cells as they are now
-		std::vector<int64_t> cells(n);
-		HIP_TRY(hipMemcpy(cells.data(), e->d_cells.get(), n * sizeof(int64_t), hipMemcpyDeviceToHost));
-		float* g = (float*)h_out;
-		for (size_t i = 0; i < n; ++i) g[i] = (float)((double)cells[i] * 0x1p-32);
-		return NRS_OK;
-	}
+	if (which == NRS_EXPOSURE_CELLS || which == NRS_EXPOSURE_GRADIENT) return signed_cells_to_host(e, n, which == NRS_EXPOSURE_GRADIENT, h_out);
 	const float* src = which == NRS_EXPOSURE_VALUES ? e->d_values.get() : (which == NRS_EXPOSURE_M ? e->d_m.get() : e->d_v.get());
 	HIP_TRY(hipMemcpy(h_out, src, n * sizeof(float), hipMemcpyDeviceToHost));
 	return NRS_OK;
@@ -132,7 +115,7 @@ int nrs_exposure_targets(nrs_exposure* e, void* stream, uint32_t n_rays, const u
                          const float* d_target_rgba, float* d_target_out, uint32_t* d_scale) {
 	if (!e || (n_rays && (!d_ray_counter || !d_ray_indices || !d_pixels || !d_target_rgba || !d_target_out || !d_scale)))
 		return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_targets: NULL argument");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_targets: more than 2^21 rays");
+	NRS_TRY(check_ray_count(n_rays, "nrs_exposure_targets"));
 	if (!aligned16(d_scale)) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_targets: d_scale is not 16-byte aligned");
 	if (n_rays == 0) return NRS_OK;
 	{ // one slot's output must not land on another slot's input: the two arrays are indexed differently
@@ -154,7 +137,7 @@ int nrs_exposure_accumulate(nrs_exposure* e, void* stream, const nrs_exposure_ac
 	if (p->struct_size != sizeof(nrs_exposure_accumulate_params))
 		return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_accumulate: params->struct_size is not sizeof(nrs_exposure_accumulate_params)");
 	if (!std::isfinite(p->loss_scale) || !(p->loss_scale > 0.f)) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_accumulate: loss_scale is not finite or <= 0");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_accumulate: more than 2^21 rays");
+	NRS_TRY(check_ray_count(n_rays, "nrs_exposure_accumulate"));
 	if (!aligned16(d_ray_aux) || !aligned16(d_scale)) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_accumulate: d_ray_aux or d_scale is not 16-byte aligned");
 	if (n_rays == 0) return NRS_OK;
 	if (n_rays > kTrainMaxRays - e->rays_accumulated)
@@ -171,7 +154,7 @@ int nrs_exposure_accumulate(nrs_exposure* e, void* stream, const nrs_exposure_ac
 
 int nrs_exposure_step(nrs_exposure* e, void* stream, float loss_scale, float learning_rate) {
 	if (!e) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_step: NULL exposure");
-	NRS_TRY(check_step(loss_scale, learning_rate, "nrs_exposure_step"));
+	NRS_TRY(check_step_scalars(loss_scale, learning_rate, "nrs_exposure_step"));
 	HIP_TRY(hipSetDevice(e->ctx->device));
 	ExposureStepArgs a{};
 	a.n_images = e->n_images;
@@ -187,7 +170,7 @@ int nrs_exposure_step_host(uint32_t n_images, const nrs_exposure_params* params,
                            uint32_t* step_count) {
 	if (!cells || !values || !m || !v || !step_count) return fail(NRS_ERR_INVALID_ARG, "nrs_exposure_step_host: NULL argument");
 	NRS_TRY(check_params(params, n_images, "nrs_exposure_step_host"));
-	NRS_TRY(check_step(loss_scale, learning_rate, "nrs_exposure_step_host"));
+	NRS_TRY(check_step_scalars(loss_scale, learning_rate, "nrs_exposure_step_host"));
 	const nrs_exposure_params p = params ? *params : default_exposure_params();
 	*step_count += 1u;
 	exposure_step_host(n_images, exposure_step_consts(n_images, p.beta1, p.beta2, p.epsilon, p.l2_reg, p.steps_between_updates, loss_scale, learning_rate, *step_count), cells,

@@ -1,6 +1,6 @@
 // nrs_api_optimizer.cpp -- the optimiser behind the C-ABI (include/nrs.h, "optimiser"): the bias table and the schedule on the host, the handle, the step.
 // Everything that can be refused is refused before the first HIP call; nrs_optimizer_step never waits for the device.
-#include "nrs_handles.h"
+#include "nrs_train_host.h"
 #include "nrs_optimizer.h"
 
 #include <cmath>
@@ -164,8 +164,7 @@ int nrs_optimizer_set_weights(nrs_optimizer* o, const float* weights, int on_dev
 
 int nrs_optimizer_step(nrs_optimizer* o, void* stream, float* d_grad, float loss_scale, float learning_rate, int zero_grad) {
 	if (!o || !d_grad) return fail(NRS_ERR_INVALID_ARG, "nrs_optimizer_step: NULL argument");
-	if (!std::isfinite(loss_scale) || !(loss_scale > 0.f)) return fail(NRS_ERR_INVALID_ARG, "nrs_optimizer_step: loss_scale is not finite or <= 0");
-	if (!finite_nonneg(learning_rate)) return fail(NRS_ERR_INVALID_ARG, "nrs_optimizer_step: learning_rate is negative or not finite");
+	NRS_TRY(check_step_scalars(loss_scale, learning_rate, "nrs_optimizer_step"));
 	if (((uintptr_t)d_grad & 3u) != 0u) return fail(NRS_ERR_INVALID_ARG, "nrs_optimizer_step: d_grad is not 4-byte aligned");
 	if (!o->have_weights) return fail(NRS_ERR_STATE, "nrs_optimizer_step: weights not set (nrs_optimizer_set_weights)");
 	HIP_TRY(hipSetDevice(o->ctx->device));

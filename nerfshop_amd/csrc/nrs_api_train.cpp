@@ -1,5 +1,5 @@
 // nrs_api_train.cpp -- the training-ray path behind the C-ABI: nrs_training_samples, nrs_ray_loss, nrs_ray_loss_ex.  Everything that can be refused is refused before the first HIP call.
-#include "nrs_handles.h"
+#include "nrs_train_host.h"
 #include "nrs_train.h"
 
 #include <cmath>
@@ -23,7 +23,7 @@ int nrs_training_samples(nrs_model* m, void* stream, uint32_t n_rays, const floa
 	if (ld < NRS_NETWORK_INPUT_FLOATS) return fail(NRS_ERR_INVALID_ARG, "nrs_training_samples: ld < 7");
 	if (max_samples == 0) return fail(NRS_ERR_INVALID_ARG, "nrs_training_samples: max_samples is 0");
 	if (!(cone_angle_constant >= 0.f) || !std::isfinite(cone_angle_constant)) return fail(NRS_ERR_INVALID_ARG, "nrs_training_samples: cone_angle_constant is negative or not finite");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_training_samples: more than 2^21 rays (the sample counters are 32 bits wide)");
+	NRS_TRY(check_ray_count(n_rays, "nrs_training_samples", " (the sample counters are 32 bits wide)"));
 	if (m->n_extra_dims != 0u) return fail(NRS_ERR_UNSUPPORTED, "nrs_training_samples: n_extra_dims (0 is supported: no training samples with light directions)");
 	if (!m->have_bitfield) return fail(NRS_ERR_STATE, "nrs_training_samples: occupancy not set (nrs_model_set_density_bitfield/_grid)");
 	HIP_TRY(hipSetDevice(m->ctx->device));
@@ -64,8 +64,8 @@ int nrs_ray_loss_ex(nrs_model* m, void* stream, const nrs_ray_loss_params* p, ui
 	if (dl_layout == NRS_PLANES && ld_dl < p->max_samples_compacted) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: ld_dl < max_samples_compacted");
 	if (!std::isfinite(p->loss_scale)) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: loss_scale is not finite");
 	if (p->near_distance > 0.f && !d_ray_origins) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: near_distance > 0 needs d_ray_origins");
-	if (n_rays > kTrainMaxRays) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss: more than 2^21 rays (the sample counters are 32 bits wide)");
-	if (((uintptr_t)d_ray_aux & 15u) != 0u) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss_ex: d_ray_aux is not 16-byte aligned");
+	NRS_TRY(check_ray_count(n_rays, "nrs_ray_loss", " (the sample counters are 32 bits wide)"));
+	if (!aligned16(d_ray_aux)) return fail(NRS_ERR_INVALID_ARG, "nrs_ray_loss_ex: d_ray_aux is not 16-byte aligned");
 	if (n_rays) { // the compaction is not done in place
 		const char *in0 = (const char*)d_coords, *in1 = in0 + (size_t)n_samples * ld_in * sizeof(float);
 		const char *out0 = (const char*)d_coords_out, *out1 = out0 + (size_t)p->max_samples_compacted * ld_in * sizeof(float);

@@ -11,6 +11,8 @@
 #include "nrs_internal.h"
 #include "nrs_launch.h"
 #include "nrs_dataset.h"
+#include "nrs_train.h"
+#include "nrs_cells.h"
 #include "nrs_vec.cuh"
 #include "nrs_grid_math.cuh"
 #include "nrs_random.cuh"
@@ -190,15 +192,10 @@ int launch_dataset_rays_ex(const DatasetRaysArgs& a, void* stream) {
 }
 
 // ---- the error map: deposits (tn:1861-1886) -----------------------------------------------------------------------------------------------------------
-// One deposit (include/nrs.h, deviation 1): skipped unless v > 0 (NaN too), clamped to 1024, scaled by 2^32 (exact), truncated; the add returns nothing.
-__device__ __forceinline__ uint64_t error_map_quantise(float v) { return v > 0.0f ? (uint64_t)(fminf(v, 1024.0f) * 4294967296.0f) : 0ull; }
-__device__ __forceinline__ void error_map_deposit(uint64_t* cell, float v) {
-	const uint64_t q = error_map_quantise(v);
-	if (q) (void)__hip_atomic_fetch_add(cell, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// One deposit (include/nrs.h, deviation 1): error_cell_deposit (nrs_cells.h).
 __global__ __launch_bounds__(256) void error_map_accumulate_kernel(const ErrorMapAccumulateArgs a) {
 	const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-	if (s >= min(*a.ray_counter, a.n_rays)) return;
+	if (s >= live_slots(a.ray_counter, a.n_rays)) return;
 	const uint32_t i = a.ray_indices[s];
 	if (i >= a.n_rays) return;
 	const float loss = a.loss[s];
@@ -215,10 +212,10 @@ __global__ __launch_bounds__(256) void error_map_accumulate_kernel(const ErrorMa
 	// res >= 2 and the clamp of pos put the cell into [0, res - 2] already; the clamp below acts for a NaN in xy alone (include/nrs.h, deviation 3)
 	const uint32_t cx = (uint32_t)max(min(ix, (int)a.res_x - 2), 0), cy = (uint32_t)max(min(iy, (int)a.res_y - 2), 0);
 	uint64_t* c = a.cells + ((size_t)img * a.res_y + cy) * a.res_x + cx;
-	error_map_deposit(c, (1 - wx) * (1 - wy) * e);
-	error_map_deposit(c + 1, wx * (1 - wy) * e);
-	error_map_deposit(c + a.res_x, (1 - wx) * wy * e);
-	error_map_deposit(c + a.res_x + 1, wx * wy * e);
+	error_cell_deposit(c, (1 - wx) * (1 - wy) * e);
+	error_cell_deposit(c + 1, wx * (1 - wy) * e);
+	error_cell_deposit(c + a.res_x, (1 - wx) * wy * e);
+	error_cell_deposit(c + a.res_x + 1, wx * wy * e);
 }
 int launch_error_map_accumulate(const ErrorMapAccumulateArgs& a, void* stream) {
 	if (a.n_rays == 0) return NRS_OK;
@@ -250,7 +247,7 @@ __global__ __launch_bounds__(64) void error_map_cdf_kernel(uint32_t n_rows, uint
 			const uint32_t e = k * 64u + lane, r = e / kCdfTile, x = e % kCdfTile;
 			if (r < rows && x < cw) {
 				const size_t at = (size_t)(row0 + r) * width + c0 + x;
-				tile[r][x] = MODE == 0 ? (float)((const uint64_t*)src)[at] * 0x1p-32f + 1e-10f : ((const float*)src)[at];
+				tile[r][x] = MODE == 0 ? error_cell_to_float(((const uint64_t*)src)[at]) + 1e-10f : ((const float*)src)[at];
 			}
 		}
 		__syncthreads();

@@ -16,14 +16,13 @@
 #include "nrs_vec.cuh"
 #include "nrs_camera.cuh"
 #include "nrs_loss.cuh"
+#include "nrs_cells.h"
 
 namespace nrs {
 
-__device__ __forceinline__ uint32_t envmap_live_slots(const uint32_t* ray_counter, uint32_t n_rays) { return min(*ray_counter, n_rays); }
-
 __global__ __launch_bounds__(256) void envmap_background_kernel(const EnvmapBackgroundArgs a) {
 	const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-	if (s >= envmap_live_slots(a.ray_counter, a.n_rays)) return;
+	if (s >= live_slots(a.ray_counter, a.n_rays)) return;
 	const uint32_t i = a.ray_indices[s];
 	if (i >= a.n_rays) return;
 	const float* r = a.rays + 6 * (size_t)i;
@@ -39,15 +38,9 @@ __global__ __launch_bounds__(256) void envmap_background_kernel(const EnvmapBack
 	reinterpret_cast<int4*>(a.footprint)[s] = make_int4(f.tx, f.ty, __float_as_int(f.wx), __float_as_int(f.wy));
 }
 
-// One deposit (include/nrs.h, "the environment map", DEPOSIT): envmap_quantise (nrs_loss.cuh), and the add returns nothing.
-__device__ __forceinline__ void envmap_deposit(unsigned long long* cell, float p) {
-	const long long q = envmap_quantise(p);
-	if (q) (void)__hip_atomic_fetch_add(cell, (unsigned long long)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __global__ __launch_bounds__(256) void envmap_accumulate_kernel(const EnvmapAccumulateArgs a) {
 	const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-	if (s >= envmap_live_slots(a.ray_counter, a.n_rays)) return;
+	if (s >= live_slots(a.ray_counter, a.n_rays)) return;
 	const uint4* aux = reinterpret_cast<const uint4*>(a.ray_aux + kRayAuxWords * (size_t)s);
 	const uint4 a2 = aux[2];
 	const uint32_t n = a2.z;
@@ -84,14 +77,14 @@ __global__ __launch_bounds__(256) void envmap_accumulate_kernel(const EnvmapAccu
 	#pragma unroll
 	for (int k = 0; k < 4; ++k) {
 		#pragma unroll
-		for (int c = 0; c < 3; ++c) envmap_deposit(cell[k] + c, v[c] * w[k]); // (alpha's gradient is 0: tn:1981)
+		for (int c = 0; c < 3; ++c) signed_cell_deposit(cell[k] + c, v[c] * w[k]); // include/nrs.h, "the environment map", DEPOSIT (alpha's gradient is 0: tn:1981)
 	}
 }
 
 __global__ __launch_bounds__(256) void envmap_cells_to_gradient_kernel(uint32_t n, unsigned long long* __restrict__ cells, float* __restrict__ grad) {
 	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
 		const long long c = (long long)cells[i];
-		grad[i] = (float)((double)c * 0x1p-32);
+		grad[i] = signed_cell_to_float(c);
 		if (c) cells[i] = 0ull;
 	}
 }

@@ -15,14 +15,13 @@
 #include "nrs_train.h"
 #include "nrs_scan.cuh"
 #include "nrs_loss.cuh"
+#include "nrs_cells.h"
 
 namespace nrs {
 
-__device__ __forceinline__ uint32_t exposure_live_slots(const uint32_t* ray_counter, uint32_t n_rays) { return min(*ray_counter, n_rays); }
-
 __global__ __launch_bounds__(256) void exposure_targets_kernel(const ExposureTargetsArgs a) {
 	const uint32_t s = blockIdx.x * 256 + threadIdx.x;
-	if (s >= exposure_live_slots(a.ray_counter, a.n_rays)) return;
+	if (s >= live_slots(a.ray_counter, a.n_rays)) return;
 	const uint32_t i = a.ray_indices[s];
 	if (i >= a.n_rays) return;
 	const uint32_t img = a.pixels[2 * (size_t)i];
@@ -35,17 +34,12 @@ __global__ __launch_bounds__(256) void exposure_targets_kernel(const ExposureTar
 	reinterpret_cast<uint4*>(a.scale)[s] = make_uint4(__float_as_uint(sx), __float_as_uint(sy), __float_as_uint(sz), img);
 }
 
-// One cell's add: no return value.
-__device__ __forceinline__ void exposure_add(unsigned long long* cell, long long q) {
-	(void)__hip_atomic_fetch_add(cell, (unsigned long long)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Every thread of the workgroup reaches the wave operations below: a slot that deposits nothing carries q = 0 and stays out of the ballots.
 __global__ __launch_bounds__(256) void exposure_accumulate_kernel(const ExposureAccumulateArgs a) {
 	const uint32_t s = blockIdx.x * 256 + threadIdx.x;
 	long long q[3] = {0ll, 0ll, 0ll};
 	uint32_t img = 0u;
-	if (s < exposure_live_slots(a.ray_counter, a.n_rays)) {
+	if (s < live_slots(a.ray_counter, a.n_rays)) {
 		const uint32_t i = a.ray_indices[s];
 		if (i < a.n_rays && a.numsteps_out[2 * (size_t)s] > 0u) { // (tn:1838: a ray without compact samples has returned)
 			const uint4 sc = reinterpret_cast<const uint4*>(a.scale)[s];
@@ -62,7 +56,7 @@ __global__ __launch_bounds__(256) void exposure_accumulate_kernel(const Exposure
 				for (int c = 0; c < 3; ++c) {
 					float dgt = -g[c] / pdf; // tn:1948
 					if (!a.train_in_linear_colors) dgt = dgt / train_srgb_to_linear_derivative(target[c]); // tn:1950-1952
-					q[c] = envmap_quantise(((per_ray * dgt) * scale[c]) * kExposureLn2); // tn:1955
+					q[c] = signed_cell_quantise(((per_ray * dgt) * scale[c]) * kExposureLn2); // tn:1955
 				}
 			}
 		}
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(256) void exposure_accumulate_kernel(const Exposure
 #ifdef NRS_EXPOSURE_NO_PEEL // measurements only (tools/exposure_probe.py): one atomic per lane and channel
 	if (deposits) {
 		#pragma unroll
-		for (int c = 0; c < 3; ++c) if (q[c]) exposure_add(a.cells + 3 * (size_t)img + c, q[c]);
+		for (int c = 0; c < 3; ++c) if (q[c]) cell_add(a.cells + 3 * (size_t)img + c, (unsigned long long)q[c]);
 	}
 #else
 	// peel the wave's distinct images: the first lane left names the image, its lanes are summed across the wave and leave
@@ -86,7 +80,7 @@ __global__ __launch_bounds__(256) void exposure_accumulate_kernel(const Exposure
 		for (int c = 0; c < 3; ++c) sum[c] = wave_sum(mine ? q[c] : 0ll);
 		// lanes 0..2 add the three channels: one atomic instruction per image and wave, on 24 contiguous bytes
 		const long long mine_sum = lane == 0u ? sum[0] : (lane == 1u ? sum[1] : sum[2]);
-		if (lane < 3u && mine_sum) exposure_add(a.cells + 3 * (size_t)cur + lane, mine_sum);
+		if (lane < 3u && mine_sum) cell_add(a.cells + 3 * (size_t)cur + lane, (unsigned long long)mine_sum);
 		left &= ~__ballot(mine);
 	}
 #endif

@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "nrs_cells.h"
+
 #if defined(__HIPCC__)
 #define NRS_EXPOSURE_FN __host__ __device__ __forceinline__
 #else
@@ -33,7 +35,7 @@ inline ExposureStepConsts exposure_step_consts(uint32_t n_images, float beta1, f
 
 // adam_optimizer.h:41-44 on one channel of one image (tn:3892-3898): an element whose cell is zero still steps
 NRS_EXPOSURE_FN void exposure_adam(const ExposureStepConsts& k, long long cell, float& value, float& m, float& v) {
-	const float g = (float)((double)cell * 0x1p-32) * k.pcls + value * k.l2_reg;
+	const float g = signed_cell_to_float(cell) * k.pcls + value * k.l2_reg;
 	m = k.beta1 * m + (1.0f - k.beta1) * g;
 	v = k.beta2 * v + (1.0f - k.beta2) * (g * g);
 	value -= k.alr * (m / (sqrtf(v) + k.epsilon));

@@ -1,6 +1,6 @@
-// nrs_loss.cuh -- the per-channel loss of the training path, the colour curves it is evaluated behind and the fixed-point deposit of a gradient, each stated once: the
-// ray loss (nrs_train.hip), the environment map's gradient (nrs_envmap.hip) and the exposure's (nrs_exposure.hip) read the same text, so the same inputs give them the
-// same bits.
+// nrs_loss.cuh -- the per-channel loss of the training path and the colour curves it is evaluated behind, each stated once: the ray loss (nrs_train.hip), the
+// environment map's gradient (nrs_envmap.hip) and the exposure's (nrs_exposure.hip) read the same text, so the same inputs give them the same bits.  (The fixed-point
+// cells the two gradients are deposited in: nrs_cells.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/nrs.h"
@@ -29,15 +29,6 @@ __device__ __forceinline__ void loss_and_gradient(uint32_t type, float target, f
 		case NRS_LOSS_LOG_L1: { const float div = fabsf(diff) + 1.0f; loss = logf(div); grad = copysignf(1.0f / div, diff); break; }
 		default: loss = diff * diff; grad = 2.0f * diff; break; // L2
 	}
-}
-
-// One deposit into a signed 64-bit fixed-point cell (include/nrs.h, "the environment map", DEPOSIT; per-image exposure shares it): 0 -- nothing to add -- unless
-// finite and non-zero; clamped to +-512, scaled by 2^32 (exact), rounded to nearest even.
-constexpr float kEnvmapDepositClamp = 512.0f;     // 2^21 rays x 512 x 2^32 = 2^62: a cell never wraps
-constexpr float kEnvmapCellScale = 4294967296.0f; // 2^32
-__device__ __forceinline__ long long envmap_quantise(float p) {
-	if (!(fabsf(p) <= 3.402823466e38f) || p == 0.0f) return 0ll; // NaN, +-inf, +-0
-	return (long long)rintf(fminf(fmaxf(p, -kEnvmapDepositClamp), kEnvmapDepositClamp) * kEnvmapCellScale);
 }
 
 } // namespace nrs

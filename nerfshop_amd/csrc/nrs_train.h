@@ -10,6 +10,12 @@ namespace nrs {
 constexpr uint32_t kTrainMaxRays = 1u << 21; // 2^21 rays x NERF_STEPS = 2^31 samples: every sum of counts fits 32 bits
 constexpr uint32_t kRayAuxWords = 12;        // nrs_ray_loss_ex's record per slot: g[3], T, target[3], C[3], n, M
 constexpr uint32_t kTrainScanTile = 1024;    // rays per tile of the scan over the per-ray counts
+// The live slots of a step: the generator's ray counter (nrs_training_samples' d_counters[0]), never more than n_rays.  Whatever is indexed by slot -- the loss, the
+// environment map, the exposure, the error map -- stops here.
+__device__ __forceinline__ uint32_t live_slots(const uint32_t* ray_counter, uint32_t n_rays) {
+	const uint32_t emitted = *ray_counter;
+	return emitted < n_rays ? emitted : n_rays;
+}
 inline uint32_t train_scan_tiles(uint32_t n_rays) { return (n_rays + kTrainScanTile - 1u) / kTrainScanTile; }
 // what the scan keeps behind a view's per-ray arrays: two sums per tile, then the two totals
 inline size_t train_scan_words(uint32_t n_rays) { return 2 * (size_t)train_scan_tiles(n_rays) + 2; }

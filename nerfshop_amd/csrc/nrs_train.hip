@@ -251,7 +251,7 @@ __device__ __forceinline__ Sample load_sample(const DeviceModel& m, const RayLos
 	q.alpha = 1.f - q.rest;
 	return q;
 }
-__device__ __forceinline__ uint32_t live_rays(const RayLossArgs& a) { return a.ray_counter ? min(*a.ray_counter, a.n_rays) : a.n_rays; }
+__device__ __forceinline__ uint32_t live_rays(const RayLossArgs& a) { return a.ray_counter ? live_slots(a.ray_counter, a.n_rays) : a.n_rays; }
 
 // The ray's target, the background behind a ray that was not stopped, loss_and_gradient, and the ray's row of the workspace (tn:1789-1828, :1847-1858)
 __device__ __forceinline__ void finish_ray(const RayLossArgs& a, uint32_t i, uint32_t M, uint32_t n, f3 C, float T) {

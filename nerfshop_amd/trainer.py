@@ -44,6 +44,93 @@ class ErrorMapSchedule:
         self.resolution, self.last_rays, self.last_loss = None, None, None
 
 
+class _RayBuffers:
+    """Every tensor of a step whose size follows n_rays, made here and re-made only when n_rays changes: the five of NerfNetwork.ray_loss_buffers; aux [n, RAY_AUX_WORDS],
+    the per-slot record of the loss that both side gradients read, when there is a side parameter; the envmap's background_linear and footprint; the exposure's target
+    and scale.  What a side parameter reads by slot is made zero: rows at or past the ray counter are never written."""
+
+    def __init__(self, net, n_rays, max_samples, device, envmap, exposure):
+        def zeros(width, dtype):
+            return torch.zeros((n_rays, width), dtype=dtype, device=device)
+        self.n_rays = n_rays
+        self.numsteps_out, self.coords_out, self.dl, self.loss, self.counter = net.ray_loss_buffers(n_rays, max_samples, device=device)
+        self.aux = zeros(_abi.RAY_AUX_WORDS, torch.int32) if envmap or exposure else None
+        self.background_linear, self.footprint = (zeros(3, torch.float32), zeros(4, torch.int32)) if envmap else (None, None)
+        self.target, self.scale = (zeros(4, torch.float32), zeros(4, torch.int32)) if exposure else (None, None)
+
+
+class _Envmap:
+    """What the trainer `t` knows about its environment map (m_envmap), whose state is t's own -- t.envmap, t.envmap_loss_type (base.json's envmap loss),
+    t.envmap_learning_rate and t.envmap_decay (its schedule): in front of the loss the background a ray sees through the live texels, and the lookup's footprint for
+    the gradient; behind the loss the gradient's deposits; behind the network's step the texels'."""
+
+    def __init__(self, t, envmap, loss_type, learning_rate, decay):
+        if envmap is not None and not isinstance(envmap, runtime.Envmap):
+            envmap = runtime.Envmap(t.ctx, int(envmap[0]), int(envmap[1]))
+        if envmap is not None and envmap.ctx is not t.ctx:
+            raise NrsError("Trainer: the envmap belongs to another context")
+        self.t, t.envmap, t.envmap_loss_type, t.envmap_learning_rate, t.envmap_decay = t, envmap, int(loss_type), float(learning_rate), tuple(decay)
+
+    def before_loss(self, b, rays, ray_indices, counter, background):
+        self.t.envmap.background(rays, ray_indices, counter, background=background, default_background=tuple(self.t.loss_params.background),
+                                 out=(b.background_linear, b.footprint))
+
+    def after_loss(self, b, ray_indices, counter, xy_pdf):
+        t, p = self.t, self.t.loss_params
+        acc = _abi.EnvmapAccumulateParams(p.loss_type, t.envmap_loss_type, p.loss_scale, p.train_in_linear_colors)
+        t.envmap.accumulate(acc, counter, b.numsteps_out, b.aux, b.background_linear, b.footprint, n_rays=b.n_rays)
+
+    def after_optimizer(self):
+        self.t.envmap.step(loss_scale=float(self.t.loss_params.loss_scale), lr=self.t.current_envmap_learning_rate())
+
+
+class _Exposure:
+    """What the trainer `t` knows about its per-image exposures (m_nerf.training.optimize_exposure), whose state is t's own -- t.exposure (None, a runtime.Exposure, or
+    True until the first dataset step, which knows the number of images, makes one), t.exposure_l2_reg, t.cam_update_every: what a dataset step and a step refuse; in
+    front of the loss the targets by slot (the gather and the image's 2^exposure in one pass; the scale is kept for the gradient); behind the loss the gradient's
+    deposits; and the camera update of train_nerf (src/testbed_nerf.cu:3834-3915) on the step on which cam_update_every of them have been accumulated, with the
+    network's learning rate."""
+
+    def __init__(self, t, exposure, l2_reg, update_every):
+        if exposure is not None and exposure is not True and not isinstance(exposure, runtime.Exposure):
+            raise NrsError("Trainer: exposure must be None, True or a runtime.Exposure")
+        if isinstance(exposure, runtime.Exposure) and exposure.ctx is not t.ctx:
+            raise NrsError("Trainer: the exposure belongs to another context")
+        if int(update_every) < 1:
+            raise NrsError("Trainer: cam_update_every must be at least 1")
+        self.t, t.exposure, t.exposure_l2_reg, t.cam_update_every, self.steps_since_update = t, exposure, float(l2_reg), int(update_every), 0
+
+    def before_dataset_step(self, dataset, error_map):
+        t = self.t
+        if error_map is not None and error_map.sample_images and error_map.sample_pixels:
+            raise NrsError("Trainer.step_dataset: exposure with sample_images and sample_pixels: the exposure's gradient is divided by the pixel's density alone, "
+                           "but the dataset writes the product of the image's and the pixel's, and the two cannot be told apart")
+        if t.exposure is True:
+            t.exposure = runtime.Exposure(t.ctx, dataset.n_images, _abi.ExposureParams(l2_reg=t.exposure_l2_reg, steps_between_updates=t.cam_update_every))
+        elif t.exposure.n_images != dataset.n_images:
+            raise NrsError("Trainer.step_dataset: the exposure was made for another number of images")
+
+    def before_step(self, pixels):
+        if pixels is None:
+            raise NrsError("Trainer.step: with an exposure, `pixels` must name each ray's image")
+        if self.t.exposure is True:
+            raise NrsError("Trainer.step: exposure=True is made by the first step_dataset, which knows the number of images; pass a runtime.Exposure to step() directly")
+
+    def before_loss(self, b, ray_indices, counter, pixels, target_rgba):
+        self.t.exposure.targets(ray_indices, counter, pixels, target_rgba, out=(b.target, b.scale))
+
+    def after_loss(self, b, ray_indices, counter, xy_pdf):
+        p = self.t.loss_params
+        self.t.exposure.accumulate(_abi.ExposureAccumulateParams(p.loss_scale, p.train_in_linear_colors), counter, ray_indices, b.numsteps_out, b.aux, b.scale,
+                                   xy_pdf=xy_pdf, n_rays=b.n_rays)
+
+    def after_optimizer(self):
+        self.steps_since_update += 1
+        if self.steps_since_update >= self.t.cam_update_every:
+            self.t.exposure.step(loss_scale=float(self.t.loss_params.loss_scale), lr=self.t.current_learning_rate())
+            self.steps_since_update = 0
+
+
 class Trainer:
     """A NerfNetwork without cell records, an Optimizer bound to it, one persistent gradient buffer (zero between steps: the optimiser clears what it reads) and
     base.json's learning-rate schedule.
@@ -65,21 +152,9 @@ class Trainer:
         gradient; the step on which cam_update_every of them have been accumulated runs Exposure.step with the network's current learning rate.  exposures() returns
         the values: a training view is displayed with the tonemap's exposure + exposures()[view]."""
         self.ctx, self.lib, self.desc = ctx, ctx.lib, desc
-        if exposure is not None and exposure is not True and not isinstance(exposure, runtime.Exposure):
-            raise NrsError("Trainer: exposure must be None, True or a runtime.Exposure")
-        if isinstance(exposure, runtime.Exposure) and exposure.ctx is not ctx:
-            raise NrsError("Trainer: the exposure belongs to another context")
-        if int(cam_update_every) < 1:
-            raise NrsError("Trainer: cam_update_every must be at least 1")
-        self.exposure, self.exposure_l2_reg, self.cam_update_every = exposure, float(exposure_l2_reg), int(cam_update_every)
-        self._exposure_bufs, self._steps_since_cam_update = None, 0
-        if envmap is not None and not isinstance(envmap, runtime.Envmap):
-            envmap = runtime.Envmap(ctx, int(envmap[0]), int(envmap[1]))
-        if envmap is not None and envmap.ctx is not ctx:
-            raise NrsError("Trainer: the envmap belongs to another context")
-        self.envmap, self.envmap_loss_type = envmap, int(envmap_loss_type)
-        self.envmap_learning_rate, self.envmap_decay = float(envmap_learning_rate), tuple(envmap_decay)
-        self._envmap_bufs = None
+        self._expo = _Exposure(self, exposure, exposure_l2_reg, cam_update_every)  # (each sets its part of the trainer's state)
+        self._env = _Envmap(self, envmap, envmap_loss_type, envmap_learning_rate, envmap_decay)
+        self._bufs = None  # _RayBuffers: made by the first step
         self.network = runtime.NerfNetwork(ctx, desc, cell_cache_bytes=0)  # no cell-record cache: it would be rebuilt after every step
         self.optimizer = runtime.Optimizer(ctx, network=self.network, params=adam)
         n = self.optimizer.n_params
@@ -93,7 +168,6 @@ class Trainer:
         self.training_step = 0
         self.n_rays_total = 0  # m_nerf.training.n_rays_total: rays drawn from a dataset so far (step_dataset)
         self._out16 = torch.empty((self.max_samples, 16), dtype=torch.float16, device=dev)
-        self._loss_bufs = None
         self._grid_update = _abi.GridUpdate()
         self._grid_update.max_cascade, self._grid_update.ema_step = int(max_cascade), 0
         self._grid_update.rng_state, self._grid_update.rng_inc = runtime.rng_seed(seed)
@@ -142,60 +216,38 @@ class Trainer:
 
     def _step(self, rays, target_rgba, jitter, background, after_loss, pixels=None, xy_pdf=None):
         """step(); after_loss(ray_counter, ray_indices, loss), if given, runs between the ray loss and the backward pass and may rewrite the per-slot losses in place."""
-        net = self.network
-        n_rays = int(rays.shape[0])
+        net, n_rays = self.network, int(rays.shape[0])
         if tuple(target_rgba.shape) != (n_rays, 4):
             raise NrsError("Trainer.step: target_rgba must be [n_rays, 4]")
-        expo = self.exposure
-        if expo is not None:
-            if pixels is None:
-                raise NrsError("Trainer.step: with an exposure, `pixels` must name each ray's image")
-            if expo is True:
-                raise NrsError("Trainer.step: exposure=True is made by the first step_dataset, which knows the number of images; pass a runtime.Exposure to step() directly")
+        env, expo = self._env if self.envmap is not None else None, self._expo if self.exposure is not None else None
+        sides = [side for side in (env, expo) if side]  # in the order of their calls behind the loss
+        if expo:
+            expo.before_step(pixels)
         coords, numsteps, ray_indices, counters = net.training_samples(None, rays, jitter, self.cone_angle_constant, self.max_samples)
         net.inference_strided(None, coords, self._out16)
+        if self._bufs is None or self._bufs.n_rays != n_rays:
+            self._bufs = _RayBuffers(net, n_rays, self.max_samples, rays.device, bool(env), bool(expo))
+        b, counter = self._bufs, counters[:1]
         # the loss reads its per-ray inputs by ray SLOT: gather them with the generator's indices (slots at or past counters[0] are not live)
         slots = ray_indices.to(torch.int64)
-        if expo is None:
-            target = target_rgba.index_select(0, slots)
-        else:  # the gather and the image's 2^exposure in one pass; the scale is kept for the gradient
-            if self._exposure_bufs is None or self._exposure_bufs[0].shape[0] != n_rays:
-                self._exposure_bufs = (torch.zeros((n_rays, 4), dtype=torch.float32, device=rays.device), torch.zeros((n_rays, 4), dtype=torch.int32, device=rays.device),
-                                       None if self.envmap is not None else torch.zeros((n_rays, _abi.RAY_AUX_WORDS), dtype=torch.int32, device=rays.device))
-            target, scale = expo.targets(ray_indices, counters[:1], pixels, target_rgba, out=self._exposure_bufs[:2])
+        if expo:
+            expo.before_loss(b, ray_indices, counter, pixels, target_rgba)
+        target = b.target if expo else target_rgba.index_select(0, slots)
         bg = None if background is None else background.index_select(0, slots)
-        if self._loss_bufs is None or self._loss_bufs[0].shape[0] != n_rays:
-            self._loss_bufs = net.ray_loss_buffers(n_rays, self.max_samples, device=rays.device)
-        env, bg_linear, aux = self.envmap, None, None if expo is None else self._exposure_bufs[2]
-        if env is not None:  # the background the ray sees through the envmap's live texels, and the lookup's footprint for the gradient
-            if self._envmap_bufs is None or self._envmap_bufs[0].shape[0] != n_rays:
-                self._envmap_bufs = (torch.zeros((n_rays, 3), dtype=torch.float32, device=rays.device), torch.zeros((n_rays, 4), dtype=torch.int32, device=rays.device),
-                                     torch.zeros((n_rays, _abi.RAY_AUX_WORDS), dtype=torch.int32, device=rays.device))
-            aux = self._envmap_bufs[2]
-            p = self.loss_params
-            bg_linear, footprint = env.background(rays, ray_indices, counters[:1], background=bg, default_background=tuple(p.background), out=self._envmap_bufs[:2])
-        numsteps_out, coords_out, dl, loss, _ = net.ray_loss(None, self.loss_params, numsteps, coords, self._out16, target, background=bg, ray_counter=counters[:1],
-                                                             out=self._loss_bufs, background_linear=bg_linear, aux=aux)
+        if env:
+            env.before_loss(b, rays, ray_indices, counter, bg)
+        net.ray_loss(None, self.loss_params, numsteps, coords, self._out16, target, background=bg, ray_counter=counter,
+                     out=(b.numsteps_out, b.coords_out, b.dl, b.loss, b.counter), background_linear=b.background_linear, aux=b.aux)
         if after_loss is not None:
-            after_loss(counters[:1], ray_indices, loss)
-        if env is not None:
-            acc = _abi.EnvmapAccumulateParams(p.loss_type, self.envmap_loss_type, p.loss_scale, p.train_in_linear_colors)
-            env.accumulate(acc, counters[:1], numsteps_out, aux, bg_linear, footprint, n_rays=n_rays)
-        if expo is not None:
-            lp = self.loss_params
-            expo.accumulate(_abi.ExposureAccumulateParams(lp.loss_scale, lp.train_in_linear_colors), counters[:1], ray_indices, numsteps_out, aux, scale, xy_pdf=xy_pdf,
-                            n_rays=n_rays)
-        net.backward(None, coords_out, dl, self.grad, None, accumulate=True)
+            after_loss(counter, ray_indices, b.loss)
+        for side in sides:
+            side.after_loss(b, ray_indices, counter, xy_pdf)
+        net.backward(None, b.coords_out, b.dl, self.grad, None, accumulate=True)
         self.optimizer.step(self.grad, loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate(), zero_grad=True)
-        if env is not None:
-            env.step(loss_scale=float(self.loss_params.loss_scale), lr=self.current_envmap_learning_rate())
-        if expo is not None:  # the camera update of train_nerf (src/testbed_nerf.cu:3834-3915): every cam_update_every steps, with the network's learning rate
-            self._steps_since_cam_update += 1
-            if self._steps_since_cam_update >= self.cam_update_every:
-                expo.step(loss_scale=float(self.loss_params.loss_scale), lr=self.current_learning_rate())
-                self._steps_since_cam_update = 0
+        for side in sides:
+            side.after_optimizer()
         self.training_step += 1
-        return loss.sum()
+        return b.loss.sum()
 
     def step_dataset(self, dataset, n_rays=4096, snap=True, random_bg=True, error_map=None):
         """One training step on n_rays pixels of a runtime.Dataset: dataset.rays (image and pixel selection, the pixel's camera, lens distortion; the target colour and
@@ -206,19 +258,12 @@ class Trainer:
         from the schedule, when no step has passed since the last build; the rays are drawn from the CDFs once there are valid ones and the schedule asks for it; every
         ray's loss is deposited after the ray loss (the returned loss is then the sum of loss / pdf, the loss the reference reports); and once steps_between steps have
         passed the CDFs are rebuilt and steps_between grows.  All on the device; with both sampling switches off the step computes what it computes without a schedule."""
-        u = self._grid_update
-        if self.exposure is not None:
-            if error_map is not None and error_map.sample_images and error_map.sample_pixels:
-                raise NrsError("Trainer.step_dataset: exposure with sample_images and sample_pixels: the exposure's gradient is divided by the pixel's density alone, "
-                               "but the dataset writes the product of the image's and the pixel's, and the two cannot be told apart")
-            if self.exposure is True:
-                self.exposure = runtime.Exposure(self.ctx, dataset.n_images,
-                                                 _abi.ExposureParams(l2_reg=self.exposure_l2_reg, steps_between_updates=self.cam_update_every))
-            elif self.exposure.n_images != dataset.n_images:
-                raise NrsError("Trainer.step_dataset: the exposure was made for another number of images")
+        u, expo = self._grid_update, self.exposure is not None
+        if expo:
+            self._expo.before_dataset_step(dataset, error_map)
+        draw = dict(n_rays=n_rays, n_rays_total=self.n_rays_total, rng=(u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg)
         if error_map is None:
-            rays, jitter, target, background, pixels = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg,
-                                                                    want_pixels=self.exposure is not None)
+            rays, jitter, target, background, pixels = dataset.rays(**draw, want_pixels=expo)
             loss = self.step(rays, target, jitter=jitter, background=background, pixels=pixels)
         else:
             em = error_map
@@ -226,16 +271,14 @@ class Trainer:
                 em.resolution = dataset.error_map_resolution(em.steps_between, n_rays)
                 dataset.error_map_reset(*em.resolution)
             by_error = (em.sample_images and em.builds > 0, em.sample_pixels and em.builds > 0)  # (the reference hands the CDFs over only once is_cdf_valid)
-            rays, jitter, target, background, pixels, xy, pdf = dataset.rays(n_rays, self.n_rays_total, (u.rng_state, u.rng_inc), snap=snap, random_bg=random_bg,
-                                                                             by_error=by_error)
+            rays, jitter, target, background, pixels, xy, pdf = dataset.rays(**draw, by_error=by_error)
             em.last_rays = (xy, pixels, pdf)
 
             def accumulate(ray_counter, ray_indices, loss):
                 em.last_loss = (ray_counter.clone(), ray_indices.clone(), loss.clone()) if em.keep_last else None
                 dataset.error_map_accumulate(n_rays, ray_counter, ray_indices, loss, xy, pixels, pdf=pdf, loss_weighted=loss)
             # the exposure's divisor is xy_pdf alone (src/testbed_nerf.cu:1948): with images drawn uniformly the dataset's pdf is exactly that
-            xy_pdf = pdf if self.exposure is not None and by_error[1] else None
-            loss = self._step(rays, target, jitter, background, accumulate, pixels if self.exposure is not None else None, xy_pdf)
+            loss = self._step(rays, target, jitter, background, accumulate, pixels if expo else None, pdf if expo and by_error[1] else None)
             em.steps_since += 1
             if em.steps_since >= em.steps_between:
                 dataset.error_map_build_cdfs()
@@ -281,8 +324,5 @@ class Trainer:
                 dataset.mark_untrained(self.network, clear_visible=True)
             if self.training_step % int(grid_every) == 0:
                 self.update_density_grid()
-            if error_map is None:
-                losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg))
-            else:
-                losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg, error_map=error_map))
+            losses.append(self.step_dataset(dataset, n_rays, snap=snap, random_bg=random_bg, error_map=error_map))
         return losses

@@ -13,85 +13,27 @@ import numpy as np
 import pytest
 import torch
 
+from training_rig import N_IMAGES, N_RAYS, RES, after_step, bits, by_hand, envmap_state, make_rig, make_trainer, step_rays
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-W, H, N_IMAGES, N_RAYS, RES = 16, 12, 4, 256, (16, 8)
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def rig(built):
-    from nerfshop_amd import _abi, runtime, synth
-    ctx = runtime.Context(0)
-    desc = synth.model_desc(log2_hashmap_size=14)
-    focal = 0.5 * W / math.tan(0.5 * synth.CAMERA_ANGLE_X)
-    ds = runtime.Dataset(ctx, N_IMAGES, W, H)
-    colours = [(230, 160, 60), (60, 200, 120), (90, 110, 240), (200, 200, 200)]
-    for k in range(N_IMAGES):
-        img = np.empty((H, W, 4), np.uint8)
-        img[..., :3], img[..., 3] = colours[k], 255    # opaque: the target is the image's colour whatever lies behind it
-        ds.set_image(k, img)
-        cam = _abi.TrainingCamera()
-        cam.xform_start[:] = cam.xform_end[:] = synth.orbit_camera(40.0 + 90.0 * k).tolist()
-        cam.focal_length[:], cam.principal_point[:] = (focal, focal), (0.5, 0.5)
-        ds.set_camera(k, cam)
-    return ctx, desc, ds, synth.density_grid(1)
-
-
-def make_trainer(rig, envmap=RES, **kw):
-    from nerfshop_amd.trainer import Trainer
-    ctx, desc, _, grid = rig
-    return Trainer(ctx, desc, seed=11, density_grid=grid, max_samples=1 << 14, envmap=envmap, **kw)
-
-
-def step_rays(rig, trainer):
-    """the rays Trainer.step_dataset would draw at the trainer's state"""
-    u = trainer._grid_update
-    rays, jitter, target, background, _ = rig[2].rays(N_RAYS, trainer.n_rays_total, (u.rng_state, u.rng_inc), snap=True, random_bg=True, want_pixels=False)
-    return rays, jitter, target, background
-
-
-def by_hand(t, rays, target, jitter, background):
-    """the calls of Trainer._step with an envmap, in its order, on the trainer's own objects"""
-    from nerfshop_amd import _abi
-    net, env, p = t.network, t.envmap, t.loss_params
-    n = int(rays.shape[0])
-    coords, numsteps, ray_indices, counters = net.training_samples(None, rays, jitter, t.cone_angle_constant, t.max_samples)
-    net.inference_strided(None, coords, t._out16)
-    slots = ray_indices.to(torch.int64)
-    target_s, bg_s = target.index_select(0, slots), background.index_select(0, slots)
-    bg_linear, footprint = env.background(rays, ray_indices, counters[:1], background=bg_s, default_background=tuple(p.background))
-    aux = torch.zeros((n, _abi.RAY_AUX_WORDS), dtype=torch.int32, device=rays.device)
-    numsteps_out, coords_out, dl, loss, _ = net.ray_loss(None, p, numsteps, coords, t._out16, target_s, background=bg_s, ray_counter=counters[:1],
-                                                         background_linear=bg_linear, aux=aux)
-    acc = _abi.EnvmapAccumulateParams(p.loss_type, t.envmap_loss_type, p.loss_scale, p.train_in_linear_colors)
-    env.accumulate(acc, counters[:1], numsteps_out, aux, bg_linear, footprint, n_rays=n)
-    net.backward(None, coords_out, dl, t.grad, None, accumulate=True)
-    t.optimizer.step(t.grad, loss_scale=float(p.loss_scale), lr=t.current_learning_rate(), zero_grad=True)
-    env.step(loss_scale=float(p.loss_scale), lr=t.current_envmap_learning_rate())
-    t.training_step += 1
-    return loss.sum(), dl
-
-
-def bits(x):
-    return x.detach().cpu().numpy().tobytes() if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).tobytes()
-
-
-def envmap_state(t):
-    from nerfshop_amd import _abi
-    return [t.envmap.get(w).tobytes() for w in (_abi.ENVMAP_TEXELS, _abi.ENVMAP_EMA, _abi.ENVMAP_CELLS)]
+    return make_rig()
 
 
 def test_step_is_the_calls_made_by_hand(rig):
-    from nerfshop_amd import _abi, runtime
+    from nerfshop_amd import _abi
     # the default learning rates: loss, dL/doutput and the envmap in every bit; the network's weights counted
-    a, b = make_trainer(rig), make_trainer(rig)
-    rays, jitter, target, background = step_rays(rig, a)
+    a, b = make_trainer(rig, envmap=RES), make_trainer(rig, envmap=RES)
+    rays, jitter, target, background, _ = step_rays(rig[2], a, want_pixels=False)
     loss_a = a.step(rays, target, jitter=jitter, background=background)
-    loss_b, dl_b = by_hand(b, rays, target, jitter, background)
+    loss_b, dl_b = by_hand(b, [0], rays, target, jitter, background)
     torch.cuda.synchronize()
     assert math.isfinite(float(loss_a)) and float(loss_a) > 0 and bits(loss_a) == bits(loss_b)
-    assert bits(a._loss_bufs[2]) == bits(dl_b), "dL/doutput: what the backward pass is given"
+    assert bits(a._bufs.dl) == bits(dl_b), "dL/doutput: what the backward pass is given"
     assert envmap_state(a) == envmap_state(b)
     tex = a.envmap.get(_abi.ENVMAP_TEXELS)
     assert (tex[..., :3] != 0).sum() >= 12 and (tex[..., 3] == 0).all() and not a.envmap.get(_abi.ENVMAP_CELLS).any(), "the envmap moved, alpha did not, the cells are clear"
@@ -99,14 +41,12 @@ def test_step_is_the_calls_made_by_hand(rig):
     wa, wb = a.optimizer.get_state(_abi.OPT_MASTER), b.optimizer.get_state(_abi.OPT_MASTER)
     print(f"default learning rate: {int((wa.view(np.uint32) != wb.view(np.uint32)).sum())} of {wa.size} master weights differ in a bit after one step (float atomics of the backward pass)")
     # network learning rate 0: two steps, everything in every bit
-    a, b = make_trainer(rig, learning_rate=0.0), make_trainer(rig, learning_rate=0.0)
+    a, b = make_trainer(rig, envmap=RES, learning_rate=0.0), make_trainer(rig, envmap=RES, learning_rate=0.0)
     for k in range(2):
-        rays, jitter, target, background = step_rays(rig, a)
+        rays, jitter, target, background, _ = step_rays(rig[2], a, want_pixels=False)
         loss_a = a.step(rays, target, jitter=jitter, background=background)
-        loss_b, _ = by_hand(b, rays, target, jitter, background)
-        for t in (a, b):   # what step_dataset does behind a step
-            t.n_rays_total += N_RAYS
-            t._grid_update.rng_state = runtime.rng_advance(t._grid_update.rng_state, t._grid_update.rng_inc)
+        loss_b, _ = by_hand(b, [0], rays, target, jitter, background)
+        after_step((a, b))
         torch.cuda.synchronize()
         assert bits(loss_a) == bits(loss_b), k
     assert envmap_state(a) == envmap_state(b)
@@ -130,9 +70,9 @@ def test_an_envmap_that_is_never_reached_changes_nothing(rig):
             la, lb = plain.step_dataset(ds, N_RAYS), with_env.step_dataset(ds, N_RAYS)
             torch.cuda.synchronize()
             assert math.isfinite(float(la)) and float(la) > 0 and bits(la) == bits(lb), (lr, k)
-            live = int((with_env._envmap_bufs[2][:, 10] > 0).sum())   # the emitted rays: every one has samples, and rows at or past the counter are never written
-            assert bits(plain._loss_bufs[2]) == bits(with_env._loss_bufs[2]) and bits(plain._loss_bufs[0][:live]) == bits(with_env._loss_bufs[0][:live])
-        aux = with_env._envmap_bufs[2].cpu().numpy().view(np.uint32)
+            live = int((with_env._bufs.aux[:, 10] > 0).sum())   # the emitted rays: every one has samples, and rows at or past the counter are never written
+            assert bits(plain._bufs.dl) == bits(with_env._bufs.dl) and bits(plain._bufs.numsteps_out[:live]) == bits(with_env._bufs.numsteps_out[:live])
+        aux = with_env._bufs.aux.cpu().numpy().view(np.uint32)
         assert (aux[:, 11] <= aux[:, 10]).all() and (aux[:, 10] > 0).sum() >= 8, "rays were emitted"
         n, M = aux[:, 10], aux[:, 11]
         T = aux[:, 3].copy().view(f32)
@@ -148,7 +88,7 @@ def test_the_envmap_learns_the_background(rig):
     """With the network's learning rate 0 only the envmap can lower the loss: over 32 steps on flat-coloured opaque images seen through a network that is still half
     transparent, the mean loss of the last 8 steps is below that of the first 8."""
     from nerfshop_amd import _abi
-    t = make_trainer(rig, learning_rate=0.0)
+    t = make_trainer(rig, envmap=RES, learning_rate=0.0)
     before = t.optimizer.get_state(_abi.OPT_MASTER).tobytes()
     losses = torch.stack([t.step_dataset(rig[2], N_RAYS, random_bg=False) for _ in range(32)]).cpu().numpy()
     assert np.isfinite(losses).all() and (losses > 0).all()
@@ -163,7 +103,7 @@ def test_the_envmap_learns_the_background(rig):
 def test_evaluate_renders_the_exported_texels(rig):
     from nerfshop_amd import runtime
     ctx, desc, ds, _ = rig
-    t = make_trainer(rig)
+    t = make_trainer(rig, envmap=RES)
     for _ in range(4):
         t.step_dataset(ds, N_RAYS, random_bg=False)
     summary, records = t.evaluate(ds, spp=2)

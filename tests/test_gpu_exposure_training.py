@@ -16,93 +16,15 @@ import torch
 import envmap_ref
 import exposure_ref as ref
 
+from training_rig import N_IMAGES, N_RAYS, after_step, bits, by_hand, exposure_state, make_dataset, make_rig, make_trainer, new_exposure, step_rays
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-W, H, N_IMAGES, N_RAYS = 16, 12, 4, 256
 f32 = np.float32
-
-
-def make_dataset(ctx, colours):
-    from nerfshop_amd import _abi, runtime, synth
-    focal = 0.5 * W / math.tan(0.5 * synth.CAMERA_ANGLE_X)
-    ds = runtime.Dataset(ctx, len(colours), W, H)
-    for k, colour in enumerate(colours):
-        img = np.empty((H, W, 4), np.uint8)
-        img[..., :3], img[..., 3] = colour, 255    # opaque: the target is the image's colour whatever lies behind it
-        ds.set_image(k, img)
-        cam = _abi.TrainingCamera()
-        cam.xform_start[:] = cam.xform_end[:] = synth.orbit_camera(40.0 + 90.0 * k).tolist()
-        cam.focal_length[:], cam.principal_point[:] = (focal, focal), (0.5, 0.5)
-        ds.set_camera(k, cam)
-    return ds
 
 
 @pytest.fixture(scope="module")
 def rig(built):
-    from nerfshop_amd import runtime, synth
-    ctx = runtime.Context(0)
-    desc = synth.model_desc(log2_hashmap_size=14)
-    ds = make_dataset(ctx, [(230, 160, 60), (60, 200, 120), (90, 110, 240), (200, 200, 200)])
-    return ctx, desc, ds, synth.density_grid(1)
-
-
-def make_trainer(rig, **kw):
-    from nerfshop_amd.trainer import Trainer
-    ctx, desc, _, grid = rig
-    return Trainer(ctx, desc, seed=11, density_grid=grid, max_samples=1 << 14, **kw)
-
-
-def new_exposure(rig, values=None, n_images=N_IMAGES, **params):
-    from nerfshop_amd import _abi, runtime
-    exp = runtime.Exposure(rig[0], n_images, _abi.ExposureParams(**params))
-    if values is not None:
-        exp.set(values)
-    return exp
-
-
-def step_rays(ds, trainer):
-    """the rays Trainer.step_dataset would draw at the trainer's state"""
-    u = trainer._grid_update
-    return ds.rays(N_RAYS, trainer.n_rays_total, (u.rng_state, u.rng_inc), snap=True, random_bg=True, want_pixels=True)
-
-
-def after_step(trainers):
-    """what step_dataset does behind a step"""
-    from nerfshop_amd import runtime
-    for t in trainers:
-        t.n_rays_total += N_RAYS
-        t._grid_update.rng_state = runtime.rng_advance(t._grid_update.rng_state, t._grid_update.rng_inc)
-
-
-def by_hand(t, hand, rays, target, jitter, background, pixels):
-    """the calls of Trainer._step with an exposure, in its order, on the trainer's own objects; hand: the steps accumulated since the last update (a one-element list)"""
-    from nerfshop_amd import _abi
-    net, expo, p = t.network, t.exposure, t.loss_params
-    n = int(rays.shape[0])
-    coords, numsteps, ray_indices, counters = net.training_samples(None, rays, jitter, t.cone_angle_constant, t.max_samples)
-    net.inference_strided(None, coords, t._out16)
-    target_s, scale = expo.targets(ray_indices, counters[:1], pixels, target)
-    bg_s = background.index_select(0, ray_indices.to(torch.int64))
-    aux = torch.zeros((n, _abi.RAY_AUX_WORDS), dtype=torch.int32, device=rays.device)
-    numsteps_out, coords_out, dl, loss, _ = net.ray_loss(None, p, numsteps, coords, t._out16, target_s, background=bg_s, ray_counter=counters[:1], aux=aux)
-    expo.accumulate(_abi.ExposureAccumulateParams(p.loss_scale, p.train_in_linear_colors), counters[:1], ray_indices, numsteps_out, aux, scale, n_rays=n)
-    net.backward(None, coords_out, dl, t.grad, None, accumulate=True)
-    t.optimizer.step(t.grad, loss_scale=float(p.loss_scale), lr=t.current_learning_rate(), zero_grad=True)
-    hand[0] += 1
-    if hand[0] >= t.cam_update_every:
-        expo.step(loss_scale=float(p.loss_scale), lr=t.current_learning_rate())
-        hand[0] = 0
-    t.training_step += 1
-    return loss.sum(), dl
-
-
-def bits(x):
-    return x.detach().cpu().numpy().tobytes() if isinstance(x, torch.Tensor) else np.ascontiguousarray(x).tobytes()
-
-
-def exposure_state(t):
-    from nerfshop_amd import _abi
-    return [t.exposure.get(w).tobytes() for w in (_abi.EXPOSURE_VALUES, _abi.EXPOSURE_M, _abi.EXPOSURE_V, _abi.EXPOSURE_CELLS)] + [t.exposure.step_count()]
+    return make_rig()
 
 
 def test_step_is_the_calls_made_by_hand(rig):
@@ -111,12 +33,12 @@ def test_step_is_the_calls_made_by_hand(rig):
     start = np.random.default_rng(2).uniform(-1.0, 1.0, (N_IMAGES, 3)).astype(f32)
     # the default learning rate, an update on every step: one step, the exposures move
     a, b = (make_trainer(rig, exposure=new_exposure(rig, start), cam_update_every=1) for _ in range(2))
-    rays, jitter, target, background, pixels = step_rays(ds, a)
+    rays, jitter, target, background, pixels = step_rays(ds, a, want_pixels=True)
     loss_a = a.step(rays, target, jitter=jitter, background=background, pixels=pixels)
     loss_b, dl_b = by_hand(b, [0], rays, target, jitter, background, pixels)
     torch.cuda.synchronize()
     assert math.isfinite(float(loss_a)) and float(loss_a) > 0 and bits(loss_a) == bits(loss_b)
-    assert bits(a._loss_bufs[2]) == bits(dl_b), "dL/doutput: what the backward pass is given"
+    assert bits(a._bufs.dl) == bits(dl_b), "dL/doutput: what the backward pass is given"
     assert exposure_state(a) == exposure_state(b)
     values = a.exposures()
     assert a.exposure.step_count() == 1 and (values != start).all() and not a.exposure.get(_abi.EXPOSURE_CELLS).any(), "the exposures moved, the cells are clear"
@@ -125,12 +47,12 @@ def test_step_is_the_calls_made_by_hand(rig):
     a, b = (make_trainer(rig, learning_rate=0.0, exposure=new_exposure(rig, start)) for _ in range(2))
     hand = [0]
     for k in range(17):
-        rays, jitter, target, background, pixels = step_rays(ds, a)
+        rays, jitter, target, background, pixels = step_rays(ds, a, want_pixels=True)
         loss_a = a.step(rays, target, jitter=jitter, background=background, pixels=pixels)
         loss_b, dl_b = by_hand(b, hand, rays, target, jitter, background, pixels)
         after_step((a, b))
         torch.cuda.synchronize()
-        assert bits(loss_a) == bits(loss_b) and bits(a._loss_bufs[2]) == bits(dl_b), k
+        assert bits(loss_a) == bits(loss_b) and bits(a._bufs.dl) == bits(dl_b), k
         assert exposure_state(a) == exposure_state(b), k
         assert a.exposure.step_count() == (1 if k >= 15 else 0), "the update falls on the 16th step"
         assert bool(a.exposure.get(_abi.EXPOSURE_CELLS).any()) == (k != 15), "the cells fill between updates and are clear behind one"
@@ -149,8 +71,8 @@ def test_without_an_exposure_nothing_changes(rig):
         la, lb = plain.step_dataset(ds, N_RAYS), none.step_dataset(ds, N_RAYS)
         torch.cuda.synchronize()
         assert math.isfinite(float(la)) and float(la) > 0 and bits(la) == bits(lb), k
-        assert bits(plain._loss_bufs[2]) == bits(none._loss_bufs[2])
-    assert none.exposure is None and none.exposures() is None and none._exposure_bufs is None
+        assert bits(plain._bufs.dl) == bits(none._bufs.dl)
+    assert none.exposure is None and none.exposures() is None and none._bufs.target is None and none._bufs.scale is None and none._bufs.aux is None
     for which in (_abi.OPT_MASTER, _abi.OPT_PARAMS_FP16):
         assert plain.optimizer.get_state(which).tobytes() == none.optimizer.get_state(which).tobytes()
 
@@ -208,7 +130,7 @@ def test_refusals(rig):
     from nerfshop_amd._abi import NrsError
     ds = rig[2]
     t = make_trainer(rig, exposure=new_exposure(rig))
-    rays, jitter, target, background, pixels = step_rays(ds, t)
+    rays, jitter, target, background, pixels = step_rays(ds, t, want_pixels=True)
     with pytest.raises(NrsError, match="pixels"):
         t.step(rays, target, jitter=jitter, background=background)
     t = make_trainer(rig, exposure=True)

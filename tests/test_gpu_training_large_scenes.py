@@ -172,7 +172,7 @@ def test_step_gathers_by_ray_slot(ctx, desc4):
         slots = ray_indices.cpu().numpy()[:emitted]
         per_ray = np.zeros(n, np.float32)
         has = np.zeros(n, bool)
-        per_ray[idx[slots]] = trainer._loss_bufs[3].cpu().numpy()[:emitted]
+        per_ray[idx[slots]] = trainer._bufs.loss.cpu().numpy()[:emitted]
         has[idx[slots]] = True
         return per_ray, has, float(total), slots
 

@@ -20,6 +20,9 @@ import sys
 
 import torch
 
+import probe_timing
+from probe_timing import alternate
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nerfshop_amd import _abi, runtime, synth  # noqa: E402
@@ -85,15 +88,6 @@ class Rig:
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         self.check(self.lib.nrs_dataset_rays(self.ds, stream, C.byref(self.p), n_rays, *[t.data_ptr() for t in self.out]))
 
-    def time_batch(self, n_rays, launches):
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(launches):
-            self.launch(n_rays)
-        end.record()
-        end.synchronize()
-        return start.elapsed_time(end) * 1e3 / launches   # microseconds per launch
-
 
 def kernel_ab(libs, rounds, launches):
     images = [torch.rand((RES, RES, 4), device=DEV).to(torch.float16) for _ in range(N_IMAGES)]
@@ -109,16 +103,9 @@ def kernel_ab(libs, rounds, launches):
                 if not torch.equal(a.view(torch.int32), b.view(torch.int32)):
                     raise RuntimeError(f"{r.name}: outputs differ from {rigs[0].name}'s")
         for n_rays in RAY_COUNTS:
-            for r in rigs:
-                r.time_batch(n_rays, launches)   # warm-up
-            times = {r.name: [] for r in rigs}
-            for _ in range(rounds):
-                for r in rigs:
-                    times[r.name].append(r.time_batch(n_rays, launches))
             key = f"{'iterative lens' if lens else 'pinhole'}, {n_rays} rays"
-            results[key] = {name: {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)} for name, t in times.items()}
-            for name, t in times.items():
-                print(f"dataset_rays_kernel, {key}, {name}: median {statistics.median(t):.2f} us, min {min(t):.2f}, max {max(t):.2f} over {rounds} rounds of {launches}")
+            candidates = {r.name: (lambda r: lambda: r.launch(n_rays))(r) for r in rigs}
+            results[key] = alternate(candidates, rounds, launches, f"dataset_rays_kernel, {key}", warmup=launches)
     return results
 
 
@@ -149,13 +136,7 @@ def step_ab(rounds, steps, n_rays):
     rays, jitter, target, background, pixels = ds.rays(n_rays, 0, (u.rng_state, u.rng_inc))
 
     def timed(fn):
-        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(steps):
-            fn()
-        end.record()
-        end.synchronize()
-        return start.elapsed_time(end) / steps   # milliseconds per step
+        return probe_timing.timed(fn, steps) * 1e-3   # milliseconds per step
 
     with_dataset = lambda: trainer.step_dataset(ds, n_rays)
     on_rays = lambda: trainer.step(rays, target, jitter=jitter, background=background)

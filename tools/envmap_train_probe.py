@@ -15,11 +15,12 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
 import numpy as np
 import torch
+
+from probe_timing import alternate
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -29,30 +30,6 @@ from nerfshop_amd.trainer import Trainer  # noqa: E402
 DEV = "cuda:0"
 RES = (256, 128)
 W, H, N_IMAGES = 128, 128, 8
-
-
-def timed(fn, calls):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(calls):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / calls   # microseconds per call
-
-
-def alternate(candidates, rounds, calls, title):
-    for fn in candidates.values():
-        timed(fn, max(calls // 4, 1))   # warm-up
-    times = {name: [] for name in candidates}
-    for _ in range(rounds):
-        for name, fn in candidates.items():
-            times[name].append(timed(fn, calls))
-    out = {}
-    for name, t in times.items():
-        out[name] = {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)}
-        print(f"{title}, {name}: median {statistics.median(t):.2f} us, min {min(t):.2f}, max {max(t):.2f} over {rounds} rounds of {calls}")
-    return out
 
 
 def dataset(ctx):

@@ -16,11 +16,12 @@ import ctypes as C
 import json
 import math
 import os
-import statistics
 import sys
 
 import numpy as np
 import torch
+
+import probe_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -69,28 +70,8 @@ def fill(lib, ctx_out, images, cams):
     return ds
 
 
-def timed(fn, launches):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(launches):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / launches   # microseconds per launch
-
-
 def alternate(candidates, rounds, launches, title):
-    for fn in candidates.values():
-        timed(fn, launches)   # warm-up
-    times = {name: [] for name in candidates}
-    for _ in range(rounds):
-        for name, fn in candidates.items():
-            times[name].append(timed(fn, launches))
-    out = {}
-    for name, t in times.items():
-        out[name] = {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)}
-        print(f"{title}, {name}: median {statistics.median(t):.2f} us, min {min(t):.2f}, max {max(t):.2f} over {rounds} rounds of {launches}")
-    return out
+    return probe_timing.alternate(candidates, rounds, launches, title, warmup=launches)   # (a whole batch to warm up)
 
 
 def main():

@@ -16,12 +16,13 @@ import argparse
 import json
 import math
 import os
-import statistics
 import subprocess
 import sys
 
 import numpy as np
 import torch
+
+import probe_timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -32,30 +33,8 @@ DEV = "cuda:0"
 W, H, N_IMAGES = 128, 128, 8
 
 
-def timed(fn, calls, after=None):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(calls):
-        fn()
-    end.record()
-    end.synchronize()
-    if after is not None:
-        after()
-    return start.elapsed_time(end) * 1e3 / calls   # microseconds per call
-
-
 def alternate(candidates, rounds, calls, title, after=None):
-    for fn in candidates.values():
-        timed(fn, max(calls // 4, 1), after)   # warm-up
-    times = {name: [] for name in candidates}
-    for _ in range(rounds):
-        for name, fn in candidates.items():
-            times[name].append(timed(fn, calls, after))
-    out = {}
-    for name, t in times.items():
-        out[name] = {"median_us": statistics.median(t), "min_us": min(t), "max_us": max(t)}
-        print(f"{title}, {name}: median {statistics.median(t):.2f} us, min {min(t):.2f}, max {max(t):.2f} over {rounds} rounds of {calls}", file=sys.stderr)
-    return out
+    return probe_timing.alternate(candidates, rounds, calls, title, after=after, file=sys.stderr)   # (stdout carries the JSON)
 
 
 def kernels(ctx, rounds):
